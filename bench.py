@@ -12,11 +12,14 @@ Workload (BASELINE.json configs[1]): 8 synthetic ScanNet-shape scenes per GPU, 1
 One step = one pass of the hot path over the batch with the points already resident in HBM:
 voxelise -> rulebooks -> backbone -> superpoint pooling -> decoder -> matcher/loss -> backward ->
 (gradient all-reduce when N > 1) -> grad clip + AdamW.  Weak scaling: every rank runs its own 8 scenes.
-Prints ONE JSON line (rank 0).  The line's headline is the fp32 cfg2 measurement; measured right after it in the same process ride
-along (N = 1 only): `fp32_native_mfma` (the same workload on the native fp32 MFMA kernels), `cfg3` (BASELINE.json configs[2]: bf16
-MFMA operands, 16 scenes per GPU), `cfg4` and `cfg5` (configs[3] / [4], one GPU's share each: the six-dataset joint batch, one 1 M-point
-room) and `cpu_baseline`; --no-mfma-line / --no-cfg3 / --no-extra-configs / --no-cpu-baseline skip them.  `tree_hash` stamps the line
+Prints ONE JSON line (rank 0).  The line's headline is the fp32 cfg2 measurement.  A plain run measures only that: set-up, W warm-up
+steps, K timed steps, the line.  With --full, the per-family kernel times and rooflines (`roofline`, `kernels`, `step_roofline`, over
+extra instrumented steps after the timed region) are added, and these blocks are measured right after it in the same process (N = 1
+only): `fp32_native_mfma` (the same workload on the native fp32 MFMA kernels), `cfg3` (BASELINE.json configs[2]: bf16 MFMA operands,
+16 scenes per GPU), `cfg4` and `cfg5` (configs[3] / [4], one GPU's share each: the six-dataset joint batch, one 1 M-point room) and
+`cpu_baseline`; --no-mfma-line / --no-cfg3 / --no-extra-configs / --no-cpu-baseline skip them there.  `tree_hash` stamps the line
 with a hash of the shipped sources (`python bench.py --tree-hash` prints it without a GPU).
+--dump-outputs DIR writes what the last timed step of the headline computed (dump_outputs below) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -45,7 +48,7 @@ def parse():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='cfg2', choices=['cfg2', 'cfg4', 'cfg5'],
-                    help="workload: cfg2 = BASELINE.json configs[1] (the metric's configuration; default; the line also carries cfg3); "
+                    help="workload: cfg2 = BASELINE.json configs[1] (the metric's configuration; default; --full adds cfg3); "
                          "cfg4 = configs[3]'s per-GPU share: the six-dataset joint model, 8 mixed scenes of 100k / 180k / 200k points by "
                          "dataset; cfg5 = configs[4]'s per-GPU share: ONE S3DIS-shape room of 1 M points.  cfg4 / cfg5 print the same "
                          "line shape (value in scenes/s of THAT workload) and never stand in for the headline")
@@ -57,10 +60,10 @@ def parse():
                     help="how the fp32 path forms its products: 'bf16x3' (library default) = three exact bf16 planes per operand, six bf16 "
                          "MFMAs per product, fp32-level error; 'mfma' = native v_mfma_f32_* (round 1-2 headline kernels)")
     ap.add_argument('--no-mfma-line', action='store_true',
-                    help='skip the `fp32_native_mfma` block (the same fp32 workload on the native fp32 MFMA kernels) appended to the default line')
-    ap.add_argument('--no-cfg3', action='store_true', help='skip the cfg3 block (bf16 operands, 16 scenes/GPU) appended to the fp32 line')
+                    help='skip the `fp32_native_mfma` block (the same fp32 workload on the native fp32 MFMA kernels) appended to the --full line')
+    ap.add_argument('--no-cfg3', action='store_true', help='skip the cfg3 block (bf16 operands, 16 scenes/GPU) appended to the fp32 --full line')
     ap.add_argument('--no-extra-configs', action='store_true',
-                    help="skip the cfg4 / cfg5 blocks (BASELINE.json configs[3] / [4] per-GPU shares, fp32) appended to the default line")
+                    help="skip the cfg4 / cfg5 blocks (BASELINE.json configs[3] / [4] per-GPU shares, fp32) appended to the --full line")
     ap.add_argument('--tree-hash', action='store_true', help='print the hash of the shipped source tree (the stamp of every line) and exit; needs no GPU')
     ap.add_argument('--points', type=int, default=100_000)
     ap.add_argument('--voxel-size', type=float, default=0.02)
@@ -76,7 +79,16 @@ def parse():
                          'input gradient, 2 (default here) a chain of their own joined at the end of backward')
     ap.add_argument('--no-prefetch', action='store_true',
                     help="build the next step's voxel grid / rulebooks at the start of that step instead of on a side stream")
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: per-family kernel times / rooflines and the fp32_native_mfma, cfg3, '
+                         'cfg4, cfg5 and cpu_baseline blocks (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step of the headline computed as DIR/<name>.npy: the loss, a '
+                         'fixed sample of the clipped gradient and of the updated parameters (e.g. bench_outputs/, which git ignores)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def _free_port() -> int:
@@ -249,6 +261,30 @@ def git_head() -> str:
         return '?'
 
 
+DUMP_SAMPLE = 1 << 22      # elements kept of a larger array by dump_outputs (2 x 16 MB for the gradient and parameter samples)
+
+
+def dump_outputs(out_dir: str, arrays: dict, sample: int = DUMP_SAMPLE, seed: int = 0) -> dict:
+    """Write each array as out_dir/<name>.npy, flattened, in float32 (float64 where the array is float64).  An array of more than
+    `sample` elements is written as a fixed sample of it: the elements at `sample` positions drawn without replacement by a CPU
+    generator seeded with `seed`, in increasing order -- the same positions on every run and for every array of that length.
+    Returns {name: elements written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    picks, written = {}, {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > sample:
+            if n not in picks:
+                picks[n] = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:sample].sort().values
+            t = t[picks[n].to(t.device)]
+        a = t.to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+        written[name] = int(a.size)
+    return written
+
+
 def _pmc_traffic(bf: bool, workload: str = 'cfg2'):
     """HBM bytes per sparse-convolution (forward / input-gradient) launch from the newest committed PMC pass of this command whose
     source hashes match the library timed here (tools/pmc_bench.sh: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes,
@@ -273,9 +309,11 @@ def _pmc_traffic(bf: bool, workload: str = 'cfg2'):
     return None, (f'{len(files)} PMC file(s) under profiles/ were measured on different kernel sources (or hold no pass of this command): not reported' if files else None)
 
 
-def measure(args, dtype: str, batch: int, rank: int, world: int, dev, fp32_math=None):
+def measure(args, dtype: str, batch: int, rank: int, world: int, dev, fp32_math=None, profile: bool = True, dump_dir=None):
     """W untimed + K timed steps of one configuration (model, optimizer, scenes built here); returns the fields of the JSON line
-    that describe it.  Collective when world > 1 (every rank calls it with the same arguments)."""
+    that describe it.  Collective when world > 1 (every rank calls it with the same arguments).  profile: per-family kernel times
+    over extra instrumented steps after the timed region (`roofline`, `kernels`, `step_roofline`).  dump_dir: rank 0 writes what
+    the last timed step computed there (dump_outputs)."""
     from unidet3d_amd import _lib as L
     from unidet3d_amd import account, precision
     from unidet3d_amd import sparse
@@ -355,7 +393,8 @@ def measure(args, dtype: str, batch: int, rank: int, world: int, dev, fp32_math=
             dist.barrier()
         torch.cuda.synchronize()
 
-    sparse.set_profile_flops(True)      # launches carry their algorithmic flops (pair counts cached during warm-up)
+    if profile:
+        sparse.set_profile_flops(True)  # launches carry their algorithmic flops (pair counts cached during warm-up)
     log(f'[{dtype}] inputs resident, warm-up')
     warm_losses = []
     for i in range(max(args.warmup, 1)):
@@ -373,36 +412,73 @@ def measure(args, dtype: str, batch: int, rank: int, world: int, dev, fp32_math=
     fence()
     dt = time.perf_counter() - t0
     log(f'[{dtype}] timed region done: {dt / args.steps * 1e3:.2f} ms/step')
-    # ---- per-family kernel times: HIP events around every launch of a family, on the stream it runs on, over extra steps
-    # OUTSIDE the timed region (recording ~300 event pairs per step costs ~1 ms/step of host time) ----------------------
-    prof_steps = max(1, min(args.steps, 5))
+    loss_val = float(loss.item())
+    n_vox = int(model._vb.coords.shape[0])
+    if dump_dir and rank == 0:
+        # what a caller of the timed step gets from its last call: the loss, the gradient the optimizer consumed (the flat buffer
+        # every p.grad aliases, clipped) and the parameters after the update -- read before any further step runs
+        n = dump_outputs(dump_dir, {'det_loss': loss, 'grad': bucket.flat, 'params': torch.cat([p.detach().reshape(-1) for p in params])})
+        log(f'[{dtype}] last timed step written to {dump_dir}: ' + ', '.join(f'{k}.npy ({v} values)' for k, v in n.items()))
     overlap_was = sparse.set_wgrad_overlap(0)       # per-family times are those of kernels running alone (overlapped kernels stretch each other)
-    for _, c in families:
-        L.prof_enable(c, True)
-    account.reset()
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    prof = {}
-    acc = account.snapshot()
-    for name, c in families:
-        ms, n, work = L.prof_collect(c)
-        L.prof_enable(c, False)
-        prof[name] = dict(ms=ms, launches=n, flops=work, bytes=acc.get(name, {}).get('bytes', 0.0),
-                          flops_booked=acc.get(name, {}).get('flops', 0.0))
-    sparse.set_profile_flops(False)
+    if profile:
+        # ---- per-family kernel times: HIP events around every launch of a family, on the stream it runs on, over extra steps
+        # OUTSIDE the timed region (recording ~300 event pairs per step costs ~1 ms/step of host time) ----------------------
+        prof_steps = max(1, min(args.steps, 5))
+        for _, c in families:
+            L.prof_enable(c, True)
+        account.reset()
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        prof = {}
+        acc = account.snapshot()
+        for name, c in families:
+            ms, n, work = L.prof_collect(c)
+            L.prof_enable(c, False)
+            prof[name] = dict(ms=ms, launches=n, flops=work, bytes=acc.get(name, {}).get('bytes', 0.0),
+                              flops_booked=acc.get(name, {}).get('flops', 0.0))
+        sparse.set_profile_flops(False)
     sparse.set_wgrad_overlap(overlap_was)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
-    loss_val = float(loss.item())
-    n_vox = int(model._vb.coords.shape[0])
     inflight.clear()
     del model, opt, bucket, params, inputs, samples
     torch.cuda.empty_cache()
 
     bf = dtype == 'bf16'
+    line = {
+        'value': batch * world * args.steps / dt,
+        'unit': 'scenes/s',
+        'ms_per_step': dt / args.steps * 1e3,
+        'dtype': 'bf16' if bf else 'f32',
+        'config': {'workload': ((f'cfg4 (BASELINE.json configs[3], one GPU\'s share): {batch} mixed synthetic scenes/GPU over the six datasets '
+                                 f'({", ".join(f"{n} {p // 1000}k" for n, p in CFG4_SCENES[:batch])} pts), 0.02 m voxels, the joint '
+                                 'unidet3d_1xb8_scannet_s3dis_multiscan_3rscan_scannetpp_arkitscenes model (7-dof head, rotated DIoU), ') if wl == 'cfg4' else
+                                (f'cfg5 (BASELINE.json configs[4], one GPU\'s share): {batch} synthetic S3DIS-shape room/GPU x 1M pts, '
+                                 f'{args.voxel_size} m voxels, unidet3d_1xb8_scannet model, ') if wl == 'cfg5' else
+                                f'{"cfg3" if bf else "cfg2"}: {batch} synthetic ScanNet-shape scenes/GPU x {args.points} pts, '
+                                f'{args.voxel_size} m voxels, unidet3d_1xb8_scannet model, ')
+                               + ('bf16 MFMA operands (sparse conv fwd/dgrad/wgrad, Linear fwd/dX/dW, attention), fp32 accumulate/BN/softmax/optimizer; '
+                                  + ('decoder activations (q/k/v, attention output, MLP hidden tensors, their gradients, LayerNorm copies) are bf16 '
+                                     'tensors in HBM, residual stream / LayerNorm / parameters fp32 (the data flow of the reference\'s autocast); '
+                                     if _bf16_act() else 'fp32 tensors rounded in flight (U3D_BF16_ACT=0); ')
+                                  if bf else ('fp32 (products from three exact bf16 planes per operand on the bf16 matrix pipe, fp32 accumulation, '
+                                              'fp32-level error; --fp32-math mfma = native fp32 MFMAs); ' if x3 else 'fp32 (native fp32 MFMAs); ')) +
+                               'step = voxelise+rulebook+fwd+loss+bwd' + ('' if args.no_optimizer else f'+clip+{args.optimizer}')
+                               + ('' if args.no_prefetch else "; each step's voxelise+rulebook part is queued on a side stream during "
+                                  "the previous step's backward")
+                               + ({0: '', 1: "; conv weight gradients on a side stream next to each layer's input gradient",
+                                   2: '; weight-gradient kernels (sparse conv + Linear) run as a side-stream chain joined at the end of backward'}[overlap_was]),
+                   'front_prefetch': not args.no_prefetch, 'wgrad_overlap': overlap_was, 'fp32_math': ('bf16x3' if x3 else 'mfma') if not bf else None,
+                   'bf16_activations': _bf16_act() if bf else None,
+                   'global_batch': batch * world, 'points_per_scene': args.points if wl == 'cfg2' else n_points_total // max(batch, 1),
+                   'points_per_gpu': n_points_total,
+                   'active_voxels_per_gpu': n_vox, 'parallelism': f'dp{world}', 'loss': loss_val, 'warmup_losses': warm_losses},
+    }
+    if not profile:
+        return line
     # which MFMA peak prices a family = the matrix instruction its kernels ISSUE.  bf16 operands (cfg3): every family multiplies on
     # v_mfma_f32_16x16x32_bf16 -- sparse conv forward / input gradient, the weight gradient (u3d_spconv_wgrad_rows on the bf16 shadows, or
     # u3d_spconv_wgrad_bf16), Linear fwd / dX / dW and attention; only the 16-channel input convolution stays on fp32 MFMAs (round 4
@@ -434,33 +510,7 @@ def measure(args, dtype: str, batch: int, rank: int, world: int, dev, fp32_math=
     traffic, traffic_src = _pmc_traffic(bf, wl)
     fam_ms = sum(v['ms'] for v in prof.values())
     return {
-        'value': batch * world * args.steps / dt,
-        'unit': 'scenes/s',
-        'ms_per_step': dt / args.steps * 1e3,
-        'dtype': 'bf16' if bf else 'f32',
-        'config': {'workload': ((f'cfg4 (BASELINE.json configs[3], one GPU\'s share): {batch} mixed synthetic scenes/GPU over the six datasets '
-                                 f'({", ".join(f"{n} {p // 1000}k" for n, p in CFG4_SCENES[:batch])} pts), 0.02 m voxels, the joint '
-                                 'unidet3d_1xb8_scannet_s3dis_multiscan_3rscan_scannetpp_arkitscenes model (7-dof head, rotated DIoU), ') if wl == 'cfg4' else
-                                (f'cfg5 (BASELINE.json configs[4], one GPU\'s share): {batch} synthetic S3DIS-shape room/GPU x 1M pts, '
-                                 f'{args.voxel_size} m voxels, unidet3d_1xb8_scannet model, ') if wl == 'cfg5' else
-                                f'{"cfg3" if bf else "cfg2"}: {batch} synthetic ScanNet-shape scenes/GPU x {args.points} pts, '
-                                f'{args.voxel_size} m voxels, unidet3d_1xb8_scannet model, ')
-                               + ('bf16 MFMA operands (sparse conv fwd/dgrad/wgrad, Linear fwd/dX/dW, attention), fp32 accumulate/BN/softmax/optimizer; '
-                                  + ('decoder activations (q/k/v, attention output, MLP hidden tensors, their gradients, LayerNorm copies) are bf16 '
-                                     'tensors in HBM, residual stream / LayerNorm / parameters fp32 (the data flow of the reference\'s autocast); '
-                                     if _bf16_act() else 'fp32 tensors rounded in flight (U3D_BF16_ACT=0); ')
-                                  if bf else ('fp32 (products from three exact bf16 planes per operand on the bf16 matrix pipe, fp32 accumulation, '
-                                              'fp32-level error; --fp32-math mfma = native fp32 MFMAs); ' if x3 else 'fp32 (native fp32 MFMAs); ')) +
-                               'step = voxelise+rulebook+fwd+loss+bwd' + ('' if args.no_optimizer else f'+clip+{args.optimizer}')
-                               + ('' if args.no_prefetch else "; each step's voxelise+rulebook part is queued on a side stream during "
-                                  "the previous step's backward")
-                               + ({0: '', 1: "; conv weight gradients on a side stream next to each layer's input gradient",
-                                   2: '; weight-gradient kernels (sparse conv + Linear) run as a side-stream chain joined at the end of backward'}[overlap_was]),
-                   'front_prefetch': not args.no_prefetch, 'wgrad_overlap': overlap_was, 'fp32_math': ('bf16x3' if x3 else 'mfma') if not bf else None,
-                   'bf16_activations': _bf16_act() if bf else None,
-                   'global_batch': batch * world, 'points_per_scene': args.points if wl == 'cfg2' else n_points_total // max(batch, 1),
-                   'points_per_gpu': n_points_total,
-                   'active_voxels_per_gpu': n_vox, 'parallelism': f'dp{world}', 'loss': loss_val, 'warmup_losses': warm_losses},
+        **line,
         'roofline': {'kernel': 'spconv_gmm_k (sparse conv forward + input-gradient, all levels)',
                      'bound': 'mfma', 'achieved': ach, 'peak': x3_ceiling if x3 else peak['conv_gmm'], 'unit': 'TFLOP/s',
                      'frac': ach / (x3_ceiling if x3 else peak['conv_gmm']),
@@ -509,9 +559,9 @@ def main():
     dev = torch.device('cuda', local_dev)
 
     head_batch = args.batch if args.batch is not None else (1 if args.config == 'cfg5' else (16 if args.dtype == 'bf16' else 8))
-    if args.config != 'cfg2':      # the extra blocks (native MFMAs, cfg3, cfg4, cfg5, CPU baseline) belong to the headline line
-        args.no_mfma_line = args.no_cfg3 = args.no_cpu_baseline = args.no_extra_configs = True
-    head = measure(args, args.dtype, head_batch, rank, world, dev)
+    if args.config != 'cfg2' or not args.full:     # the extra blocks (native MFMAs, cfg3, cfg4, cfg5, CPU baseline) belong to the
+        args.no_mfma_line = args.no_cfg3 = args.no_cpu_baseline = args.no_extra_configs = True       # headline line of --full
+    head = measure(args, args.dtype, head_batch, rank, world, dev, profile=args.full, dump_dir=args.dump_outputs)
     # The two extra blocks below belong to the single-GPU line only: at N > 1 every further configuration builds a second model,
     # gradient bucket and communicator inside the same job -- measured with 2 gloo ranks: an ~11 s one-time stall lands somewhere in
     # the second configuration's first steps (3.7 s/step "timed") -- and the scaling runs need the headline only.
@@ -529,7 +579,7 @@ def main():
 
     extra = {}
     if world == 1 and args.dtype == 'fp32' and not args.no_extra_configs:
-        # BASELINE.json configs[3] / [4], one GPU's share each, behind the headline in the same process so that the driver's default run
+        # BASELINE.json configs[3] / [4], one GPU's share each, behind the headline in the same process so that a --full run
         # measures all four GPU configurations.  Same protocol with their own, smaller step counts (stated in the block)
         import copy as _copy
         for name, b in (('cfg4', 8), ('cfg5', 1)):
@@ -543,8 +593,8 @@ def main():
     if rank == 0:
         out = {'metric': METRIC, 'value': head['value'], 'unit': head['unit'], 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
                'ms_per_step': head['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-               'dtype': head['dtype'], 'data': 'synthetic', 'config': head['config'], 'roofline': head['roofline'],
-               'kernels': head['kernels'], 'step_roofline': head['step_roofline']}
+               'dtype': head['dtype'], 'data': 'synthetic', 'config': head['config'],
+               **{k: head[k] for k in ('roofline', 'kernels', 'step_roofline') if k in head}}
         if native is not None:
             out['fp32_native_mfma'] = dict(note='same workload / steps / protocol with U3D_FP32_MATH=mfma (v_mfma_f32_* instead of six bf16 MFMAs per '
                                                 'product), measured right after the headline in the same process',
@@ -563,8 +613,9 @@ def main():
         # the line is long and a log keeps its TAIL: the few numbers a reader wants first are repeated here, last
         out['summary'] = {'scenes_per_s': round(head['value'], 2), 'ms_per_step': round(head['ms_per_step'], 3), 'workload': args.config,
                           'dtype': head['dtype'], 'n_gpus': world,
-                          'roofline_frac': round(head['roofline']['frac'], 4), 'roofline_frac_of_dtype_peak': round(head['roofline'].get('frac_of_dtype_peak', head['roofline']['frac']), 4),
-                          'roofline_traffic_bytes_per_launch': head['roofline']['traffic'],
+                          **({'roofline_frac': round(head['roofline']['frac'], 4),
+                              'roofline_frac_of_dtype_peak': round(head['roofline'].get('frac_of_dtype_peak', head['roofline']['frac']), 4),
+                              'roofline_traffic_bytes_per_launch': head['roofline']['traffic']} if 'roofline' in head else {}),
                           'fp32_native_mfma_scenes_per_s': round(native['value'], 2) if native is not None else None,
                           'cfg3_bf16_scenes_per_s': round(cfg3['value'], 2) if cfg3 is not None else None,
                           'cfg4_joint_scenes_per_s': round(extra['cfg4']['value'], 2) if 'cfg4' in extra else None,

@@ -18,7 +18,40 @@ def test_defaults_are_one_gpu_and_a_run_of_minutes(monkeypatch):
     assert bench.METRIC == json.load(open(os.path.join(ROOT, 'BASELINE.json')))['metric']
     assert a.gpus == 1 and 1 <= a.steps <= 50 and a.warmup >= 1 and a.dtype == 'fp32' and a.points == 100_000
     assert not a.no_prefetch and not a.no_optimizer and not a.no_cpu_baseline and not a.no_cfg3 and not a.no_mfma_line and a.optimizer == 'adamw'
-    assert not a.no_extra_configs and a.config == 'cfg2'          # the default line carries cfg2 (headline), native MFMAs, cfg3, cfg4, cfg5
+    assert not a.no_extra_configs and a.config == 'cfg2'          # --full's line carries cfg2 (headline), native MFMAs, cfg3, cfg4, cfg5
+    assert not a.full and a.dump_outputs is None                  # a plain run times the headline only and writes no arrays
+
+
+def test_full_steps_and_dump_outputs_options(monkeypatch, tmp_path):
+    """--full brings back everything beyond the headline, --steps is the number of timed steps (at least one), and --dump-outputs
+    writes float32 / float64 .npy files, a larger array as a fixed sample of it, at most 64 MB in all for the bench's arrays."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '7', '--warmup', '2', '--full', '--dump-outputs', str(tmp_path / 'o')])
+    a = bench.parse()
+    assert a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs == str(tmp_path / 'o')
+    for bad in (['--steps', '0'], ['--warmup', '-1']):
+        monkeypatch.setattr(sys, 'argv', ['bench.py'] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
+    g = torch.Generator().manual_seed(1)
+    arrays = {'det_loss': torch.tensor(1.5), 'grad': torch.randn(5000, generator=g), 'params': torch.randn(5000, generator=g).double(),
+              'pos': torch.arange(5000.0), 'small': torch.arange(10, dtype=torch.float16)}
+    n1 = bench.dump_outputs(str(tmp_path / 'a'), arrays, sample=1000)
+    n2 = bench.dump_outputs(str(tmp_path / 'b'), arrays, sample=1000)
+    assert n1 == n2 == {'det_loss': 1, 'grad': 1000, 'params': 1000, 'pos': 1000, 'small': 10}
+    out = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in arrays}
+    for k, x in out.items():
+        assert x.dtype == (np.float64 if k == 'params' else np.float32), k
+        assert np.array_equal(x, np.load(tmp_path / 'b' / f'{k}.npy')), k             # the same sample on every run
+    pos = out['pos'].astype(np.int64)
+    assert (np.diff(pos) > 0).all() and pos[0] >= 0 and pos[-1] < 5000            # distinct positions, in order
+    assert np.array_equal(out['grad'], arrays['grad'].numpy()[pos]) and np.array_equal(out['params'], arrays['params'].numpy()[pos])
+    assert out['det_loss'].tolist() == [1.5] and np.array_equal(out['small'], np.arange(10))
+    assert 2 * bench.DUMP_SAMPLE * 4 + 4 <= 64 << 20                  # loss + gradient sample + parameter sample, float32
 
 
 def test_gpus_n_turns_itself_into_a_torchrun_launch(monkeypatch):

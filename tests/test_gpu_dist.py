@@ -211,3 +211,30 @@ def test_bench_gpus_2_launches_itself():
     assert d['n_gpus'] == 2 and d['config']['parallelism'] == 'dp2' and d['config']['global_batch'] == 16
     assert d['steps'] == 2 and d['value'] > 0 and d['scaling'] == 'weak'
     assert abs(d['value'] - 16 / d['ms_per_step'] * 1e3) < 1e-6 * d['value']
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_last_step(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR`: ONE JSON line for exactly K timed steps with the headline fields and
+    nothing measured beyond them (no kernel-family, cfg3 or CPU-baseline blocks without --full), and DIR holds the last timed step's
+    loss, gradient sample and parameter sample as float32 .npy files (64 MB at most)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / 'outputs'
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--points', '20000',
+                          '--dump-outputs', str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['n_gpus'] == 1 and d['unit'] == 'scenes/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f32' and d['ms_per_step'] > 0 and abs(d['value'] - 8 / d['ms_per_step'] * 1e3) < 1e-6 * d['value']
+    for k in ('kernels', 'roofline', 'step_roofline', 'fp32_native_mfma', 'cfg3', 'cfg4', 'cfg5', 'cpu_baseline'):
+        assert k not in d, k
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert set(files) == {'det_loss.npy', 'grad.npy', 'params.npy'}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert float(files['det_loss.npy'][0]) == d['config']['loss'] and files['grad.npy'].size == files['params.npy'].size > 0
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20

@@ -1,6 +1,7 @@
 """The reference's 6-dataset joint config (BASELINE configs[3]) builds into the drop-in modules and its criterion runs on a
 mixed batch that includes rotated (ARKitScenes) ground truth -- CPU, torch ops only (no kernel is launched: the model is only
-constructed, the criterion is device agnostic).  Skipped where /root/reference is absent (the GPU box)."""
+constructed, the criterion is device agnostic).  The config is the reference's ``model=dict(...)`` as captured in
+tests/golden/ref_joint_model_cfg.json (tools/gen_golden_reference.py), loaded through ``load_model_cfg`` like a config file."""
 import os
 
 import pytest
@@ -10,8 +11,16 @@ import unidet3d_amd  # noqa: F401
 from unidet3d_amd.config import build_model, load_model_cfg
 from unidet3d_amd.structures import DepthInstance3DBoxes, InstanceData_
 
-CFG = '/root/reference/configs/unidet3d_1xb8_scannet_s3dis_multiscan_3rscan_scannetpp_arkitscenes.py'
-pytestmark = pytest.mark.skipif(not os.path.exists(CFG), reason='reference configs are only available in the build container')
+GOLDEN_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_joint_model_cfg.json')
+
+
+@pytest.fixture
+def CFG(tmp_path):
+    """the joint config as a config file of the reference's form (``model = dict(...)``), written from the golden fixture"""
+    import json
+    path = tmp_path / 'unidet3d_1xb8_scannet_s3dis_multiscan_3rscan_scannetpp_arkitscenes.py'
+    path.write_text(f'model = {json.load(open(GOLDEN_CFG))!r}\n')
+    return str(path)
 
 
 def test_packaged_joint_config_is_the_reference_fixture():
@@ -19,11 +28,11 @@ def test_packaged_joint_config_is_the_reference_fixture():
     from the reference's joint config."""
     import json
     from unidet3d_amd.config import joint_model_cfg
-    ref = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_joint_model_cfg.json')))
+    ref = json.load(open(GOLDEN_CFG))
     assert joint_model_cfg() == ref
 
 
-def test_joint_config_builds_and_flags_arrive():
+def test_joint_config_builds_and_flags_arrive(CFG):
     cfg = load_model_cfg(CFG)
     m = build_model(cfg)
     assert m.decoder.datasets == ['scannet', 's3dis', 'multiscan', '3rscan', 'scannetpp', 'arkitscenes']
@@ -34,7 +43,7 @@ def test_joint_config_builds_and_flags_arrive():
     assert m.get_dataset('data/arkitscenes/points/x.bin') == 'arkitscenes'
 
 
-def test_joint_criterion_on_mixed_batch_with_rotated_ground_truth():
+def test_joint_criterion_on_mixed_batch_with_rotated_ground_truth(CFG):
     cfg = load_model_cfg(CFG)
     m = build_model(cfg)
     g = torch.Generator().manual_seed(0)
