@@ -35,7 +35,7 @@ typedef void* u3d_stream_t; /* hipStream_t */
 
 /* Bumped with every change of an entry point's argument list; unidet3d_amd/_lib.py refuses a library whose version differs from
  * the one it was written against (a stale .so would misread shifted arguments instead of failing). */
-#define U3D_ABI_VERSION 114
+#define U3D_ABI_VERSION 115
 int u3d_version(void);
 const char* u3d_last_error(void);
 /* How the fp32 matrix kernels (decoder GEMMs, attention, sparse convolutions without U3D_BF16_OPERANDS) multiply:
@@ -506,6 +506,48 @@ int u3d_nms_rotated(const float* boxes, const int32_t* labels, int n, float iou_
  * (+inf / -inf when none, as in the reference); centre = (max+min)/2 and size = max-min are left to the caller. */
 int u3d_trim_boxes(const float* points, int64_t pt_ld, const int32_t* sp_list, const int32_t* sp_offsets, int S,
                    const float* boxes, int nb, int box_dim, float low_thr, float up_thr, float* minmax, u3d_stream_t stream);
+
+/* ---- inference post-processing of a whole batch: one chain of launches, no host read in between ---------------------------
+ * The batched form of softmax -> top-k -> class-wise NMS -> superpoint trimming (UniDet3D.predict_by_feat for every scene of a
+ * batch, each scene with its own dataset's settings).  Per-scene settings are two small device tables:
+ *   meta  int32 [B][U3D_PP_META] = {n queries, C classes, ld (row stride of the probability matrix, elements; >= C),
+ *                                   topk, box_dim (6 | 7), NMS mode (0 BEV IoU = nms3d_normal, 1 3-D IoU of the corner boxes =
+ *                                   aligned_3d_nms, 2 rotated BEV IoU = nms3d; 7-column boxes must use 2), trim (0 | 1), 0}
+ *   fmeta float [B][U3D_PP_FMETA] = {score_thr, iou_thr, low_sp_thr, up_sp_thr}
+ * K is the per-scene stride of every [B][K] array: the entries of scene b start at row b * K.  K <= 3600 (a class segment of
+ * rotated boxes must fit one workgroup's LDS; callers fall back to the per-scene entry points above it).  n * C < 2^31. */
+#define U3D_PP_META 8
+#define U3D_PP_FMETA 4
+/* top k of each scene's n x C probabilities, read in place: element (q, c) of scene b at ((const float*)prob_ptrs[b])[q * ld + c]
+ * (the first C columns of softmax(cls_preds), without copying [:, :-1]).  Probabilities must be >= 0 (their bit patterns order
+ * as uint32).  score / label (flat % C) / query (flat / C) [B][K] in descending score, ties by ascending flat index
+ * (np.argsort(-x, kind='stable')); count [B] = min(topk, K, n * C) entries written per scene. */
+int u3d_topk_segmented(const uint64_t* prob_ptrs, const int32_t* meta, int B, int K, float* score, int32_t* label, int32_t* query,
+                       int32_t* count, u3d_stream_t stream);
+/* class-wise greedy NMS of the top-k candidates of every scene.  Per scene: candidates with score <= score_thr are dropped, the
+ * rest are stably ordered by label (torch.sort(labels, stable=True) of the score-sorted list): order [B][K] = candidate rank r,
+ * n_order [B] = how many; boxes_ord [B][K][7] = the candidates' boxes (row query[r] of the scene's [n][box_dim] box matrix at
+ * box_ptrs[b]) in that order, heading 0 for 6-column boxes; keep [B][K] = 1 for the survivors of the greedy suppression inside
+ * each (scene, class) segment -- the same arithmetic, and so the same flags, as u3d_nms_bev / u3d_nms_aligned3d /
+ * u3d_nms_rotated on the scene's ordered list.  max_classes >= every C.  ws: u3d_nms_batched_ws_bytes(B, max_classes). */
+int u3d_nms_batched(const uint64_t* box_ptrs, const int32_t* meta, const float* fmeta, int B, int K, int max_classes, const float* score,
+                    const int32_t* label, const int32_t* query, const int32_t* count, int32_t* order, int32_t* n_order, uint8_t* keep,
+                    float* boxes_ord, void* ws, u3d_stream_t stream);
+int64_t u3d_nms_batched_ws_bytes(int B, int max_classes);
+/* stable compaction of the keep flags: the survivors of scene b in the reference's output order (label asc, score desc) at rows
+ * b * K .. b * K + out_count[b] of out_boxes [B][K][7], out_scores [B][K], out_labels int64 [B][K]; yaw [B] = 1 when a survivor
+ * has a non-zero (or NaN) heading; minmax [B][K][6] is set to (+inf, -inf) for the survivors of trimmed scenes. */
+int u3d_nms_compact(const int32_t* meta, int B, int K, const float* score, const int32_t* label, const int32_t* order, const int32_t* n_order,
+                    const uint8_t* keep, const float* boxes_ord, float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_count,
+                    int32_t* yaw, float* minmax, u3d_stream_t stream);
+/* superpoint trimming of the boxes of every scene with trim = 1 (u3d_trim_boxes per scene): (sp_list, sp_offsets [S+1]) is the
+ * batch-global CSR of point rows per superpoint, sp_scene int32 [B+1] the first superpoint of each scene; a superpoint is paired
+ * with its own scene's out_count[b] boxes only, which are rotated by their heading when yaw[b] != 0 and taken as yaw-free
+ * otherwise.  minmax as u3d_nms_compact left it; boxes [B][K][7] (u3d_nms_compact's out_boxes): columns 0..5 of the trimmed
+ * scenes' rows are replaced by (centre, size) = ((max + min) / 2, max - min) of the selected points. */
+int u3d_trim_boxes_batched(const float* points, int64_t pt_ld, const int32_t* sp_list, const int32_t* sp_offsets, const int32_t* sp_scene,
+                           int B, int S, const int32_t* meta, const float* fmeta, int K, const int32_t* count, const int32_t* yaw,
+                           float* minmax, float* boxes, u3d_stream_t stream);
 
 /* =====================================================================================
  * R12  matcher + losses of a batch on the device: forward value AND gradients in five launches

@@ -77,6 +77,11 @@ PROTOTYPES = {
     'u3d_nms_aligned3d': (_i32, [_vp, _vp, _i32, _f32, _vp, _vp]),
     'u3d_nms_rotated': (_i32, [_vp, _vp, _i32, _f32, _vp, _vp]),
     'u3d_trim_boxes': (_i32, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _f32, _vp, _vp]),
+    'u3d_topk_segmented': (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_nms_batched': (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_nms_batched_ws_bytes': (_i64, [_i32, _i32]),
+    'u3d_nms_compact': (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_trim_boxes_batched': (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     'u3d_weight_pack': (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'u3d_weight_transpose': (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     'u3d_bn_stats': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
@@ -127,7 +132,7 @@ PROTOTYPES = {
     'u3d_attn_varlen_bwd_b16': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
 }
 
-ABI_VERSION = 114         # include/u3d.h U3D_ABI_VERSION this table was written against
+ABI_VERSION = 115         # include/u3d.h U3D_ABI_VERSION this table was written against
 
 K_CONV_FWD, K_CONV_WGRAD, K_BN, K_POOL, K_ATTN_FWD, K_ATTN_BWD, K_RULEBOOK, K_VOXELIZE, K_GEMM = range(9)
 

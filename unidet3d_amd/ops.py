@@ -236,6 +236,143 @@ def trim_boxes_by_superpoints(points: torch.Tensor, sp_offsets: torch.Tensor, sp
     return torch.cat(((mx + mn) / 2, mx - mn), dim=1)
 
 
+# ----------------------------------------------------------------------------------------
+# inference post-processing of a whole batch (u3d.h "batched"): softmax per dataset group, then one chain of kernels
+# (segmented top-k -> ordering by class -> NMS per (scene, class) -> compaction -> superpoint trimming), one host read
+# ----------------------------------------------------------------------------------------
+PP_MAX_K = NMS_ROT_MAX          # csrc/postproc.hip PP_MAX_K: top-k candidates per scene the batched kernels take
+PP_META, PP_FMETA = 8, 4        # include/u3d.h U3D_PP_META / U3D_PP_FMETA
+NMS_MODE_BEV, NMS_MODE_ALIGNED3D, NMS_MODE_ROTATED = 0, 1, 2
+
+
+def postproc_settings(test_cfg: dict, dataset_index: int, fast_nms, use_superpoints) -> dict:
+    """The post-processing settings of a scene of dataset ``dataset_index`` (UniDet3D.predict_by_feat, unidet3d.py:498-538)."""
+    return dict(topk=int(test_cfg['topk_insts']), score_thr=float(test_cfg['score_thr']), iou_thr=float(test_cfg['iou_thr'][dataset_index]),
+                fast_nms=bool(fast_nms[dataset_index]), trim=bool(use_superpoints[dataset_index]),
+                low_sp_thr=float(test_cfg['low_sp_thr']), up_sp_thr=float(test_cfg['up_sp_thr']))
+
+
+def postproc_batched_ok(n_queries: int, n_classes: int, settings: dict) -> bool:
+    """Whether a scene fits the batched kernels (top-k within the in-LDS sort, flat indices in 31 bits); the others take the
+    per-scene path, which gives the same result."""
+    return settings['topk'] <= PP_MAX_K and n_queries * n_classes < 2 ** 31
+
+
+def postproc_scene_table(n_queries, n_classes, box_dims, settings):
+    """Host side of the per-scene settings tables of u3d_topk_segmented / u3d_nms_batched / u3d_trim_boxes_batched:
+    (meta int32 [B, 8], fmeta float32 [B, 4]).  A scene that does not fit the batched kernels gets topk = 0 and trim = 0 there
+    (it has no candidates in the chain)."""
+    import numpy as np
+    B = len(settings)
+    meta = np.zeros((B, PP_META), np.int32)
+    fmeta = np.zeros((B, PP_FMETA), np.float32)
+    for i, (n, c, bd, st) in enumerate(zip(n_queries, n_classes, box_dims, settings)):
+        if bd not in (6, 7):
+            raise ValueError('boxes must be (cx, cy, cz, dx, dy, dz[, heading])')
+        ok = postproc_batched_ok(n, c, st)
+        mode = NMS_MODE_ROTATED if bd == 7 else (NMS_MODE_BEV if st['fast_nms'] else NMS_MODE_ALIGNED3D)
+        meta[i] = (n, c, c + 1, st['topk'] if ok else 0, bd, mode, int(st['trim'] and ok), 0)
+        fmeta[i] = (st['score_thr'], st['iou_thr'], st['low_sp_thr'], st['up_sp_thr'])
+    return meta, fmeta
+
+
+def postproc_columns(box_dim: int, settings: dict, n_out: int) -> int:
+    """Columns of a scene's output boxes, as the per-scene path returns them: trimmed boxes are (centre, size); untrimmed ones keep
+    the heading of 7-dof boxes or get the zero heading the fast-NMS branch appends (unidet3d.py:629-638) -- except when nothing
+    passed the score threshold, where nms_multiclass returns zeros of the input width (:645-648)."""
+    if settings['trim']:
+        return 6
+    if n_out == 0:
+        return box_dim
+    return 7 if box_dim == 7 or settings['fast_nms'] else box_dim
+
+
+def postprocess_scene(cls_pred: torch.Tensor, bbox: torch.Tensor, settings: dict, points: torch.Tensor, sp_offsets: torch.Tensor,
+                      sp_points: torch.Tensor, n_superpoints: int, probs: Optional[torch.Tensor] = None):
+    """One scene through the per-scene kernels (unidet3d.py:498-538): softmax -> torch top-k -> ``nms_multiclass`` ->
+    ``trim_boxes_by_superpoints``.  ``sp_offsets`` starts at the scene's first superpoint.  Returns (boxes, labels, scores)."""
+    import torch.nn.functional as F
+    scores = (probs if probs is not None else F.softmax(cls_pred, dim=-1))[:, :-1]
+    num_classes = scores.shape[1]
+    scores, topk_idx = scores.flatten(0, 1).topk(min(settings['topk'], scores.numel()), sorted=True)
+    labels = topk_idx % num_classes
+    boxes = bbox[torch.div(topk_idx, num_classes, rounding_mode='floor')]
+    boxes, scores, labels = nms_multiclass(boxes, scores, labels, settings['iou_thr'], settings['score_thr'], settings['fast_nms'])
+    if settings['trim']:       # trimmed boxes are axis-aligned whatever went in (:585-592)
+        boxes = trim_boxes_by_superpoints(points, sp_offsets, sp_points, n_superpoints, boxes, settings['low_sp_thr'], settings['up_sp_thr'])
+    return boxes, labels, scores
+
+
+def postprocess_batch(cls_preds, bboxes, settings, vb: VoxelBatch, plan: PoolPlan, batch_offsets):
+    """Post-processing of every scene of a batch, each with its own settings (``postproc_settings``): ``cls_preds[i]`` [n_i, C_i + 1]
+    logits and ``bboxes[i]`` [n_i, 6 | 7] boxes of the decoder, ``vb`` / ``plan`` / ``batch_offsets`` (superpoints of scene i:
+    batch_offsets[i] .. batch_offsets[i + 1]) from the batch's front end.  Returns [(boxes [m_i, 6 | 7], labels, scores)] equal to
+    ``postprocess_scene`` on each scene, except that exact score ties inside a top-k go to the lower flat index (the documented rule
+    of oracle.postproc.topk_instances; torch.topk documents none).  The softmax runs once per group of scenes with the same class
+    count (F.softmax: row by row, so the same bits as per scene); the rest is one chain of kernels with the [B] survivor counts as
+    the only read back to the host.  Scenes outside the kernels' limits (``postproc_batched_ok``) take ``postprocess_scene``."""
+    import torch.nn.functional as F
+    B = len(settings)
+    if B == 0:
+        return []
+    cls = [cls_preds[i] for i in range(B)]
+    box = [bboxes[i].contiguous().float() for i in range(B)]
+    dev = box[0].device
+    n_q = [int(c.shape[0]) for c in cls]
+    n_c = [int(c.shape[1]) - 1 for c in cls]
+    bdim = [int(b.shape[1]) for b in box]
+    meta, fmeta = postproc_scene_table(n_q, n_c, bdim, settings)
+    groups = {}
+    for i, c in enumerate(cls):
+        if c.dtype != torch.float32:
+            raise TypeError('postprocess_batch: class logits must be float32')
+        groups.setdefault(n_c[i], []).append(i)
+    probs, prob_ptr = [None] * B, [0] * B
+    for g in groups.values():
+        p = F.softmax(torch.cat([cls[i] for i in g]) if len(g) > 1 else cls[g[0]], dim=-1)
+        r0 = 0
+        for i in g:
+            probs[i] = p[r0:r0 + n_q[i]]
+            prob_ptr[i] = p.data_ptr() + r0 * p.shape[1] * p.element_size()
+            r0 += n_q[i]
+    takes = [min(int(meta[i, 3]), n_q[i] * n_c[i]) for i in range(B)]
+    K = max(1, max(takes))
+    C_max = max(1, max(n_c))
+    d_ptr, d_meta, d_fmeta, d_sp = L.h2d_pack([(prob_ptr + [b.data_ptr() for b in box], torch.int64), (meta.tolist(), torch.int32),
+                                               (fmeta.tolist(), torch.float32), ([int(v) for v in batch_offsets], torch.int32)], dev)
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    score, label, query = torch.empty(B * K, **f32), torch.empty(B * K, **i32), torch.empty(B * K, **i32)
+    count, n_order = torch.empty(B, **i32), torch.empty(B, **i32)
+    L.call('u3d_topk_segmented', L.ptr(d_ptr[:B]), L.ptr(d_meta), B, K, L.ptr(score), L.ptr(label), L.ptr(query), L.ptr(count), L.stream())
+    order, keep, boxes_ord = torch.empty(B * K, **i32), torch.empty(B * K, dtype=torch.uint8, device=dev), torch.empty(B * K, 7, **f32)
+    w = L.ws(L.lib().u3d_nms_batched_ws_bytes(B, C_max), dev)
+    L.call('u3d_nms_batched', L.ptr(d_ptr[B:]), L.ptr(d_meta), L.ptr(d_fmeta), B, K, C_max, L.ptr(score), L.ptr(label), L.ptr(query),
+           L.ptr(count), L.ptr(order), L.ptr(n_order), L.ptr(keep), L.ptr(boxes_ord), L.ptr(w), L.stream())
+    out_b, out_s = torch.empty(B * K, 7, **f32), torch.empty(B * K, **f32)
+    out_l, out_n, yaw = torch.empty(B * K, dtype=torch.int64, device=dev), torch.empty(B, **i32), torch.empty(B, **i32)
+    minmax = torch.empty(B * K, 6, **f32)
+    L.call('u3d_nms_compact', L.ptr(d_meta), B, K, L.ptr(score), L.ptr(label), L.ptr(order), L.ptr(n_order), L.ptr(keep), L.ptr(boxes_ord),
+           L.ptr(out_b), L.ptr(out_s), L.ptr(out_l), L.ptr(out_n), L.ptr(yaw), L.ptr(minmax), L.stream())
+    if bool(meta[:, 6].any()):
+        L.call('u3d_trim_boxes_batched', L.ptr(vb.points), vb.points.stride(0), L.ptr(plan.sp_points), L.ptr(plan.sp_offsets), L.ptr(d_sp),
+               B, plan.S, L.ptr(d_meta), L.ptr(d_fmeta), K, L.ptr(out_n), L.ptr(yaw), L.ptr(minmax), L.ptr(out_b), L.stream())
+    counts = out_n.tolist()                                   # the one device -> host read of the batch
+    res = []
+    for i in range(B):
+        st = settings[i]
+        if not postproc_batched_ok(n_q[i], n_c[i], st):
+            o0 = int(batch_offsets[i])
+            res.append(postprocess_scene(cls[i], box[i], st, vb.points, plan.sp_offsets[o0:], plan.sp_points,
+                                         int(batch_offsets[i + 1]) - o0, probs[i]))
+            continue
+        n, r0 = counts[i], i * K
+        if n == 0:                          # nms_multiclass: all three outputs are zeros made from the boxes (unidet3d.py:645-648)
+            res.append((box[i].new_zeros((0, postproc_columns(bdim[i], st, 0))), box[i].new_zeros((0,)), box[i].new_zeros((0,))))
+            continue
+        res.append((out_b[r0:r0 + n, :postproc_columns(bdim[i], st, n)], out_l[r0:r0 + n], out_s[r0:r0 + n]))
+    return res
+
+
 def cat_views(ts):
     """``torch.cat(ts)`` -- without the copy (and without the slice / cat nodes in the autograd graph) when ``ts`` are the consecutive row
     slices of ONE contiguous tensor that together cover it, which is how the per-scene lists of the reference's interface are made

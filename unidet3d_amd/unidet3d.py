@@ -5,7 +5,7 @@ registry name, constructor arguments (:59-76), parameter names (``input_conv.0.w
 ``unet.*``, ``output_layer.0.*``, ``decoder.*``), ``collate`` (:136-176), ``extract_feat``
 (:113-134), ``_select_queries`` (:182-218), ``loss`` (:277-364) and the feature / decoder part of
 ``predict`` (:411-462), and the NMS / superpoint-trimming post-processing (:475-650, SURVEY.md section 8f
-rank 1) through ``ops.nms_multiclass`` / ``ops.trim_boxes_by_superpoints``.
+rank 1) for every scene of a batch through ``ops.postprocess_batch``.
 
 Batches are lists of per-scene tensors exactly as the reference receives them from its data
 preprocessor: ``batch_inputs_dict['points']`` = List[Tensor[N_i, 6]] on the device.
@@ -331,35 +331,35 @@ class UniDet3D(nn.Module):
         return self.decoder(feats, sp_centers, names)
 
     # ------------------------------------------------------------------ post-processing (unidet3d.py:475-538)
-    def predict_by_feat(self, out, plan, vb, n_sp0, dataset_name):
-        """Scene 0 of the batch, as in the reference (:498-502): softmax -> top-k over (query, class) -> class-wise NMS ->
-        superpoint trimming.  Returns [(DepthInstance3DBoxes, labels, scores)]."""
-        cls_preds, pred_bboxes = out['cls_preds'][0], out['bboxes'][0]
-        idx = self.decoder.datasets.index(dataset_name)
-        scores = F.softmax(cls_preds, dim=-1)[:, :-1]
-        num_classes = scores.shape[1]
-        scores, topk_idx = scores.flatten(0, 1).topk(min(self.test_cfg['topk_insts'], scores.numel()), sorted=True)
-        labels = topk_idx % num_classes
-        pred_bboxes = pred_bboxes[torch.div(topk_idx, num_classes, rounding_mode='floor')]
-        nms_bboxes, nms_scores, nms_labels = ops.nms_multiclass(pred_bboxes, scores, labels, self.test_cfg['iou_thr'][idx],
-                                                                self.test_cfg['score_thr'], bool(self.fast_nms[idx]))
-        if self.use_superpoints[idx]:       # trimmed boxes are axis-aligned whatever went in (:585-592)
-            nms_bboxes = ops.trim_boxes_by_superpoints(vb.points, plan.sp_offsets, plan.sp_points, n_sp0, nms_bboxes,
-                                                       self.test_cfg['low_sp_thr'], self.test_cfg['up_sp_thr'])
-        with_yaw = nms_bboxes.shape[1] == 7   # without trimming: 7 columns (zero heading after the fast-NMS branch, :629-636)
-        boxes = DepthInstance3DBoxes(nms_bboxes, with_yaw=with_yaw, box_dim=nms_bboxes.shape[1], origin=(0.5, 0.5, 0.5))
-        return [(boxes, nms_labels, nms_scores)]
+    def postproc_settings(self, names):
+        """Per-scene post-processing settings of a batch whose scenes come from the datasets ``names`` (``ops.postproc_settings``)."""
+        return [ops.postproc_settings(self.test_cfg, self.decoder.datasets.index(n), self.fast_nms, self.use_superpoints) for n in names]
+
+    def predict_by_feat(self, out, plan, vb, batch_offsets, names):
+        """Every scene of the batch, each with its own dataset's settings: softmax -> top-k over (query, class) -> class-wise NMS ->
+        superpoint trimming (unidet3d.py:498-538 for one scene; the reference post-processes scene 0 only and cannot run test
+        batches of more than one scene).  One chain of kernels for the batch (``ops.postprocess_batch``).
+        Returns [(DepthInstance3DBoxes, labels, scores)], one entry per scene."""
+        B = len(names)
+        res = ops.postprocess_batch([out['cls_preds'][i] for i in range(B)], [out['bboxes'][i] for i in range(B)], self.postproc_settings(names),
+                                    vb, plan, batch_offsets)
+        results = []
+        for nms_bboxes, nms_labels, nms_scores in res:
+            with_yaw = nms_bboxes.shape[1] == 7   # without trimming: 7 columns (zero heading after the fast-NMS branch, :629-636)
+            boxes = DepthInstance3DBoxes(nms_bboxes, with_yaw=with_yaw, box_dim=nms_bboxes.shape[1], origin=(0.5, 0.5, 0.5))
+            results.append((boxes, nms_labels, nms_scores))
+        return results
 
     def predict(self, batch_inputs_dict, batch_data_samples, **kwargs):
-        """unidet3d.py:411-473 (the reference post-processes scene 0 only -- test batches hold one scene)."""
+        """unidet3d.py:411-473, with ``pred_instances_3d`` for every scene of the batch (the reference post-processes scene 0 only)."""
         vb, plan, batch_offsets, sp_centers, names = self._front(batch_inputs_dict, batch_data_samples, False)
         x = self._sparse_input(len(batch_data_samples))
         feats = self.extract_feat(x, plan, vb.inverse, batch_offsets)
         out = self.decoder(feats, sp_centers, names)
-        results = self.predict_by_feat(out, plan, vb, batch_offsets[1] - batch_offsets[0], names[0])
-        for ds, (bboxes, labels, scores) in zip(batch_data_samples, results):
+        results = self.predict_by_feat(out, plan, vb, batch_offsets, names)
+        for i, (ds, (bboxes, labels, scores)) in enumerate(zip(batch_data_samples, results)):
             ds.pred_instances_3d = InstanceData_(bboxes_3d=bboxes, scores_3d=scores, labels_3d=labels,
-                                                 points=batch_inputs_dict['points'][0])
+                                                 points=batch_inputs_dict['points'][i])
         return batch_data_samples
 
     # ------------------------------------------------------------------ what an mmengine-style runner calls (BaseModel)
