@@ -100,7 +100,10 @@ __device__ __forceinline__ float clipped_edges_area(const float (&pa)[8], const 
             const float n0 = ex * (py - ay) - ey * (px - ax);       // side of the edge's start, > 0 = inside
             const float m = ex * dy - ey * dx;                       // change of the side along the edge
             if (m == 0.f) {
-                alive = alive && (strict ? n0 > 0.f : n0 >= 0.f);
+                // parallel: inside the half-plane, or -- for the closed test -- on f's line with the same direction (both
+                // outlines on the same side, a true edge of the intersection).  Opposite directions are outlines that only touch
+                // along the line, and a zero-length f (degenerate B) has no inside: neither contributes area.
+                alive = alive && (strict ? n0 > 0.f : (n0 > 0.f || (n0 == 0.f && ex * dx + ey * dy > 0.f)));
             } else {
                 const float tc = -n0 / m;
                 if (m > 0.f) t0 = fmaxf(t0, tc); else t1 = fminf(t1, tc);
@@ -170,12 +173,15 @@ __global__ __launch_bounds__(1024) void nms_rot_k(const float* __restrict__ boxe
     }
 }
 
+// float min / max by integer atomics on the bit pattern: sign bit clear -> signed compare, set -> unsigned compare reversed.  The
+// branch tests the sign bit, not v >= 0: -0.0f has it set (as a signed int it is INT_MIN, which would never raise a max and
+// would overwrite a negative min).
 __device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
-    if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
+    if (__float_as_int(v) >= 0) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-    if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
