@@ -35,7 +35,7 @@ typedef void* u3d_stream_t; /* hipStream_t */
 
 /* Bumped with every change of an entry point's argument list; unidet3d_amd/_lib.py refuses a library whose version differs from
  * the one it was written against (a stale .so would misread shifted arguments instead of failing). */
-#define U3D_ABI_VERSION 115
+#define U3D_ABI_VERSION 116
 int u3d_version(void);
 const char* u3d_last_error(void);
 /* How the fp32 matrix kernels (decoder GEMMs, attention, sparse convolutions without U3D_BF16_OPERANDS) multiply:
@@ -582,6 +582,59 @@ int u3d_box_decode_bwd(const float* raw, const float* dbox, int64_t M, float* dr
  * raw heading columns get a zero gradient (the reference never evaluates them for scenes of yaw-free datasets, encoder.py:186-199). */
 int u3d_box_decode7_fwd(const float* raw, const float* centers, const uint8_t* yaw_rows, int64_t M, float* box, u3d_stream_t stream);
 int u3d_box_decode7_bwd(const float* raw, const float* dbox, const uint8_t* yaw_rows, int64_t M, float* draw, u3d_stream_t stream);
+
+/* =====================================================================================
+ * R13  training-input augmentation of a whole ragged batch on the device (csrc/augment.hip): the steps of the reference's ScanNet /
+ *      S3DIS train pipelines after file loading -- PointSample_, RandomFlip3D, GlobalRotScaleTrans, NormalizePointsColor_
+ *      (unidet3d/loading.py:71-107), ElasticTransfrom, PointDetClassMappingScanNet / S3DIS (unidet3d/transforms_3d.py:12-295).
+ *  The batch is the concatenated per-point arrays plus pt_offsets int64 [B+1]; every entry point covers all scenes in a fixed
+ *  number of launches.  Source arrays (a device-resident scene cache of src_rows rows) are addressed through src int64 [B][2] =
+ *  (first row, row count) of each scene and an optional gather int64 [n]: batch point i of scene b reads source row
+ *  first_b + gather[i] % count_b (a draw below the count is taken as it is), or first_b + (i - pt_offsets[b]) when gather is NULL.
+ *  Zero points / zero scenes / an empty scene inside a batch are valid (nothing is launched for them) or U3D_EINVAL.
+ * ===================================================================================== */
+/* points [n][6] = (affine_b (x, y, z), colour): x' = ((a00 x + a01 y) + a02 z) + a03 in fp32 in this order, affine float [B][3][4];
+ * colour c' = (c - mean) / std, fp32 subtract then fp32 divide, each only when its host pointer (3 floats) is non-NULL;
+ * coords (nullable) [n][3] = x' / voxel_size, IEEE fp32 division (what ElasticTransfrom.transform starts from). */
+int u3d_aug_points(const float* src_points, int64_t src_rows, const int64_t* gather, const int64_t* src, const int64_t* pt_offsets, int B,
+                   int64_t n, const float* affine, const float* color_mean_host, const float* color_std_host, float voxel_size,
+                   float* points, float* coords, u3d_stream_t stream);
+/* extent [B][3] = max |coord| per scene and axis (0 for an empty scene), exact; coords [n][3]. */
+int u3d_aug_extent_f32(const float* coords, const int64_t* pt_offsets, int B, int64_t max_pts_per_scene, float* extent, u3d_stream_t stream);
+int u3d_aug_extent_f64(const double* coords, const int64_t* pt_offsets, int B, int64_t max_pts_per_scene, double* extent, u3d_stream_t stream);
+/* the six sweeps of transforms._box_blur3 (axes 0,1,2,0,1,2, zero padding, (a/3' + b/3') + c/3' with 3' = fp32(1/3) as products)
+ * over the noise grids of one elastic pass: noise holds scene b's [3][d0][d1][d2] floats at 3 grid_offsets[b] (grid_offsets int64
+ * [B+1] in cells, dims int32 [B][3]; a scene without a pass has zero cells).  grids receives them cell-major: 4 floats per cell
+ * (channel 0, 1, 2, unused) at cell grid_offsets[b] + (i0 d1 + i1) d2 + i2.  Six launches.  ws: u3d_aug_noise_blur_ws_bytes. */
+int u3d_aug_noise_blur(const float* noise, const int32_t* dims, const int64_t* grid_offsets, int B, int64_t total_cells, float* grids,
+                       void* ws, u3d_stream_t stream);
+int64_t u3d_aug_noise_blur_ws_bytes(int64_t total_cells);
+/* one elastic pass: out = x + trilinear(grids)(x) * mag per point in fp64 (transforms.trilinear_lookup: t = (x + (b-1) gran) / (2 gran),
+ * i0 = clip(floor(t), 0, b-2), 0 outside [0, b-1], eight corners in (dx, dy, dz) order); coords_in fp32 or fp64 [n][3] (in_f64),
+ * coords_out likewise (out_f64).  Scenes with gate[b] == 0 pass x through unchanged. */
+int u3d_aug_elastic(const void* coords_in, int in_f64, void* coords_out, int out_f64, const int64_t* pt_offsets, int B, int64_t n,
+                    const float* grids, const int64_t* grid_offsets, const int32_t* dims, const uint8_t* gate, double gran, double mag,
+                    u3d_stream_t stream);
+/* np.unique(ids, return_inverse=True)[1] per scene for ids in [-1, max_id]: scene b owns table_offsets[b+1] - table_offsets[b] =
+ * max_id_b + 2 table entries (table_offsets int64 [B+1]); an id outside that range counts as -1.  keep_negative: -1 stays -1 and
+ * the other ids become 0..k-1.  sem (nullable, a source array like ids): sem_out [n] (nullable) receives the gathered labels, and
+ * points whose label l has sem_drop[l] != 0 (uint8 [n_sem_drop], nullable) take id -1 first.  counts int32 [B] = distinct ids that
+ * received a rank; first (nullable) int64 [table_entries]: batch row of the first occurrence of new id r of scene b at
+ * table_offsets[b] + r (np.unique's return_index), 0 past the count.  ws: u3d_relabel_ids_ws_bytes. */
+int u3d_relabel_ids(const int64_t* ids, int64_t src_rows, const int64_t* gather, const int64_t* src, const int64_t* pt_offsets, int B, int64_t n,
+                    const int64_t* table_offsets, int64_t table_entries, int keep_negative, const int64_t* sem, const uint8_t* sem_drop,
+                    int n_sem_drop, int64_t* new_ids, int64_t* sem_out, int32_t* counts, int64_t* first, void* ws, u3d_stream_t stream);
+int64_t u3d_relabel_ids_ws_bytes(int64_t table_entries);
+/* ids[i] = table[table_offsets[b] + ids[i]] in place for ids inside the scene's table, -1 otherwise (PointDetClassMappingS3DIS's remap). */
+int u3d_aug_remap_ids(int64_t* ids, const int64_t* pt_offsets, int B, int64_t n, const int64_t* table, const int64_t* table_offsets,
+                      u3d_stream_t stream);
+/* transforms._sp_masks of every scene: masks (uint8 0 / 1), scene b's [n_inst_b][S_b] matrix at mask_offsets[b] (int64 [B+1]),
+ * S_b = sp_offsets[b+1] - sp_offsets[b]; entry (j, s) = 2 hits[j][s] > cnt[s].  inst [n] in batch order; sp [n] in batch order, or a
+ * source array read through sp_src (the `src` table) when that is non-NULL.  ws: u3d_aug_sp_masks_ws_bytes. */
+int u3d_aug_sp_masks(const int64_t* inst, const int64_t* sp, const int64_t* sp_src, int64_t src_rows, const int64_t* pt_offsets, int B, int64_t n,
+                     const int32_t* n_inst, const int64_t* sp_offsets, const int64_t* mask_offsets, int64_t mask_entries, int64_t n_superpoints,
+                     uint8_t* masks, void* ws, u3d_stream_t stream);
+int64_t u3d_aug_sp_masks_ws_bytes(int64_t mask_entries, int64_t n_superpoints);
 
 #ifdef __cplusplus
 }

@@ -130,9 +130,20 @@ PROTOTYPES = {
     'u3d_attn_varlen_bwd_bf16': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
     'u3d_attn_varlen_fwd_b16': (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
     'u3d_attn_varlen_bwd_b16': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
+    'u3d_aug_points': (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, C.POINTER(_f32), C.POINTER(_f32), _f32, _vp, _vp, _vp]),
+    'u3d_aug_extent_f32': (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
+    'u3d_aug_extent_f64': (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
+    'u3d_aug_noise_blur': (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp]),
+    'u3d_aug_noise_blur_ws_bytes': (_i64, [_i64]),
+    'u3d_aug_elastic': (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _vp]),
+    'u3d_relabel_ids': (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_relabel_ids_ws_bytes': (_i64, [_i64]),
+    'u3d_aug_remap_ids': (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
+    'u3d_aug_sp_masks': (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    'u3d_aug_sp_masks_ws_bytes': (_i64, [_i64, _i64]),
 }
 
-ABI_VERSION = 115         # include/u3d.h U3D_ABI_VERSION this table was written against
+ABI_VERSION = 116         # include/u3d.h U3D_ABI_VERSION this table was written against
 
 K_CONV_FWD, K_CONV_WGRAD, K_BN, K_POOL, K_ATTN_FWD, K_ATTN_BWD, K_RULEBOOK, K_VOXELIZE, K_GEMM = range(9)
 

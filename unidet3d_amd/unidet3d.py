@@ -404,7 +404,11 @@ class UniDet3D(nn.Module):
         if self._side_stream is None:
             self._side_stream = torch.cuda.Stream(dev)
         main = torch.cuda.current_stream(dev)
+        # a batch produced on the device (augment.DeviceAugment) carries the event recorded after its kernels
+        produced = data['inputs'].get('ready_event') if isinstance(data, dict) and isinstance(data.get('inputs'), dict) else None
         with torch.cuda.stream(self._side_stream):
+            if produced is not None:
+                self._side_stream.wait_event(produced)
             prepped = self._prep(data, True)
         self.prefetch(prepped['inputs'], prepped['data_samples'])          # same side stream: ordered after the uploads
         for t in _tensors_of(prepped):
