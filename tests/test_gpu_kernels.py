@@ -266,6 +266,129 @@ def test_register_stationary_bf16_row_conv_matches_the_pair_kernel(H, monkeypatc
         assert _rel(res['rs'][0], res['pairs'][0]) < 2e-6 and _rel(res['rs'][1], res['pairs'][1]) < 2e-6, (cin, cout)
 
 
+def _record_calls(monkeypatch):
+    """every ``_lib.call`` from here on as (entry point, raw stream that was current) in the returned list"""
+    from unidet3d_amd import _lib as L
+    log, real = [], L.call
+
+    def call(name, *args):
+        log.append((name, L.stream()))
+        return real(name, *args)
+    monkeypatch.setattr(L, 'call', call)
+    return log
+
+
+# conv entry point -> the single-weight pack of its operand format
+_CONV_ENTRY_PACK = {'u3d_spconv_gmm': 'u3d_weight_pack', 'u3d_spconv_gmm_x3': 'u3d_weight_pack_x3', 'u3d_spconv_rs_x3': 'u3d_weight_pack_x3',
+                    'u3d_spconv_ts_x3': 'u3d_weight_pack_x3', 'u3d_spconv_gmm_bf16': 'u3d_weight_pack_bf16',
+                    'u3d_spconv_gmm_bf16a': 'u3d_weight_pack_bf16', 'u3d_spconv_rs_bf16a': 'u3d_weight_pack_bf16'}
+
+
+def test_the_conv_kernel_that_was_asked_for_is_the_one_that_ran(monkeypatch):
+    """The register- / tile-stationary tests compare those kernels with the pair kernel to 2e-6 -- a toggle that fell through to the
+    pair kernel would pass them.  Here the entry point itself is recorded: forward and input gradient of one SubM convolution per
+    mode and shape call exactly the kernel the mode asks for (16 source channels: always the fp32 pair kernel), with exactly one
+    single-weight pack of the matching format in front of each -- and none once a WeightPacks has packed that weight."""
+    from contextlib import ExitStack
+    from unidet3d_amd import precision as P
+    from unidet3d_amd import sparse
+    monkeypatch.setattr(sparse, '_RS_MIN_ROWS', 1)
+    vb, _, _ = _level_geometry(n_points=20_000, vs=0.03)
+    rb = sparse.build_subm_rulebook(vb.coords, vb.index)
+    n = rb.n_out
+    assert sparse._ts_plan(32, 32, n) is not None                  # the tile-stationary arm below is not vacuous
+    log = _record_calls(monkeypatch)
+    x3, bf16 = (lambda: P.fp32_math('bf16x3')), (lambda: P.operands('bf16'))
+    modes = [('mfma', [lambda: P.fp32_math('mfma')], False, 'u3d_spconv_gmm'),
+             ('bf16x3', [x3], False, 'u3d_spconv_gmm_x3'),
+             ('bf16', [bf16], False, 'u3d_spconv_gmm_bf16'),
+             ('bf16 rows', [bf16], True, 'u3d_spconv_gmm_bf16a'),
+             ('rs', [x3, lambda: sparse.conv_rs(True)], False, 'u3d_spconv_rs_x3'),
+             ('rsb', [bf16, lambda: sparse.conv_rs_bf16(True)], True, 'u3d_spconv_rs_bf16a'),
+             ('ts', [x3, lambda: sparse.conv_ts(True)], False, 'u3d_spconv_ts_x3')]
+    g = torch.Generator().manual_seed(5)
+    for tag, contexts, shadows, entry in modes:
+        for cin, cout in ((32, 32), (64, 32), (16, 32)):
+            x = torch.randn(n, cin, generator=g).to(_dev()).requires_grad_(cin != 16)      # (16: the padded network input, no dgrad built)
+            w = (torch.randn(cout, 3, 3, 3, cin, generator=g) * 0.1).to(_dev()).requires_grad_()
+            go = torch.randn(n, cout, generator=g).to(_dev())
+            if shadows:
+                if cin % 32 == 0:
+                    sparse.attach_shadow(x, sparse.to_shadow(x))
+                sparse.attach_shadow(go, sparse.to_shadow(go))
+
+            def want(cs, cd):          # entry point of a launch with cs source and cd destination channels
+                if cs == 16:
+                    return 'u3d_spconv_gmm'
+                if tag == 'ts' and sparse._ts_plan(cs, cd, n) is None:
+                    return 'u3d_spconv_gmm_x3'
+                return entry
+            expected = [want(cin, cout)] + ([want(cout, cin)] if cin != 16 else [])
+            del log[:]
+            with ExitStack() as stack:
+                for c in contexts:
+                    stack.enter_context(c())
+                sparse.sparse_conv(x, w, rb).backward(go)
+            names = [name for name, _ in log]
+            assert [k for k in names if k in _CONV_ENTRY_PACK] == expected, (tag, cin, cout)
+            assert [k for k in names if k.startswith('u3d_weight_pack')] == [_CONV_ENTRY_PACK[k] for k in expected], (tag, cin, cout)
+            assert w.grad is not None and (x.grad is not None) == (cin != 16)
+    # packed ahead by WeightPacks: the same lookup serves every route, no launch of its own
+    conv = sparse.SubMConv3d(32, 32, 3).to(_dev())
+    packs = sparse.WeightPacks(conv)
+    for contexts, entry in (([x3], 'u3d_spconv_gmm_x3'), ([x3, lambda: sparse.conv_rs(True)], 'u3d_spconv_rs_x3')):
+        with ExitStack() as stack:
+            for c in contexts:
+                stack.enter_context(c())
+            del log[:]
+            packs.refresh()
+            assert [name for name, _ in log] == ['u3d_weight_pack_batch']
+            del log[:]
+            x = torch.randn(n, 32, generator=g).to(_dev()).requires_grad_()
+            sparse.sparse_conv(x, conv.weight, rb).backward(torch.randn(n, 32, generator=g).to(_dev()))
+        names = [name for name, _ in log]
+        assert [k for k in names if k in _CONV_ENTRY_PACK] == [entry, entry]
+        assert not [k for k in names if k.startswith('u3d_weight_pack')]
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('operands', ['fp32', 'bf16'])
+def test_weight_gradient_kernels_run_on_the_side_stream_when_asked(operands, monkeypatch):
+    """wgrad_stream: under set_wgrad_overlap(2) the weight-gradient kernel of a sparse convolution AND the dY^T X product of a Linear
+    (dense.py; under bf16 operands the bf16-activation form of dense16.py) are launched on a stream that is not the main one; under
+    mode 1 only the convolution's; under mode 0 none.  (The values: test_weight_gradients_on_the_side_stream_give_the_same_bits.)"""
+    from unidet3d_amd import _lib as L
+    from unidet3d_amd import dense, sparse
+    from unidet3d_amd import precision as P
+    vb, _, _ = _level_geometry(n_points=20_000, vs=0.03)
+    rb = sparse.build_subm_rulebook(vb.coords, vb.index)
+    n = rb.n_out
+    g = torch.Generator().manual_seed(9)
+    x0 = torch.randn(n, 32, generator=g).to(_dev())
+    wc0 = (torch.randn(32, 3, 3, 3, 32, generator=g) * 0.05).to(_dev())
+    wl0, bl0 = (torch.randn(64, 32, generator=g) * 0.1).to(_dev()), torch.randn(64, generator=g).to(_dev())
+    log = _record_calls(monkeypatch)
+    main = L.stream()
+    for mode, conv_on_side, linear_on_side in ((2, True, True), (1, True, False), (0, False, False)):
+        prev = sparse.set_wgrad_overlap(mode)
+        try:
+            x, wc, wl, bl = [t.clone().requires_grad_() for t in (x0, wc0, wl0, bl0)]        # fresh leaves without .grad
+            del log[:]
+            with P.operands(operands):
+                y = dense.linear(sparse.sparse_conv(x, wc, rb), wl, bl)
+                (y * y).sum().backward()
+            torch.cuda.synchronize()
+        finally:
+            sparse.set_wgrad_overlap(prev)
+        assert L.stream() == main
+        conv = [s for name, s in log if name.startswith('u3d_spconv_wgrad')]
+        lin = [s for name, s in log if name.startswith('u3d_gemm_tn')]
+        assert len(conv) == 1 and len(lin) == 1, (mode, [name for name, _ in log])
+        assert all((s != main) == conv_on_side for s in conv), (mode, conv, main)
+        assert all((s != main) == linear_on_side for s in lin), (mode, lin, main)
+        assert all(t.grad is not None and torch.isfinite(t.grad).all() for t in (x, wc, wl, bl))
+
+
 @pytest.mark.parametrize('operands', ['bf16x3', 'bf16'])
 @pytest.mark.parametrize('tile_rows', [32, 64])
 @pytest.mark.parametrize('cin,cout', [(32, 32), (64, 32), (64, 64), (96, 96), (128, 160), (256, 256)])

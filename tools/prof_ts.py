@@ -118,7 +118,7 @@ with P.fp32_math('bf16x3'):
                 os.environ['U3D_RS_H'] = str(H)
                 try:
                     with sparse.conv_rs(True):
-                        if not sparse._rs_ok(cs, cd, n, rb, P.FMT_X3):
+                        if sparse._conv_route(cs, cd, n, rb, P.FMT_X3, False, False)[0] != 'rs':
                             continue
                         xg = x.clone().requires_grad_()
                         y1 = sparse.sparse_conv(xg, w, rb)

@@ -9,6 +9,7 @@ import torch
 from . import _lib as L
 from . import precision as P
 from . import account
+from . import wgrad_stream as WS
 
 _PROFILE_FLOPS = False
 
@@ -220,26 +221,14 @@ def _weight_grad(dy, x, want_bias, bf=False):
 
 
 def _weight_grad_overlapped(dy, x, want_bias, bf, weight, bias):
-    """``_weight_grad`` on the weight-gradient side stream when sparse.set_wgrad_overlap(2) is on (nothing downstream of a Linear needs
-    its dW: the GEMM joins the sparse convolutions' weight-gradient chain and the dX chain goes on without it).  Only for leaf
-    parameters without an existing .grad -- autograd then just stores the tensor; anything else is computed in line."""
-    from . import sparse
-    ok = sparse._WGRAD_OVERLAP == 2 and _OVERLAP_TN and dy.is_cuda and sparse.async_dw_ok(weight, bias)
-    if not ok:
+    """``_weight_grad`` on the weight-gradient side stream when set_wgrad_overlap(2) is on (wgrad_stream.py; nothing downstream of a
+    Linear needs its dW: the GEMM joins the sparse convolutions' weight-gradient chain and the dX chain goes on without it).  Only for
+    leaf parameters without an existing .grad -- autograd then just stores the tensor; anything else is computed in line."""
+    if not (WS.mode() == 2 and _OVERLAP_TN and dy.is_cuda and WS.async_dw_ok(weight, bias)):
         return _weight_grad(dy, x, want_bias, bf)
-    dev = dy.device
-    main = torch.cuda.current_stream(dev)
-    side = sparse._side_stream(dev)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        dw, db = _weight_grad(dy, x, want_bias, bf)
-    dy.record_stream(side)
-    x.record_stream(side)
-    for t in (dw, db):                      # allocated from the side stream's pool, consumed on the main stream after the join
-        if t is not None:
-            t.record_stream(main)
-    sparse._queue_join(dev)
-    return dw, db
+    _, grads = WS.run_on_side_stream(dy.device, lambda: _weight_grad(dy, x, want_bias, bf), reads=(dy, x))
+    WS.queue_join(dy.device)
+    return grads
 
 
 _OVERLAP_TN = os.environ.get('U3D_OVERLAP_TN', '1') != '0'

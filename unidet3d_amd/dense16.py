@@ -25,6 +25,7 @@ import torch
 from . import _lib as L
 from . import account
 from . import dense as D
+from . import wgrad_stream as WS
 
 A16, B16, C16 = 1, 2, 4          # include/u3d.h U3D_A_BF16 / U3D_B_BF16 / U3D_C_BF16
 EPI_BIAS, EPI_RELU, EPI_RELU_MASK, EPI_ADD = 0, 1, 3, 5
@@ -100,24 +101,12 @@ def gemm_tn(dy, x, want_bias):
 
 
 def _weight_grad(dy, x, want_bias, weight, bias):
-    """``gemm_tn`` on the weight-gradient side stream when the overlap of sparse.set_wgrad_overlap(2) applies (dense._weight_grad_overlapped)"""
-    from . import sparse
-    ok = sparse._WGRAD_OVERLAP == 2 and D._OVERLAP_TN and dy.is_cuda and sparse.async_dw_ok(weight, bias)
-    if not ok:
+    """``gemm_tn`` on the weight-gradient side stream when the overlap of set_wgrad_overlap(2) applies (dense._weight_grad_overlapped)"""
+    if not (WS.mode() == 2 and D._OVERLAP_TN and dy.is_cuda and WS.async_dw_ok(weight, bias)):
         return gemm_tn(dy, x, want_bias)
-    dev = dy.device
-    main = torch.cuda.current_stream(dev)
-    side = sparse._side_stream(dev)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        dw, db = gemm_tn(dy, x, want_bias)
-    dy.record_stream(side)
-    x.record_stream(side)
-    for t in (dw, db):
-        if t is not None:
-            t.record_stream(main)
-    sparse._queue_join(dev)
-    return dw, db
+    _, grads = WS.run_on_side_stream(dy.device, lambda: gemm_tn(dy, x, want_bias), reads=(dy, x))
+    WS.queue_join(dy.device)
+    return grads
 
 
 def _transposed(weight, wt):

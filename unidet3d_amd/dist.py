@@ -16,13 +16,9 @@ from typing import Iterable, List
 import torch
 import torch.distributed as dist
 
+from .wgrad_stream import join_wgrad_stream
 
 _FORCE = False
-
-
-def _join_side_streams():
-    from .sparse import join_wgrad_stream
-    join_wgrad_stream()
 
 
 def force_collectives(on: bool = True) -> bool:
@@ -77,7 +73,7 @@ class FlatGradBucket:
             p.grad = None
 
     def pack(self):
-        _join_side_streams()
+        join_wgrad_stream()
         src, dst = [], []
         for p, v in zip(self.params, self.views):
             if p.grad is None:
@@ -151,7 +147,7 @@ class FlatGradBucket:
             self._next -= 1
 
     def _launch(self, b, sync: bool = False):
-        _join_side_streams()                   # weight gradients still running on the side stream (sparse.set_wgrad_overlap(2))
+        join_wgrad_stream()                    # weight gradients still running on the side stream (set_wgrad_overlap(2))
         src, dst = [], []
         for i in range(b['lo'], b['hi']):
             p, v = self.params[i], self.views[i]

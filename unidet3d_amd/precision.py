@@ -157,7 +157,8 @@ def bf16_act_mode(on: bool):
 
 def conv_format() -> int:
     """Operand format of the sparse-convolution kernels for the current modes: the packed-weight layout and the entry point
-    (u3d_spconv_gmm / _bf16 / _x3) go together, so the choice is made here, once per op, and remembered for its backward."""
+    (u3d_spconv_gmm / _bf16 / _x3; sparse._GMM_ENTRY) go together, so the choice is made here, once per op, and remembered for its
+    backward.  Which kernel then runs in that format is sparse._conv_route's decision."""
     if _MODE == 'bf16':
         return FMT_BF16
     return FMT_X3 if get_fp32_math() == 'bf16x3' else FMT_FP32

@@ -17,6 +17,7 @@ produce.
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import os
 from typing import Dict, Optional
 
@@ -29,6 +30,8 @@ from . import _lib as L
 from . import dense
 from . import precision as P
 from . import account
+from . import wgrad_stream as WS
+from .wgrad_stream import set_wgrad_overlap, async_dw_ok, join_wgrad_stream, end_of_backward, _ASYNC_DW_SEEN      # noqa: F401  (re-exported)
 
 
 # ----------------------------------------------------------------------------------------
@@ -259,7 +262,6 @@ def build_down_rulebook(coords: torch.Tensor, B: int, shape):
 # ----------------------------------------------------------------------------------------
 def _plan(Cs, Cd, K, n_dst, rows_kernel=False):
     """(rows per wave-tile, offset groups) the kernel wants for this shape (``rows_kernel``: u3d_spconv_gmm_bf16a's own plan)."""
-    import ctypes
     R, G = ctypes.c_int(0), ctypes.c_int(0)
     fn = L.lib().u3d_spconv_plan_bf16a if rows_kernel else L.lib().u3d_spconv_plan
     if n_dst <= 0 or fn(Cs, Cd, K, n_dst, ctypes.byref(R), ctypes.byref(G)) != 0:
@@ -390,246 +392,125 @@ def _pack_floats(numel: int, fmt: int) -> int:
 # measured BEHIND the pair-list kernels at every real layer shape of cfg2 (level 1, 32 -> 32: 148 us against 128; level 2, 64 -> 64:
 # 165 against 112; DESIGN.md 4.15 has the ablations and the cycle trace that say why).  U3D_CONV_TS=1 / set_conv_ts(True) turns it on.
 _CONV_TS = os.environ.get('U3D_CONV_TS', '0') == '1'
-
-
-def set_conv_ts(on: bool) -> bool:
-    global _CONV_TS
-    prev, _CONV_TS = _CONV_TS, bool(on)
-    return prev
-
-
-@contextlib.contextmanager
-def conv_ts(on: bool):
-    prev = set_conv_ts(on)
-    try:
-        yield
-    finally:
-        set_conv_ts(prev)
-
-
 # Register-stationary form (spconv_rs_k: weights of a 32 x 32 block in registers, persistent workgroups): U3D_CONV_RS=1 / set_conv_rs
 _CONV_RS = os.environ.get('U3D_CONV_RS', '0') == '1'
 _RS_MIN_ROWS = int(os.environ.get('U3D_CONV_RS_MIN_ROWS', '40000'))      # below that a level cannot feed one workgroup per CU
 _RS_MAX_BLOCKS = int(os.environ.get('U3D_CONV_RS_MAX_BLOCKS', '8'))      # Cs/32 x Cd/32 block launches per convolution at most
-
-
-def set_conv_rs(on: bool) -> bool:
-    global _CONV_RS
-    prev, _CONV_RS = _CONV_RS, bool(on)
-    return prev
-
-
-@contextlib.contextmanager
-def conv_rs(on: bool):
-    prev = set_conv_rs(on)
-    try:
-        yield
-    finally:
-        set_conv_rs(prev)
-
-
 # bf16 operands from bf16 rows (BASELINE configs[2]): the one-plane form spconv_rsb_k; U3D_CONV_RS_BF16=1 / set_conv_rs_bf16
 _CONV_RS_BF16 = os.environ.get('U3D_CONV_RS_BF16', '0') == '1'
 
 
-def set_conv_rs_bf16(on: bool) -> bool:
-    global _CONV_RS_BF16
-    prev, _CONV_RS_BF16 = _CONV_RS_BF16, bool(on)
-    return prev
+def _flag_toggle(name: str):
+    """(setter returning the previous value, context manager) of the boolean module flag ``name``.  The value stays in this module's
+    globals, where ``_conv_route`` reads it at call time and tests / tools patch it."""
+    def set_flag(on: bool) -> bool:
+        prev, globals()[name] = globals()[name], bool(on)
+        return prev
+
+    @contextlib.contextmanager
+    def flag(on: bool):
+        prev = set_flag(on)
+        try:
+            yield
+        finally:
+            set_flag(prev)
+    return set_flag, flag
 
 
-@contextlib.contextmanager
-def conv_rs_bf16(on: bool):
-    prev = set_conv_rs_bf16(on)
-    try:
-        yield
-    finally:
-        set_conv_rs_bf16(prev)
-
-
-def _rs_ok(Cs, Cd, n, rb, bf):
-    return (_CONV_RS and rb.coords is not None and int(bf) == P.FMT_X3 and Cs % 32 == 0 and Cd % 32 == 0 and n >= _RS_MIN_ROWS
-            and (Cs // 32) * (Cd // 32) <= _RS_MAX_BLOCKS)
+set_conv_ts, conv_ts = _flag_toggle('_CONV_TS')
+set_conv_rs, conv_rs = _flag_toggle('_CONV_RS')
+set_conv_rs_bf16, conv_rs_bf16 = _flag_toggle('_CONV_RS_BF16')
 
 
 def _ts_plan(Cs, Cd, n):
-    import ctypes
     T, H = ctypes.c_int(0), ctypes.c_int(0)
     if L.lib().u3d_spconv_ts_plan(Cs, Cd, n, ctypes.byref(T), ctypes.byref(H)) != 0:
         return None
     return T.value, H.value
 
 
+def _conv_route(Cs, Cd, n_dst, rb, bf, has_rows, want_stats):
+    """Which kernel runs a convolution of ``n_dst`` > 0 dst rows, decided here and nowhere else: (route, operand format, plan).
+      'rsb'    register-stationary, bf16 rows (u3d_spconv_rs_bf16a); plan = H, halo rows per pass.  Writes no statistics, asked or not;
+      'rs'     register-stationary, three planes (u3d_spconv_rs_x3); plan = H;
+      'ts'     tile-stationary, three planes (u3d_spconv_ts_x3) where u3d_spconv_ts_plan has a shape; plan = (T, H);
+      'pairs'  the pair-list kernels (_GMM_ENTRY, or u3d_spconv_gmm_bf16a on bf16 rows); plan = (R, G, gathers bf16 rows).  Source
+               channel counts that are not a multiple of 32 (the 6 -> 32 input convolution, padded to 16) stay on the fp32 kernel.
+    The first three are SubM-only experiments behind their toggles, tried in that order; only the pair kernels' epilogue can write the
+    batch-norm statistics, so 'rs' / 'ts' step aside when those are wanted (``want_stats`` under _EPILOGUE_STATS)."""
+    bf = int(bf)
+    subm32 = rb.coords is not None and Cs % 32 == 0
+    rs_shape = subm32 and Cd % 32 == 0 and n_dst >= _RS_MIN_ROWS and (Cs // 32) * (Cd // 32) <= _RS_MAX_BLOCKS
+    if _CONV_RS_BF16 and has_rows and bf == P.FMT_BF16 and rs_shape:
+        return 'rsb', bf, int(os.environ.get('U3D_RSB_H', '448'))
+    if bf == P.FMT_X3 and not (want_stats and _EPILOGUE_STATS):
+        if _CONV_RS and rs_shape:
+            return 'rs', bf, int(os.environ.get('U3D_RS_H', '320'))
+        ts = _ts_plan(Cs, Cd, n_dst) if _CONV_TS and subm32 else None
+        if ts is not None:
+            return 'ts', bf, ts
+    if Cs % 32:
+        bf = P.FMT_FP32
+    rows = has_rows and bf == P.FMT_BF16       # gather the bf16 shadow: same packed weights, u3d_spconv_gmm_bf16a and its own plan
+    return 'pairs', bf, _plan(Cs, Cd, rb.K, n_dst, rows) + (rows,)
+
+
+def _packed_weight(weight, transposed, fmt, Cd, K, Cs, device):
+    """``weight`` in MFMA-fragment order for format ``fmt``: the copy WeightPacks.refresh() packed with all the model's weights while
+    it is current, else packed here by a launch of its own."""
+    hit = _PACKED.get((weight.data_ptr(), int(transposed), fmt))
+    if hit is not None and hit[2] == weight._version and hit[1].device == device:
+        return hit[0]
+    wp = torch.empty(_pack_floats(weight.numel(), fmt), dtype=torch.float32, device=device)
+    L.call(_GMM_ENTRY[fmt][0], L.ptr(weight), L.ptr(wp), Cd, K, Cs, int(transposed), L.stream())
+    return wp
+
+
 def _gmm(src, weight, transposed, rb, gather, scatter, role, n_dst, addend, flops, bf=0, stats_out=None, src_rows_bf16=None):
     """weight: the layer's [C_out, K, C_in] tensor; transposed=True runs the input-gradient (dst channels = C_in).
     ``stats_out`` (a dict, or None): asks the kernel's epilogue for the per-tile column sums of dst that the batch norm behind
-    this convolution needs (``partial`` float [n_tiles, 2, Cd], ``n_tiles``); left empty when the launch splits the kernel
-    offsets over groups (deep levels: a few thousand rows, the norm then makes its own pass).
-    ``bf``: operand format (precision.conv_format: 0 fp32 MFMAs, 1 bf16 operands, 2 fp32 products from three bf16 planes);
-    source channel counts that are not a multiple of 32 (the 6 -> 32 input convolution, padded to 16) stay on the fp32 kernel.
-    ``src_rows_bf16``: the bf16 shadow of ``src`` (``shadow_of``) -- the launch then gathers those rows (u3d_spconv_gmm_bf16a)."""
+    this convolution needs (``partial`` float [n_tiles, 2, Cd], ``n_tiles``).  ONE rule: it is filled only by a pair-list launch
+    that gathers fp32 rows, under _EPILOGUE_STATS, with a single offset group; every other launch leaves it EMPTY and the norm makes
+    its own pass (offsets split over groups: deep levels of a few thousand rows; bf16 rows; the 'rsb' / 'rs' / 'ts' kernels).
+    ``bf``: operand format (precision.conv_format: 0 fp32 MFMAs, 1 bf16 operands, 2 fp32 products from three bf16 planes).
+    ``src_rows_bf16``: the bf16 shadow of ``src`` (``shadow_of``) -- the launch then gathers those rows.
+    Which kernel runs: ``_conv_route``; its packed weight: ``_packed_weight``."""
     Cs, Cd = src.shape[1], (weight.shape[2] if transposed else weight.shape[0])
     dst = torch.empty(n_dst, Cd, dtype=torch.float32, device=src.device)
-    ts = _ts_plan(Cs, Cd, n_dst) if (_CONV_TS and n_dst and rb.coords is not None and int(bf) == P.FMT_X3 and Cs % 32 == 0
-                                       and not (stats_out is not None and _EPILOGUE_STATS)) else None
-    if (n_dst and _CONV_RS_BF16 and src_rows_bf16 is not None and int(bf) == P.FMT_BF16 and rb.coords is not None and Cs % 32 == 0
-            and Cd % 32 == 0 and n_dst >= _RS_MIN_ROWS and (Cs // 32) * (Cd // 32) <= _RS_MAX_BLOCKS):
-        H = int(os.environ.get('U3D_RSB_H', '448'))
-        if _PROFILE_FLOPS:
-            account.add('conv_gmm', flops, 4.0 * (src.shape[0] * Cs + n_dst * Cd) + 8.0 * rb.total_pairs + 4.0 * rb.K * Cs * Cd)
-        nhalo, halo, loc, _pm = rb.halo(64, H)
-        hit = _PACKED.get((weight.data_ptr(), int(transposed), P.FMT_BF16))
-        if hit is not None and hit[2] == weight._version and hit[1].device == src.device:
-            wp = hit[0]
-        else:
-            wp = torch.empty(_pack_floats(weight.numel(), P.FMT_BF16), dtype=torch.float32, device=src.device)
-            L.call('u3d_weight_pack_bf16', L.ptr(weight), L.ptr(wp), Cd, rb.K, Cs, int(transposed), L.stream())
-        if stats_out is not None:
-            stats_out.clear()
-        L.call('u3d_spconv_rs_bf16a', L.ptr(src_rows_bf16), n_dst, L.ptr(wp), L.ptr(nhalo), L.ptr(halo), L.ptr(loc), H, int(transposed),
-               Cs, Cd, L.ptr(addend), L.ptr(dst), int(os.environ.get('U3D_RS_WGS', '0')), float(flops), L.stream())
-    elif n_dst and _rs_ok(Cs, Cd, n_dst, rb, bf) and not (stats_out is not None and _EPILOGUE_STATS):
-        H = int(os.environ.get('U3D_RS_H', '320'))
-        if _PROFILE_FLOPS:
-            account.add('conv_gmm', flops, 4.0 * (src.shape[0] * Cs + n_dst * Cd) + 8.0 * rb.total_pairs + 4.0 * rb.K * Cs * Cd)
-        nhalo, halo, loc, _pm = rb.halo(64, H)
-        hit = _PACKED.get((weight.data_ptr(), int(transposed), P.FMT_X3))
-        if hit is not None and hit[2] == weight._version and hit[1].device == src.device:
-            wp = hit[0]
-        else:
-            wp = torch.empty(_pack_floats(weight.numel(), P.FMT_X3), dtype=torch.float32, device=src.device)
-            L.call('u3d_weight_pack_x3', L.ptr(weight), L.ptr(wp), Cd, rb.K, Cs, int(transposed), L.stream())
-        L.call('u3d_spconv_rs_x3', L.ptr(src), n_dst, L.ptr(wp), L.ptr(nhalo), L.ptr(halo), L.ptr(loc), H, int(transposed),
-               Cs, Cd, L.ptr(addend), L.ptr(dst), int(os.environ.get('U3D_RS_WGS', '0')), float(flops), L.stream())
-    elif ts is not None:
-        T, H = ts
-        if _PROFILE_FLOPS:
-            account.add('conv_gmm', flops, 4.0 * (src.shape[0] * Cs + n_dst * Cd) + 8.0 * rb.total_pairs + 4.0 * rb.K * Cs * Cd)
-        nhalo, halo, loc, pmask = rb.halo(T, H)
-        hit = _PACKED.get((weight.data_ptr(), int(transposed), P.FMT_X3))
-        if hit is not None and hit[2] == weight._version and hit[1].device == src.device:
-            wp = hit[0]
-        else:
-            wp = torch.empty(_pack_floats(weight.numel(), P.FMT_X3), dtype=torch.float32, device=src.device)
-            L.call('u3d_weight_pack_x3', L.ptr(weight), L.ptr(wp), Cd, rb.K, Cs, int(transposed), L.stream())
-        L.call('u3d_spconv_ts_x3', L.ptr(src), n_dst, L.ptr(wp), L.ptr(nhalo), L.ptr(halo), L.ptr(loc), L.ptr(pmask), T, H, int(transposed),
-               Cs, Cd, L.ptr(addend), L.ptr(dst), float(flops), L.stream())
-    elif n_dst:
-        R, G = _plan(Cs, Cd, rb.K, n_dst, src_rows_bf16 is not None and int(bf) == P.FMT_BF16 and Cs % 32 == 0)
-        if _PROFILE_FLOPS:      # BASELINE.md section 3: N(Cs+Cd)s + 2P*idx + K*Cs*Cd*s  (s = 4 B, idx = 4 B)
-            account.add('conv_gmm', flops, 4.0 * (src.shape[0] * Cs + n_dst * Cd) + 8.0 * rb.total_pairs + 4.0 * rb.K * Cs * Cd)
+    if stats_out is not None:
+        stats_out.clear()       # filled below by the one launch form that writes statistics; empty tells the norm to make its own pass
+    if not n_dst:
+        return dst
+    route, fmt, plan = _conv_route(Cs, Cd, n_dst, rb, bf, src_rows_bf16 is not None, stats_out is not None)
+    if _PROFILE_FLOPS:      # BASELINE.md section 3: N(Cs+Cd)s + 2P*idx + K*Cs*Cd*s  (s = 4 B, idx = 4 B)
+        account.add('conv_gmm', flops, 4.0 * (src.shape[0] * Cs + n_dst * Cd) + 8.0 * rb.total_pairs + 4.0 * rb.K * Cs * Cd)
+    wp = _packed_weight(weight, transposed, fmt, Cd, rb.K, Cs, src.device)      # (the tensor, held until the launch below is queued)
+    if route == 'pairs':
+        R, G, rows = plan
         ws = torch.empty(G * n_dst * Cd, dtype=torch.float32, device=src.device) if G > 1 else None
-        partial = None
-        if stats_out is not None and G == 1 and _EPILOGUE_STATS:
-            n_tiles = (n_dst + R - 1) // R
-            partial = torch.empty(n_tiles, 2, Cd, dtype=torch.float32, device=src.device)
-            stats_out.update(partial=partial, n_tiles=n_tiles)
-        bf = int(bf) if Cs % 32 == 0 else 0
-        rows = src_rows_bf16 is not None and bf == P.FMT_BF16       # gather the bf16 shadow: same packed weights, u3d_spconv_gmm_bf16a
+        tiles = rb.tile_starts(role, R)
         if rows:
-            src, partial = src_rows_bf16, None
-            if stats_out is not None:
-                stats_out.clear()
-        pack_fn, gmm_fn = _GMM_ENTRY[bf]
-        hit = _PACKED.get((weight.data_ptr(), int(transposed), bf))
-        if hit is not None and hit[2] == weight._version and hit[1].device == src.device:
-            wp = hit[0]                                   # packed with all the model's weights by WeightPacks.refresh()
-        else:
-            wp = torch.empty(_pack_floats(weight.numel(), bf), dtype=torch.float32, device=src.device)       # MFMA-fragment order
-            L.call(pack_fn, L.ptr(weight), L.ptr(wp), Cd, rb.K, Cs, int(transposed), L.stream())
-        if rows:
-            L.call('u3d_spconv_gmm_bf16a', L.ptr(src), src.shape[0], L.ptr(wp), L.ptr(gather), L.ptr(scatter), L.ptr(rb.tile_starts(role, R)),
+            L.call('u3d_spconv_gmm_bf16a', L.ptr(src_rows_bf16), src.shape[0], L.ptr(wp), L.ptr(gather), L.ptr(scatter), L.ptr(tiles),
                    rb.K, rb.cap, Cs, Cd, n_dst, R, G, L.ptr(addend), L.ptr(dst), L.ptr(ws), float(flops), L.stream())
         else:
-            L.call(gmm_fn, L.ptr(src), src.shape[0], L.ptr(wp), L.ptr(gather), L.ptr(scatter), L.ptr(rb.tile_starts(role, R)),
+            partial = None
+            if stats_out is not None and G == 1 and _EPILOGUE_STATS:
+                n_tiles = (n_dst + R - 1) // R
+                partial = torch.empty(n_tiles, 2, Cd, dtype=torch.float32, device=src.device)
+                stats_out.update(partial=partial, n_tiles=n_tiles)
+            L.call(_GMM_ENTRY[fmt][1], L.ptr(src), src.shape[0], L.ptr(wp), L.ptr(gather), L.ptr(scatter), L.ptr(tiles),
                    rb.K, rb.cap, Cs, Cd, n_dst, R, G, L.ptr(addend), L.ptr(dst), L.ptr(ws), L.ptr(partial), float(flops), L.stream())
+    elif route == 'ts':
+        T, H = plan
+        nhalo, halo, loc, pmask = rb.halo(T, H)
+        L.call('u3d_spconv_ts_x3', L.ptr(src), n_dst, L.ptr(wp), L.ptr(nhalo), L.ptr(halo), L.ptr(loc), L.ptr(pmask), T, H, int(transposed),
+               Cs, Cd, L.ptr(addend), L.ptr(dst), float(flops), L.stream())
+    else:
+        nhalo, halo, loc, _pm = rb.halo(64, plan)
+        fn, rows = ('u3d_spconv_rs_bf16a', src_rows_bf16) if route == 'rsb' else ('u3d_spconv_rs_x3', src)
+        L.call(fn, L.ptr(rows), n_dst, L.ptr(wp), L.ptr(nhalo), L.ptr(halo), L.ptr(loc), plan, int(transposed),
+               Cs, Cd, L.ptr(addend), L.ptr(dst), int(os.environ.get('U3D_RS_WGS', '0')), float(flops), L.stream())
     return dst
-
-
-# Weight gradients on a side stream (U3D_WGRAD_SIDE_STREAM / set_wgrad_overlap):
-#   0  off: every kernel of the backward pass on the one stream;
-#   1  the weight gradient of a layer runs next to that layer's input gradient and is joined before the layer's backward returns
-#      (round 2: +0.9 % step throughput);
-#   2  decoupled: the weight gradients form their own chain on the side stream -- each waits for the gradient it reads, nothing on the
-#      main stream waits for them until the backward pass ends (an autograd-engine callback joins the streams; FlatGradBucket joins
-#      before it copies a bucket).  Nothing downstream of a layer needs its dW, so the dgrad / batch-norm chain never stalls on a
-#      weight-gradient kernel, and the small-level kernels of both chains (a few dozen workgroups each) share the chip.
-# Overlapped kernels stretch each other, so the bench's per-family HIP-event timings are taken with the overlap off.
-_WGRAD_OVERLAP = int(os.environ.get('U3D_WGRAD_SIDE_STREAM', '0') or 0)
-_SIDE = {}
-_JOIN_PENDING = {}
-
-
-def set_wgrad_overlap(mode: int) -> int:
-    global _WGRAD_OVERLAP
-    prev, _WGRAD_OVERLAP = _WGRAD_OVERLAP, int(mode)
-    return prev
-
-
-_N_SIDE = max(1, int(os.environ.get('U3D_SIDE_STREAMS', '1') or 1))      # weight-gradient chains (round-robin); A/B: tools, DESIGN.md 4.14
-_SIDE_RR = {}
-
-
-def _side_stream(device):
-    """next weight-gradient stream of ``device`` (round-robin over U3D_SIDE_STREAMS streams)"""
-    if device not in _SIDE:
-        _SIDE[device] = [torch.cuda.Stream(device=device) for _ in range(_N_SIDE)]
-        _SIDE_RR[device] = 0
-    i = _SIDE_RR[device]
-    _SIDE_RR[device] = (i + 1) % len(_SIDE[device])
-    return _SIDE[device][i]
-
-
-_ASYNC_DW_SEEN: Dict = {}       # id(parameter) -> True for parameters whose dW of the running backward pass went to the side stream
-
-
-def async_dw_ok(*params) -> bool:
-    """May the weight gradients of ``params`` (a layer's weight and bias) stay on the side stream until the backward pass ends (mode 2)?
-    Only when the ONLY consumer of each of them is autograd's AccumulateGrad storing the tensor: a leaf without an existing
-    ``.grad``, without tensor hooks or post-accumulate-grad hooks (an optimizer-in-backward would read dW on the main stream at once),
-    outside ``create_graph`` -- and used for the FIRST time in this backward pass: a parameter shared by two layers gets its two
-    gradients summed by autograd on the main stream as soon as the second arrives.  In that case (and in every other refused one) the
-    caller computes in line AND the main stream first waits for everything already queued on the side stream, so that the first
-    gradient is complete before autograd adds to it."""
-    ok = not torch.is_grad_enabled()
-    for w in params:
-        if w is None:
-            continue
-        ok = ok and w.is_leaf and w.grad is None and not getattr(w, '_backward_hooks', None) and \
-            not getattr(w, '_post_accumulate_grad_hooks', None) and id(w) not in _ASYNC_DW_SEEN
-    if ok:
-        for w in params:
-            if w is not None:
-                _ASYNC_DW_SEEN[id(w)] = True
-    elif any(w is not None and id(w) in _ASYNC_DW_SEEN for w in params):
-        join_wgrad_stream()
-    return ok
-
-
-def join_wgrad_stream(device=None):
-    """Make the current stream wait for the weight-gradient kernels queued on the side stream(s) (mode 2).  Called by the autograd
-    callback at the end of a backward pass and by anything that reads ``.grad`` of a convolution weight earlier than that
-    (``dist.FlatGradBucket`` before it copies a bucket).  A no-op when nothing is pending."""
-    for dev in ([device] if device is not None else list(_JOIN_PENDING)):
-        if _JOIN_PENDING.pop(dev, None):
-            cur = torch.cuda.current_stream(dev)
-            for st in _SIDE[dev]:
-                cur.wait_stream(st)
-
-
-def _queue_join(device):
-    """Ask the autograd engine to join the side stream(s) when the running backward pass ends.  A callback is queued for EVERY side-stream
-    launch (the first one to run joins and clears the pending flag, the rest are no-ops): a flag-guarded single callback would be lost
-    for good if a backward pass died between queueing and running it."""
-    _JOIN_PENDING[device] = True
-    torch.autograd.Variable._execution_engine.queue_callback(lambda: end_of_backward(device))
-
-
-def end_of_backward(device=None):
-    """The autograd engine's callback when a backward pass ends: join the side stream(s) and forget which parameters sent their
-    gradient there (``async_dw_ok`` counts uses per pass; a join in the middle of a pass must NOT reset that)."""
-    join_wgrad_stream(device)
-    _ASYNC_DW_SEEN.clear()
 
 
 _PROFILE_FLOPS = False      # bench.py turns this on so that launches carry exact algorithmic flops
@@ -703,25 +584,21 @@ class _SparseConvFn(torch.autograd.Function):
                 # both operands exist as bf16 rows: whole-row gathers, LDS transpose reads, bf16 MFMAs over 32 pairs (spconv_wgrad_rows.hip)
                 wg, xw, gw = 'u3d_spconv_wgrad_rows', ctx.src_shadow, dout_shadow
 
-            overlap = _WGRAD_OVERLAP if ctx.needs_input_grad[0] else 0       # (the first convolution has no input gradient to run next to)
+            def launch():
+                ws = L.scratch(ws_bytes, weight.device)       # keyed by stream: on the side stream, that stream's own workspace
+                L.call(wg, L.ptr(xw), xw.shape[0], L.ptr(gw), L.ptr(rx), L.ptr(rg), L.ptr(ts),
+                       rb.K, rb.cap, n_dy, Tw, cin, cout, L.ptr(dw), L.ptr(ws), float(flops), L.stream())
+
+            overlap = WS.mode() if ctx.needs_input_grad[0] else 0       # (the first convolution has no input gradient to run next to)
             if overlap == 2 and not async_dw_ok(weight):
                 overlap = 1      # autograd will ADD dw to an existing .grad (or feed it to another node / a hook) on this stream right away: join first
             if overlap:
-                side = _side_stream(weight.device)
-                side.wait_stream(torch.cuda.current_stream())                 # dout (and everything before it) is complete
-                with torch.cuda.stream(side):
-                    ws = L.scratch(ws_bytes, weight.device)                   # the side stream's own workspace (keyed by stream)
-                    L.call(wg, L.ptr(xw), xw.shape[0], L.ptr(gw), L.ptr(rx), L.ptr(rg), L.ptr(ts),
-                           rb.K, rb.cap, n_dy, Tw, cin, cout, L.ptr(dw), L.ptr(ws), float(flops), L.stream())
-                for t in (xw, gw, dw, ts, rx, rg):                             # blocks must not be recycled while the side kernel uses them
-                    t.record_stream(side)
+                side, _ = WS.run_on_side_stream(weight.device, launch, reads=(xw, gw, dw, ts, rx, rg))
                 if overlap == 2:
-                    _queue_join(weight.device)
+                    WS.queue_join(weight.device)
                     side = None
             else:
-                ws = L.scratch(ws_bytes, weight.device)
-                L.call(wg, L.ptr(xw), xw.shape[0], L.ptr(gw), L.ptr(rx), L.ptr(rg), L.ptr(ts),
-                       rb.K, rb.cap, n_dy, Tw, cin, cout, L.ptr(dw), L.ptr(ws), float(flops), L.stream())
+                launch()
         if ctx.needs_input_grad[0]:
             if mode == 'fwd':
                 g, s, role, n_dst = rb.pair_out, rb.pair_in, 'in', rb.n_in
@@ -729,7 +606,7 @@ class _SparseConvFn(torch.autograd.Function):
                 g, s, role, n_dst = rb.pair_in, rb.pair_out, 'out', rb.n_out
             dsrc = _gmm(dout, weight.reshape(cout, rb.K, cin).contiguous(), True, rb, g, s, role, n_dst, None, flops, ctx.bf,
                         None, dout_shadow)
-        if side is not None:
+        if side is not None:          # mode 1: joined only now, after the input gradient was queued next to it
             torch.cuda.current_stream().wait_stream(side)
         return dsrc, dw, None, None, (dout if ctx.has_addend else None), None
 
@@ -760,7 +637,7 @@ class _BNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, relu, training, sync, nbt=None, want_skip=False,
                 stats=None, yb=None, dx_shadow=False):
-        """``stats``: dict(partial, n_tiles) from the epilogue of the convolution that produced x (sparse._gmm), or None.
+        """``stats``: dict(partial, n_tiles) from the epilogue of the convolution that produced x (``_gmm``'s ``stats_out``), or None.
         ``yb`` (bf16 [n, C] or None): receives y rounded to bf16 in the same pass (precision.bf16_rows); ``dx_shadow``: the backward
         writes such a copy of dx too and attaches it to the gradient it returns (x came out of a sparse convolution)."""
         x = x.contiguous()
