@@ -635,6 +635,35 @@ int u3d_aug_sp_masks(const int64_t* inst, const int64_t* sp, const int64_t* sp_s
                      const int32_t* n_inst, const int64_t* sp_offsets, const int64_t* mask_offsets, int64_t mask_entries, int64_t n_superpoints,
                      uint8_t* masks, void* ws, u3d_stream_t stream);
 int64_t u3d_aug_sp_masks_ws_bytes(int64_t mask_entries, int64_t n_superpoints);
+/* u3d_aug_points with DenormalizePointsColor (unidet3d/loading.py:123-143) in front of the normalisation:
+ * c' = (((c * dstd) + dmean) - mean) / std in fp32 in this order, every step only when its host pointer (3 floats) is non-NULL.
+ * With both denorm pointers NULL the result equals u3d_aug_points' bit for bit. */
+int u3d_aug_points_dn(const float* src_points, int64_t src_rows, const int64_t* gather, const int64_t* src, const int64_t* pt_offsets, int B,
+                      int64_t n, const float* affine, const float* color_mean_host, const float* color_std_host,
+                      const float* denorm_mean_host, const float* denorm_std_host, float voxel_size, float* points, float* coords,
+                      u3d_stream_t stream);
+/* the ground-truth boxes of a box-annotated batch through the scenes' flip / rotation / scale / translation, one thread per box:
+ * src_boxes [src_rows][7] = (gravity centre, size, yaw) rows of the scene cache, box_src int64 [B][2] = (first row, row count) per
+ * scene, box_offsets int64 [B+1], boxes [n][7].  Centre: the point map's fp32 expression with affine [B][3][4]; size * fp32(scale);
+ * yaw in fp64 -- flip_h: pi - yaw, flip_v: -yaw, then + angle -- rounded once to fp32, no period wrapping; scalars double [B][4] =
+ * (flip_h, flip_v, angle, scale); scenes with with_yaw[b] == 0 (uint8 [B]) get yaw 0. */
+int u3d_aug_boxes(const float* src_boxes, int64_t src_rows, const int64_t* box_src, const int64_t* box_offsets, int B, int64_t n,
+                  const float* affine, const double* scalars, const uint8_t* with_yaw, float* boxes, u3d_stream_t stream);
+
+/* =====================================================================================
+ * R14  distance targets of every scene of a batch (csrc/targets.hip; unidet3d/unidet3d.py:371-409 get_targets): scene b owns the
+ *      superpoint centres centers[sp_offsets[b] .. sp_offsets[b+1]) ([n_sp][3] fp32) and the boxes box_offsets[b] .. box_offsets[b+1]
+ *      of box_centers (gravity centres, row g at box_centers + g box_ld, box_ld >= 3 floats, n_boxes rows).  masks (uint8 0 / 1)
+ *      receives scene b's [G_b][S_b] matrix row-major at mask_offsets[b] (int64 [B+1], mask_entries in all), zeros included:
+ *      d = ((cx-px)^2 + (cy-py)^2) + (cz-pz)^2 in fp32; kth[g] = the min(topk+1, S_b)-th smallest d of box g; superpoint s goes to
+ *      the box with the smallest d among those with d < kth[g] (strictly; lowest index on ties; none at d >= 1e8).  Scenes without
+ *      boxes or superpoints are valid.  max_boxes / max_sp: the largest G_b / S_b (they size the two grids).  topk + 1 <= 16, else
+ *      U3D_EUNSUPPORTED.  Two launches, no atomics.  ws: u3d_targets_by_distance_ws_bytes(n_boxes).
+ * ===================================================================================== */
+int u3d_targets_by_distance(const float* centers, int64_t n_sp, const int64_t* sp_offsets, const float* box_centers, int64_t box_ld,
+                            int64_t n_boxes, const int64_t* box_offsets, const int64_t* mask_offsets, int64_t mask_entries, int B,
+                            int64_t max_boxes, int64_t max_sp, int topk, uint8_t* masks, void* ws, u3d_stream_t stream);
+int64_t u3d_targets_by_distance_ws_bytes(int64_t n_boxes);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,6 @@ from .data_preprocessor import Det3DDataPreprocessor_  # noqa: F401
 from .unidet3d import UniDet3D  # noqa: F401
 from .structures import InstanceData_  # noqa: F401
 from . import transforms, evaluation  # noqa: F401  (registers the pipeline transforms)
-from .augment import DeviceAugment, DeviceSceneCache, AugmentDraws  # noqa: F401
+from .augment import DeviceAugment, DeviceSceneCache, MixedDeviceAugment, AugmentDraws  # noqa: F401
 
 __version__ = '0.1.0'

@@ -141,6 +141,11 @@ PROTOTYPES = {
     'u3d_aug_remap_ids': (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
     'u3d_aug_sp_masks': (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'u3d_aug_sp_masks_ws_bytes': (_i64, [_i64, _i64]),
+    'u3d_aug_points_dn': (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32),
+                                 _f32, _vp, _vp, _vp]),
+    'u3d_aug_boxes': (_i32, [_vp, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_targets_by_distance': (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'u3d_targets_by_distance_ws_bytes': (_i64, [_i64]),
 }
 
 ABI_VERSION = 116         # include/u3d.h U3D_ABI_VERSION this table was written against

@@ -21,6 +21,11 @@ Data flow of one call (B scenes, N' points after sampling):
   read 2  pass-2 extents
   device  u3d_aug_noise_blur, u3d_aug_elastic  pass 2                                  6 + 1
 
+Box-annotated scenes (MultiScan, 3RScan, ScanNet++, ARKitScenes: ``gt_bboxes_3d`` / ``gt_labels_3d`` and no per-point masks) go
+through the same chain without the instance steps: ``u3d_aug_points_dn`` when the pipeline holds ``DenormalizePointsColor``, the
+superpoint relabel of a sampled pipeline (its counts are the one read) and ``u3d_aug_boxes``, one launch for all boxes of the batch.
+``MixedDeviceAugment`` serves a batch drawn from several datasets, one ``DeviceAugment`` call per dataset present.
+
 Random draws are separated from arithmetic (``AugmentDraws``): a test injects every draw, a training loop lets
 ``DeviceAugment.draw`` take the scalars from a host generator and the per-point / per-cell draws (sample indices, noise) from torch
 on the device.  The same generator state gives the same bits twice.
@@ -30,6 +35,11 @@ states it.  mmdet3d is not a dependency of this package, so the rule is not chec
 then the translation t ~ N(0, std).  The host composes the matrix in float64 and rounds it to float32; the kernel evaluates
 x' = ((a00 x + a01 y) + a02 z) + t0 in float32.  The reference's angle ranges are symmetric ([-3.14, 3.14], [0, 0]), so the sign
 convention of the rotation does not change the distribution of the augmented scenes.
+
+Boxes follow the points: the gravity centre goes through the same float32 expression, the size is multiplied by float32(s), and the
+heading -- measured counter-clockwise from +x, as ``criterion._box2corners`` reads it -- becomes pi - yaw under the horizontal flip,
+-yaw under the vertical one, then + theta, in float64, rounded once, without period wrapping (``transforms.transform_boxes`` is the
+host twin).  A rotation of boxes without a heading would need mmdet3d's enclosing-box rule, which cannot be checked here: refused.
 """
 from __future__ import annotations
 
@@ -43,25 +53,33 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .structures import InstanceData_, PointSegData
+from .structures import DepthInstance3DBoxes, InstanceData_, PointSegData
 
-__all__ = ['DeviceSceneCache', 'DeviceAugment', 'AugmentDraws', 'compose_affine', 'blur_noise_grids']
+__all__ = ['DeviceSceneCache', 'DeviceAugment', 'MixedDeviceAugment', 'AugmentDraws', 'compose_affine', 'blur_noise_grids']
 
 _LOADERS = ('LoadPointsFromFile', 'LoadAnnotations3D_', 'LoadAnnotations3D')
 _PACKERS = ('Pack3DDetInputs_', 'Pack3DDetInputs')
 _LOAD_TIME = ('GlobalAlignment', 'PointSegClassMapping')
 _BOX_KEYS = ('gt_bboxes_3d', 'gt_bboxes', 'ann_info')
+_MASK_KEYS = ('pts_instance_mask', 'pts_semantic_mask')
 
 
 class DeviceSceneCache:
     """Pre-processed scenes (the output of ``transforms.load_scene_bins``) concatenated on the device: ``points`` float32 [N, 6],
     ``sp_pts_mask`` / ``pts_instance_mask`` / ``pts_semantic_mask`` int64 [N], host-side point offsets, ``lidar_path`` s and the
-    per-scene maximum ids (read once here, on the host; they size the relabel tables)."""
+    per-scene maximum ids (read once here, on the host; they size the relabel tables).
+
+    A cache holds scenes of one ``kind``.  'mask': the per-point instance / semantic ids above.  'box': no per-point ids but
+    ``boxes`` float32 [G, 7] = (gravity centre, size, yaw; yaw 0 for scenes whose boxes have six columns), ``box_labels`` int64 [G]
+    and ``with_yaw`` uint8 [n_scenes] on the device, ``box_offsets`` / ``scene_with_yaw`` on the host."""
 
     def __init__(self, points, sp, inst, sem, offsets, lidar_paths, max_inst, max_sp, align):
         self.points, self.sp_pts_mask, self.pts_instance_mask, self.pts_semantic_mask = points, sp, inst, sem
         self.offsets, self.lidar_paths, self.max_inst, self.max_sp, self.align = offsets, lidar_paths, max_inst, max_sp, align
         self.has_alignment = self.has_seg_mapping = False      # set by from_scene_dicts: what the load-time steps were given
+        self.kind = 'mask'
+        self.boxes = self.box_labels = self.with_yaw = None
+        self.box_offsets, self.scene_with_yaw = [0], []
 
     @property
     def device(self):
@@ -73,26 +91,57 @@ class DeviceSceneCache:
     @classmethod
     def from_scene_dicts(cls, dicts: Sequence[dict], device, seg_label_mapping=None) -> 'DeviceSceneCache':
         """``seg_label_mapping`` (optional int array): mmdet3d's ``PointSegClassMapping`` table, applied to the semantic ids here,
-        once.  A scene dict may carry ``axis_align_matrix`` [4, 4] (``GlobalAlignment``); it is composed into every affine."""
+        once.  A scene dict may carry ``axis_align_matrix`` [4, 4] (``GlobalAlignment``); it is composed into every affine.
+
+        A dict with ``gt_bboxes_3d`` float [G, 6 | 7] (gravity centre, size[, yaw]: the reference's dataset classes build their boxes
+        with ``origin=(0.5, 0.5, 0.5)``) and ``gt_labels_3d`` int [G] (G may be 0) and NO instance / semantic mask is a box-annotated
+        scene.  Box keys next to masks, other box forms and ``axis_align_matrix`` on a box scene (no reference box pipeline has
+        ``GlobalAlignment``) raise ``NotImplementedError``; mask and box scenes in one call raise ``ValueError``."""
         pts, sp, inst, sem, offs, paths, mi, ms, al = [], [], [], [], [0], [], [], [], []
+        boxes, blabels, boffs, wyaw = [], [], [0], []
+        kinds = set()
         for i, d in enumerate(dicts):
-            if any(k in d for k in _BOX_KEYS):
-                raise NotImplementedError(f'scene {i}: box annotations are not transformed on the device (box-annotated datasets are out of scope)')
+            boxed = any(k in d for k in _BOX_KEYS)
+            if boxed and any(k in d for k in _MASK_KEYS):
+                raise NotImplementedError(f'scene {i}: box annotations next to instance / semantic masks are not transformed on the device '
+                                          '(a box-annotated scene carries no per-point masks)')
+            if boxed and ('gt_bboxes_3d' not in d or 'gt_labels_3d' not in d):
+                raise NotImplementedError(f"scene {i}: box annotations are expected as 'gt_bboxes_3d' [G, 6 | 7] and 'gt_labels_3d' [G]")
+            if boxed and 'axis_align_matrix' in d:
+                raise NotImplementedError(f'scene {i}: axis_align_matrix on a box-annotated scene (no box pipeline of the reference has '
+                                          'GlobalAlignment)')
+            kinds.add('box' if boxed else 'mask')
+            if len(kinds) > 1:
+                raise ValueError(f'scene {i}: mask-annotated and box-annotated scenes in one cache; build one cache per kind')
             p = np.ascontiguousarray(np.asarray(d['points'], dtype=np.float32))
             assert p.ndim == 2 and p.shape[1] == 6, 'points: float32 [N, 6] (xyz, rgb 0..255) expected'
             ids = []
-            for key in ('sp_pts_mask', 'pts_instance_mask', 'pts_semantic_mask'):
+            for key in ('sp_pts_mask',) if boxed else ('sp_pts_mask', 'pts_instance_mask', 'pts_semantic_mask'):
                 a = np.asarray(d[key]).astype(np.int64)
                 assert a.shape == (len(p),), f'{key}: one id per point expected'
                 assert not len(a) or a.min() >= -1, f'{key}: ids below -1'
                 ids.append(a)
-            if seg_label_mapping is not None:
+            if seg_label_mapping is not None and not boxed:
                 ids[2] = np.asarray(seg_label_mapping, dtype=np.int64)[ids[2]]
             assert not len(p) or ids[0].min() >= 0, 'sp_pts_mask: superpoint ids must be non-negative'
-            pts.append(p); sp.append(ids[0]); inst.append(ids[1]); sem.append(ids[2])
+            pts.append(p); sp.append(ids[0])
+            if boxed:
+                gb = d['gt_bboxes_3d']
+                gb = np.asarray(gb.detach().cpu() if torch.is_tensor(gb) else gb, dtype=np.float32)
+                gb = gb.reshape(-1, gb.shape[-1] if gb.ndim == 2 else 7)
+                assert gb.shape[1] in (6, 7), 'gt_bboxes_3d: [G, 6] or [G, 7] (gravity centre, size[, yaw]) expected'
+                gl = d['gt_labels_3d']
+                gl = np.asarray(gl.detach().cpu() if torch.is_tensor(gl) else gl).astype(np.int64).reshape(-1)
+                assert len(gl) == len(gb), 'gt_labels_3d: one label per box expected'
+                wyaw.append(gb.shape[1] == 7)
+                boxes.append(np.concatenate((gb, np.zeros((len(gb), 7 - gb.shape[1]), np.float32)), 1))
+                blabels.append(gl)
+                boffs.append(boffs[-1] + len(gb))
+            else:
+                inst.append(ids[1]); sem.append(ids[2])
             offs.append(offs[-1] + len(p))
             paths.append(str(d.get('lidar_path', 'data/scannet/points/scene.bin')))
-            mi.append(int(ids[1].max()) if len(p) else -1)
+            mi.append(int(ids[1].max()) if len(p) and not boxed else -1)
             ms.append(int(ids[0].max()) if len(p) else -1)
             al.append(np.asarray(d.get('axis_align_matrix', np.eye(4)), dtype=np.float64).reshape(4, 4))
         dev = torch.device(device)
@@ -100,9 +149,16 @@ class DeviceSceneCache:
         def up(parts, dtype, tail):
             a = np.concatenate(parts) if parts else np.zeros((0,) + tail, dtype)
             return torch.from_numpy(a).to(dev)
-        cache = cls(up(pts, np.float32, (6,)), up(sp, np.int64, ()), up(inst, np.int64, ()), up(sem, np.int64, ()), offs, paths, mi, ms, al)
+        box = kinds == {'box'}
+        cache = cls(up(pts, np.float32, (6,)), up(sp, np.int64, ()), None if box else up(inst, np.int64, ()),
+                    None if box else up(sem, np.int64, ()), offs, paths, mi, ms, al)
         cache.has_alignment = any('axis_align_matrix' in d for d in dicts)
         cache.has_seg_mapping = seg_label_mapping is not None
+        if box:
+            cache.kind = 'box'
+            cache.boxes, cache.box_labels = up(boxes, np.float32, (7,)), up(blabels, np.int64, ())
+            cache.with_yaw = torch.from_numpy(np.asarray(wyaw, dtype=np.uint8)).to(dev)
+            cache.box_offsets, cache.scene_with_yaw = boffs, wyaw
         return cache
 
 
@@ -181,12 +237,18 @@ class DeviceAugment:
     ``axis_align_matrix`` is composed into the affine, ``seg_label_mapping`` is applied to the semantic ids once).  The test-time
     wrappers (``MultiScaleFlipAug3D``) and every other step type raise ``NotImplementedError``: this is the training path.
     Implemented: ``PointSample_``, ``RandomFlip3D``, ``GlobalRotScaleTrans``, ``NormalizePointsColor_``,
-    ``PointDetClassMappingScanNet``, ``PointDetClassMappingS3DIS``, ``ElasticTransfrom``.  Geometry, colour and label steps act on
-    disjoint columns, so their relative order is free; ``PointSample_`` must precede the class mapping and ``ElasticTransfrom``
-    must follow the geometric steps, as in the reference's lists."""
+    ``PointDetClassMappingScanNet``, ``PointDetClassMappingS3DIS``, ``ElasticTransfrom``, ``DenormalizePointsColor``.  Geometry,
+    colour and label steps act on disjoint columns, so their relative order is free; ``PointSample_`` must precede the class mapping,
+    ``DenormalizePointsColor`` must precede ``NormalizePointsColor_`` and ``ElasticTransfrom`` must follow the geometric steps, as in
+    the reference's lists.
+
+    A list without a ``PointDetClassMapping*`` step is the pipeline of a box-annotated dataset (``kind == 'box'``; the reference's
+    MultiScan / 3RScan / ScanNet++ / ARKitScenes lists); calling it on a mask-annotated cache, or a mask pipeline on a box cache,
+    raises ``ValueError``.  An instance built through the constructor has ``kind = None`` and takes the cache's kind."""
 
     def __init__(self, voxel_size, num_points=None, flip_ratio_h=0.0, flip_ratio_v=0.0, rot_range=(0.0, 0.0), scale_range=(1.0, 1.0),
-                 translation_std=(0.0, 0.0, 0.0), color_mean=None, color_std=None, mapping=None, elastic=None):
+                 translation_std=(0.0, 0.0, 0.0), color_mean=None, color_std=None, mapping=None, elastic=None, denorm_mean=None,
+                 denorm_std=None, kind=None):
         self.voxel_size = float(voxel_size)
         self.num_points = None if num_points is None else int(num_points)
         self.flip_ratio_h, self.flip_ratio_v = float(flip_ratio_h), float(flip_ratio_v)
@@ -196,6 +258,10 @@ class DeviceAugment:
                                                         else (translation_std,) * 3))
         self.color_mean = None if color_mean is None else np.broadcast_to(np.asarray(color_mean, dtype=np.float32), (3,)).copy()
         self.color_std = None if color_std is None else np.broadcast_to(np.asarray(color_std, dtype=np.float32), (3,)).copy()
+        # DenormalizePointsColor in front of the normalisation: c * denorm_std + denorm_mean (unidet3d/loading.py:123-143)
+        self.denorm_mean = None if denorm_mean is None else np.broadcast_to(np.asarray(denorm_mean, dtype=np.float32), (3,)).copy()
+        self.denorm_std = None if denorm_std is None else np.broadcast_to(np.asarray(denorm_std, dtype=np.float32), (3,)).copy()
+        self.kind = kind                  # None | 'mask' | 'box': the cache kind this pipeline is for (from_pipeline sets it)
         self.mapping = mapping            # None | ('scannet', num_classes, stuff_classes) | ('s3dis', classes)
         self.elastic = elastic            # None | dict(gran=[g0, g1], mag=[m0, m1], p=float)
         self._warned = set()
@@ -228,6 +294,10 @@ class DeviceAugment:
                 kw['translation_std'] = step.get('translation_std', [0, 0, 0])
             elif t == 'NormalizePointsColor_':
                 kw['color_mean'], kw['color_std'] = step['color_mean'], step.get('color_std', 127.5)
+            elif t == 'DenormalizePointsColor':
+                if 'NormalizePointsColor_' in seen:
+                    raise NotImplementedError('DenormalizePointsColor after NormalizePointsColor_')
+                kw['denorm_mean'], kw['denorm_std'] = step['color_mean'], step['color_std']
             elif t == 'PointDetClassMappingScanNet':
                 kw['mapping'] = ('scannet', int(step['num_classes']), list(step['stuff_classes']))
             elif t == 'PointDetClassMappingS3DIS':
@@ -240,7 +310,7 @@ class DeviceAugment:
             if t in ('RandomFlip3D', 'GlobalRotScaleTrans', 'PointSample_') and 'ElasticTransfrom' in seen:
                 raise NotImplementedError(f'{t} after ElasticTransfrom')
             seen.append(t)
-        aug = cls(voxel_size, **kw)
+        aug = cls(voxel_size, kind='box' if kw.get('mapping') is None else 'mask', **kw)
         aug.load_time_steps = tuple(load_time)
         return aug
 
@@ -266,12 +336,21 @@ class DeviceAugment:
         """``(batch_inputs_dict, batch_data_samples)`` of the scenes ``scene_ids`` of ``cache``: ``points`` / ``elastic_coords`` lists
         and ``ready_event``; per sample ``gt_pts_seg.sp_pts_mask`` / ``pts_instance_mask`` (/ ``pts_semantic_mask``),
         ``gt_instances_3d.labels_3d`` / ``sp_masks``, ``n_superpoints``, ``lidar_path`` -- dtypes and shapes of
-        ``transforms.to_batch_inputs``; the per-scene tensors are views of batch buffers."""
+        ``transforms.to_batch_inputs``; the per-scene tensors are views of batch buffers.  A box-annotated cache gives
+        ``gt_pts_seg.sp_pts_mask`` alone and ``gt_instances_3d.labels_3d`` / ``bboxes_3d`` (``DepthInstance3DBoxes``, 6 or 7 columns)."""
         from .structures import Det3DDataSample
         dev = cache.device
         B = len(scene_ids)
         if B == 0:
             raise ValueError('DeviceAugment: empty batch')
+        boxed = cache.kind == 'box'
+        if self.kind is not None and self.kind != cache.kind:
+            raise ValueError(f'DeviceAugment: a {self.kind}-annotated pipeline was called on a {cache.kind}-annotated scene cache')
+        if boxed and self.mapping is not None:
+            raise ValueError('DeviceAugment: a PointDetClassMapping step needs instance masks, the scene cache holds box annotations')
+        if boxed and self.rot_range != (0.0, 0.0) and not all(cache.scene_with_yaw[s] for s in scene_ids):
+            raise NotImplementedError('DeviceAugment: a rotation range on boxes without a heading (mmdet3d encloses the rotated box; '
+                                      'that rule cannot be checked here and no reference config uses it)')
         st = L.stream()
         self.last_launches = self.last_host_reads = 0
         for step, given, how in (('GlobalAlignment', cache.has_alignment, "no scene dict carried 'axis_align_matrix'"),
@@ -292,7 +371,7 @@ class DeviceAugment:
         N = int(off[-1])
         gate = np.asarray(draws.elastic_gate, dtype=bool) & np.asarray(m, dtype=bool) if self.elastic is not None else np.zeros(B, dtype=bool)
         affine = compose_affine(draws.flip_h, draws.flip_v, draws.angle, draws.scale, draws.trans, [cache.align[s] for s in scene_ids])
-        need_inst = sampled or self.mapping is not None
+        need_inst = (sampled or self.mapping is not None) and not boxed
         t_inst = np.concatenate(([0], np.cumsum([cache.max_inst[s] + 2 for s in scene_ids]))).astype(np.int64)
         t_sp = np.concatenate(([0], np.cumsum([cache.max_sp[s] + 2 for s in scene_ids]))).astype(np.int64)
         tab_scene = np.repeat(np.arange(B), np.diff(t_inst))
@@ -303,10 +382,21 @@ class DeviceAugment:
             drop = np.zeros(max(cl) + 1, dtype=np.uint8)
             drop[cl] = 1
         src = np.stack([[cache.offsets[s] for s in scene_ids], n_src], axis=1).astype(np.int64)
-        d_off, d_src, d_aff, d_tinst, d_tsp, d_gate, d_tscene, d_tlocal, d_drop = L.h2d_pack(
-            [(off.tolist(), torch.int64), (src.tolist(), torch.int64), (affine.tolist(), torch.float32), (t_inst.tolist(), torch.int64),
-             (t_sp.tolist(), torch.int64), (gate.astype(np.uint8).tolist(), torch.uint8), (tab_scene.tolist(), torch.int64),
-             (tab_local.tolist(), torch.int64), (drop.tolist(), torch.uint8)], dev)
+        specs = [(off.tolist(), torch.int64), (src.tolist(), torch.int64), (affine.tolist(), torch.float32), (t_inst.tolist(), torch.int64),
+                 (t_sp.tolist(), torch.int64), (gate.astype(np.uint8).tolist(), torch.uint8), (tab_scene.tolist(), torch.int64),
+                 (tab_local.tolist(), torch.int64), (drop.tolist(), torch.uint8)]
+        if boxed:
+            # the boxes ride in the same upload: (first row, count) per scene, batch offsets, (flip_h, flip_v, angle, scale) in float64
+            # and the constant that turns gravity centres into DepthInstance3DBoxes' bottom centres
+            n_box = [cache.box_offsets[s + 1] - cache.box_offsets[s] for s in scene_ids]
+            b_off = np.concatenate(([0], np.cumsum(n_box))).astype(np.int64)
+            b_src = np.stack([[cache.box_offsets[s] for s in scene_ids], n_box], axis=1).astype(np.int64)
+            scal = np.stack([np.asarray(draws.flip_h, dtype=np.float64), np.asarray(draws.flip_v, dtype=np.float64),
+                             np.asarray(draws.angle, dtype=np.float64), np.asarray(draws.scale, dtype=np.float64)], axis=1)
+            specs += [(b_src.tolist(), torch.int64), (b_off.tolist(), torch.int64), (scal.tolist(), torch.float64),
+                      ([int(cache.scene_with_yaw[s]) for s in scene_ids], torch.uint8), ([0.0, 0.0, -0.5], torch.float32)]
+        packed = L.h2d_pack(specs, dev)
+        d_off, d_src, d_aff, d_tinst, d_tsp, d_gate, d_tscene, d_tlocal, d_drop = packed[:9]
         gather = None
         if sampled and N:
             if draws.indices is not None:
@@ -322,9 +412,36 @@ class DeviceAugment:
         std = None if self.color_std is None else f3(*self.color_std.tolist())
         pts = torch.empty((N, 6), dtype=torch.float32, device=dev)
         coords = torch.empty((N, 3), dtype=torch.float32, device=dev) if self.elastic is not None else None
-        L.call('u3d_aug_points', L.ptr(cache.points), rows, L.ptr(gather), L.ptr(d_src), L.ptr(d_off), B, N, L.ptr(d_aff), mean, std,
-               self.voxel_size, L.ptr(pts), L.ptr(coords), st)
+        if self.denorm_mean is None and self.denorm_std is None:
+            L.call('u3d_aug_points', L.ptr(cache.points), rows, L.ptr(gather), L.ptr(d_src), L.ptr(d_off), B, N, L.ptr(d_aff), mean, std,
+                   self.voxel_size, L.ptr(pts), L.ptr(coords), st)
+        else:
+            dmean = None if self.denorm_mean is None else f3(*self.denorm_mean.tolist())
+            dstd = None if self.denorm_std is None else f3(*self.denorm_std.tolist())
+            L.call('u3d_aug_points_dn', L.ptr(cache.points), rows, L.ptr(gather), L.ptr(d_src), L.ptr(d_off), B, N, L.ptr(d_aff), mean, std,
+                   dmean, dstd, self.voxel_size, L.ptr(pts), L.ptr(coords), st)
         self.last_launches += 1 if N else 0
+        box_objs = box_labels = None
+        if boxed:
+            d_bsrc, d_boff, d_scal, d_wyaw, d_shift = packed[9:]
+            G = int(b_off[-1])
+            bx = torch.empty((G, 7), dtype=torch.float32, device=dev)
+            L.call('u3d_aug_boxes', L.ptr(cache.boxes), cache.boxes.shape[0], L.ptr(d_bsrc), L.ptr(d_boff), B, G, L.ptr(d_aff), L.ptr(d_scal),
+                   L.ptr(d_wyaw), L.ptr(bx), st)
+            self.last_launches += 1 if G else 0
+            # DepthInstance3DBoxes(gravity rows, origin=(0.5, 0.5, 0.5)) for the whole batch: its constructor's arithmetic with the
+            # constant from the upload (the constructor itself would copy two host tuples per scene and wait for each)
+            bx[:, :3] += bx[:, 3:6] * d_shift
+            box_objs, box_labels = [], []
+            for b, s in enumerate(scene_ids):
+                lo, hi = int(b_off[b]), int(b_off[b + 1])
+                o = DepthInstance3DBoxes.__new__(DepthInstance3DBoxes)
+                o.with_yaw = bool(cache.scene_with_yaw[s])
+                o.box_dim = 7 if o.with_yaw else 6
+                o.tensor = bx[lo:hi] if o.with_yaw else bx[lo:hi, :6]
+                o.gt_rows = None
+                box_objs.append(o)
+                box_labels.append(cache.box_labels[cache.box_offsets[s]:cache.box_offsets[s + 1]])
         read = []
         ext1 = None
         if gate.any():
@@ -418,10 +535,13 @@ class DeviceAugment:
         for b, s in enumerate(scene_ids):
             lo, hi = int(off[b]), int(off[b + 1])
             c0 = cache.offsets[s]
-            seg = PointSegData(pts_instance_mask=inst[lo:hi] if need_inst else cache.pts_instance_mask[c0:c0 + n_src[b]],
-                               sp_pts_mask=sp[lo:hi] if sampled else cache.sp_pts_mask[c0:c0 + n_src[b]],
-                               pts_semantic_mask=sem[lo:hi] if need_inst else cache.pts_semantic_mask[c0:c0 + n_src[b]])
-            gi = InstanceData_()
+            if boxed:
+                seg = PointSegData(sp_pts_mask=sp[lo:hi] if sampled else cache.sp_pts_mask[c0:c0 + n_src[b]])
+            else:
+                seg = PointSegData(pts_instance_mask=inst[lo:hi] if need_inst else cache.pts_instance_mask[c0:c0 + n_src[b]],
+                                   sp_pts_mask=sp[lo:hi] if sampled else cache.sp_pts_mask[c0:c0 + n_src[b]],
+                                   pts_semantic_mask=sem[lo:hi] if need_inst else cache.pts_semantic_mask[c0:c0 + n_src[b]])
+            gi = InstanceData_(labels_3d=box_labels[b], bboxes_3d=box_objs[b]) if boxed else InstanceData_()
             if self.mapping is not None:
                 gi = InstanceData_(labels_3d=labels[b], sp_masks=masks[int(mask_off[b]):int(mask_off[b + 1])].view(n_inst[b], int(S[b])))
             ds = Det3DDataSample(cache.lidar_paths[s], seg, gi)
@@ -470,3 +590,50 @@ class DeviceAugment:
             self.last_launches += 7
             x = out
         return x
+
+
+class MixedDeviceAugment:
+    """A batch drawn from several datasets (the joint config's ``ConcatDataset``): ``pipelines`` maps a dataset name to its
+    ``(DeviceAugment, DeviceSceneCache)``.  The pipelines differ in sampling size, ranges, colour steps and elastic ``p``, so a call
+    runs one ``DeviceAugment`` call per dataset PRESENT in the batch (not per scene) and returns the scenes in the requested order."""
+
+    def __init__(self, pipelines: dict):
+        self.pipelines = dict(pipelines)
+        for name, (aug, cache) in self.pipelines.items():
+            if aug.kind is not None and aug.kind != cache.kind:
+                raise ValueError(f'{name}: a {aug.kind}-annotated pipeline with a {cache.kind}-annotated scene cache')
+        self.last_launches = 0          # sums over the groups of the last call
+        self.last_host_reads = 0
+
+    def __call__(self, scenes, generator=None, draws: Optional[dict] = None):
+        """``scenes``: [(dataset name, scene id), ...].  ``draws`` (optional, for tests): {dataset name: AugmentDraws} for that
+        dataset's scenes in their order of appearance.  One ``ready_event`` is recorded after the last group."""
+        if not len(scenes):
+            raise ValueError('MixedDeviceAugment: empty batch')
+        groups = {}
+        for pos, (name, sid) in enumerate(scenes):
+            if name not in self.pipelines:
+                raise KeyError(f'MixedDeviceAugment: no pipeline for dataset {name!r}')
+            groups.setdefault(name, []).append((pos, sid))
+        self.last_launches = self.last_host_reads = 0
+        points, elastic, samples = [None] * len(scenes), [None] * len(scenes), [None] * len(scenes)
+        dev = None
+        for name, members in groups.items():
+            aug, cache = self.pipelines[name]
+            dev = cache.device
+            inputs, smp = aug(cache, [sid for _, sid in members], None if draws is None else draws.get(name), generator=generator)
+            self.last_launches += aug.last_launches
+            self.last_host_reads += aug.last_host_reads
+            for k, (pos, _) in enumerate(members):
+                points[pos], samples[pos] = inputs['points'][k], smp[k]
+                elastic[pos] = inputs['elastic_coords'][k] if 'elastic_coords' in inputs else None
+        out = dict(points=points)
+        if all(e is not None for e in elastic):
+            out['elastic_coords'] = elastic
+        elif any(e is not None for e in elastic):
+            raise ValueError('MixedDeviceAugment: some pipelines of the batch hold ElasticTransfrom and some do not')
+        if dev.type == 'cuda':
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            out['ready_event'] = ev
+        return out, samples

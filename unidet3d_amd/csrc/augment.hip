@@ -38,11 +38,16 @@ __device__ __forceinline__ int64_t aug_src_row(const int64_t* __restrict__ src, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- point map
+// DN: DenormalizePointsColor first (flags bit 3: c * dstd, bit 2: + dmean), then the normalisation; DN = false is the kernel
+// u3d_aug_points has always launched
+struct AugDenorm { float m0, m1, m2, s0, s1, s2; };
+
+template <bool DN>
 __global__ __launch_bounds__(256) void aug_points_k(const float* __restrict__ srcp, const int64_t* __restrict__ gather,
                                                     const int64_t* __restrict__ src, const int64_t* __restrict__ off, int B, int64_t n,
                                                     int64_t src_rows, const float* __restrict__ aff, float m0, float m1, float m2, float s0,
                                                     float s1, float s2, int flags, float vs, float* __restrict__ pts,
-                                                    float* __restrict__ coords) {
+                                                    float* __restrict__ coords, AugDenorm dn) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int b = aug_scene_of(off, B, i);
@@ -57,6 +62,10 @@ __global__ __launch_bounds__(256) void aug_points_k(const float* __restrict__ sr
     const float xo = ((a[0] * x + a[1] * y) + a[2] * z) + a[3];
     const float yo = ((a[4] * x + a[5] * y) + a[6] * z) + a[7];
     const float zo = ((a[8] * x + a[9] * y) + a[10] * z) + a[11];
+    if (DN) {
+        if (flags & 8) { r = r * dn.s0; g = g * dn.s1; bl = bl * dn.s2; }
+        if (flags & 4) { r = r + dn.m0; g = g + dn.m1; bl = bl + dn.m2; }
+    }
     if (flags & 1) { r = r - m0; g = g - m1; bl = bl - m2; }
     if (flags & 2) { r = r / s0; g = g / s1; bl = bl / s2; }
     float2* o = reinterpret_cast<float2*>(pts + i * 6);
@@ -64,6 +73,42 @@ __global__ __launch_bounds__(256) void aug_points_k(const float* __restrict__ sr
     if (coords) {
         coords[i * 3 + 0] = xo / vs; coords[i * 3 + 1] = yo / vs; coords[i * 3 + 2] = zo / vs;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- boxes
+// one thread per box of the batch: rows (cx, cy, cz, dx, dy, dz, yaw) of the cache -> the same row after the scene's flip / rotation /
+// scale / translation.  Centre: the point map's expression; size: size * float(scale); yaw in fp64 (flip_h: pi - yaw, flip_v: -yaw,
+// + angle), rounded once, no period wrapping.  scal [B][4] = (flip_h, flip_v, angle, scale); scenes with with_yaw[b] == 0 keep yaw 0.
+__global__ __launch_bounds__(256) void aug_boxes_k(const float* __restrict__ srcb, int64_t src_rows, const int64_t* __restrict__ bsrc,
+                                                   const int64_t* __restrict__ boff, int B, int64_t n, const float* __restrict__ aff,
+                                                   const double* __restrict__ scal, const uint8_t* __restrict__ with_yaw,
+                                                   float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = aug_scene_of(boff, B, i);
+    const int64_t row = aug_src_row(bsrc, nullptr, b, i, i - boff[b], src_rows);
+    float v[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (row >= 0) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) v[k] = srcb[row * 7 + k];
+    }
+    const float* a = aff + (int64_t)b * 12;
+    const double* sc = scal + (int64_t)b * 4;
+    const float s = (float)sc[3];
+    float* o = out + i * 7;
+    o[0] = ((a[0] * v[0] + a[1] * v[1]) + a[2] * v[2]) + a[3];
+    o[1] = ((a[4] * v[0] + a[5] * v[1]) + a[6] * v[2]) + a[7];
+    o[2] = ((a[8] * v[0] + a[9] * v[1]) + a[10] * v[2]) + a[11];
+    o[3] = v[3] * s; o[4] = v[4] * s; o[5] = v[5] * s;
+    float yo = 0.f;
+    if (with_yaw[b]) {
+        double y = (double)v[6];
+        if (sc[0] != 0.0) y = 3.14159265358979323846 - y;
+        if (sc[1] != 0.0) y = -y;
+        y = y + sc[2];
+        yo = (float)y;
+    }
+    o[6] = yo;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- extent
@@ -316,18 +361,44 @@ using namespace u3d;
 
 extern "C" {
 
-int u3d_aug_points(const float* src_points, int64_t src_rows, const int64_t* gather, const int64_t* src, const int64_t* pt_offsets, int B,
-                   int64_t n, const float* affine, const float* color_mean_host, const float* color_std_host, float voxel_size,
-                   float* points, float* coords, u3d_stream_t stream) {
+static int aug_points_launch(const float* src_points, int64_t src_rows, const int64_t* gather, const int64_t* src, const int64_t* pt_offsets,
+                             int B, int64_t n, const float* affine, const float* m, const float* sd, const float* dm, const float* dsd,
+                             bool dn, float voxel_size, float* points, float* coords, u3d_stream_t stream) {
     if (B < 0 || n < 0 || src_rows < 0) return U3D_EINVAL;
     if (n == 0) return U3D_OK;
     if (B == 0 || !src_points || !src || !pt_offsets || !affine || !points || !grid_ok(n)) return U3D_EINVAL;
     if (coords && !(voxel_size > 0.f)) { set_error("aug_points: voxel_size must be positive"); return U3D_EINVAL; }
-    const float* m = color_mean_host; const float* sd = color_std_host;
-    hipLaunchKernelGGL(aug_points_k, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, src_points, gather, src, pt_offsets, B, n,
-                       src_rows, affine, m ? m[0] : 0.f, m ? m[1] : 0.f, m ? m[2] : 0.f, sd ? sd[0] : 1.f, sd ? sd[1] : 1.f, sd ? sd[2] : 1.f,
-                       (m ? 1 : 0) | (sd ? 2 : 0), voxel_size, points, coords);
+    const AugDenorm d = {dm ? dm[0] : 0.f, dm ? dm[1] : 0.f, dm ? dm[2] : 0.f, dsd ? dsd[0] : 1.f, dsd ? dsd[1] : 1.f, dsd ? dsd[2] : 1.f};
+    const int flags = (m ? 1 : 0) | (sd ? 2 : 0) | (dm ? 4 : 0) | (dsd ? 8 : 0);
+    hipLaunchKernelGGL(dn ? aug_points_k<true> : aug_points_k<false>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       src_points, gather, src, pt_offsets, B, n, src_rows, affine, m ? m[0] : 0.f, m ? m[1] : 0.f, m ? m[2] : 0.f,
+                       sd ? sd[0] : 1.f, sd ? sd[1] : 1.f, sd ? sd[2] : 1.f, flags, voxel_size, points, coords, d);
     return check_launch("aug_points");
+}
+
+int u3d_aug_points(const float* src_points, int64_t src_rows, const int64_t* gather, const int64_t* src, const int64_t* pt_offsets, int B,
+                   int64_t n, const float* affine, const float* color_mean_host, const float* color_std_host, float voxel_size,
+                   float* points, float* coords, u3d_stream_t stream) {
+    return aug_points_launch(src_points, src_rows, gather, src, pt_offsets, B, n, affine, color_mean_host, color_std_host, nullptr, nullptr,
+                             false, voxel_size, points, coords, stream);
+}
+
+int u3d_aug_points_dn(const float* src_points, int64_t src_rows, const int64_t* gather, const int64_t* src, const int64_t* pt_offsets, int B,
+                      int64_t n, const float* affine, const float* color_mean_host, const float* color_std_host,
+                      const float* denorm_mean_host, const float* denorm_std_host, float voxel_size, float* points, float* coords,
+                      u3d_stream_t stream) {
+    return aug_points_launch(src_points, src_rows, gather, src, pt_offsets, B, n, affine, color_mean_host, color_std_host, denorm_mean_host,
+                             denorm_std_host, true, voxel_size, points, coords, stream);
+}
+
+int u3d_aug_boxes(const float* src_boxes, int64_t src_rows, const int64_t* box_src, const int64_t* box_offsets, int B, int64_t n,
+                  const float* affine, const double* scalars, const uint8_t* with_yaw, float* boxes, u3d_stream_t stream) {
+    if (B < 0 || n < 0 || src_rows < 0) return U3D_EINVAL;
+    if (n == 0) return U3D_OK;
+    if (B == 0 || !src_boxes || !box_src || !box_offsets || !affine || !scalars || !with_yaw || !boxes || !grid_ok(n)) return U3D_EINVAL;
+    hipLaunchKernelGGL(aug_boxes_k, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, src_boxes, src_rows, box_src, box_offsets,
+                       B, n, affine, scalars, with_yaw, boxes);
+    return check_launch("aug_boxes");
 }
 
 int u3d_aug_extent_f32(const float* coords, const int64_t* pt_offsets, int B, int64_t max_pts_per_scene, float* extent, u3d_stream_t stream) {

@@ -161,6 +161,44 @@ def instance_boxes(vb: VoxelBatch, instance_ids: torch.Tensor, n_inst_total: int
     return torch.cat(((hi + lo) / 2, hi - lo), 1)
 
 
+TARGETS_MAX_K = 16                         # csrc/targets.hip: topk + 1 values a lane keeps in registers
+
+
+def targets_by_distance(centers: torch.Tensor, sp_offsets, box_centers: torch.Tensor, box_offsets, topk: int):
+    """``UniDet3D.get_targets`` (unidet3d.py:371-409) for every scene of a batch in two launches (csrc/targets.hip).
+
+    ``centers`` float32 [S_total, 3] batch-global superpoint centres, ``sp_offsets`` host ints [B+1]; ``box_centers`` float32
+    [G_total, >=3] gravity centres in the training frame (a column view of wider rows is read in place: unit column stride, the
+    row stride is passed on), ``box_offsets`` host ints [B+1].  Returns ``(packed, mask_off)``: one bool buffer holding scene b's
+    [G_b, S_b] matrix row-major at ``mask_off[b]`` (host ints [B+1]); a scene without boxes owns an empty block."""
+    if topk + 1 > TARGETS_MAX_K:
+        raise L.U3DError(f'targets_by_distance: topk + 1 = {topk + 1} exceeds {TARGETS_MAX_K}')
+    sp_offsets, box_offsets = [int(v) for v in sp_offsets], [int(v) for v in box_offsets]
+    B = len(sp_offsets) - 1
+    assert len(box_offsets) == B + 1 and B >= 0
+    S = [sp_offsets[b + 1] - sp_offsets[b] for b in range(B)]
+    G = [box_offsets[b + 1] - box_offsets[b] for b in range(B)]
+    assert all(s >= 0 for s in S) and all(g >= 0 for g in G) and (not B or (sp_offsets[0] >= 0 and box_offsets[0] >= 0))
+    mask_off = [0]
+    for s, g in zip(S, G):
+        mask_off.append(mask_off[-1] + s * g)
+    dev = centers.device
+    packed = torch.empty(mask_off[-1], dtype=torch.bool, device=dev)
+    if not mask_off[-1]:
+        return packed, mask_off
+    assert centers.dtype == torch.float32 and centers.dim() == 2 and centers.shape[1] == 3 and sp_offsets[-1] <= centers.shape[0]
+    assert box_centers.dtype == torch.float32 and box_centers.dim() == 2 and box_centers.shape[1] >= 3 and box_offsets[-1] <= box_centers.shape[0]
+    if box_centers.stride(1) != 1 or box_centers.stride(0) < 3:
+        box_centers = box_centers[:, :3].contiguous()
+    if not box_centers.is_cuda:
+        raise L.U3DError('u3d kernels need CUDA (HIP) tensors: the product path has no CPU fallback')
+    d_sp, d_box, d_mask = L.h2d_pack([(sp_offsets, torch.int64), (box_offsets, torch.int64), (mask_off, torch.int64)], dev)
+    ws = L.scratch(L.lib().u3d_targets_by_distance_ws_bytes(box_centers.shape[0]), dev)
+    L.call('u3d_targets_by_distance', L.ptr(centers), centers.shape[0], L.ptr(d_sp), box_centers.data_ptr(), box_centers.stride(0),
+           box_centers.shape[0], L.ptr(d_box), L.ptr(d_mask), mask_off[-1], B, max(G), max(S), int(topk), L.ptr(packed), L.ptr(ws), L.stream())
+    return packed, mask_off
+
+
 # ----------------------------------------------------------------------------------------
 # inference post-processing (SURVEY.md 8f rank 1)
 # ----------------------------------------------------------------------------------------

@@ -12,6 +12,9 @@ for the reference drives these unchanged:
   ``PointDetClassMappingScanNet``   unidet3d/transforms_3d.py:148-228  (GT labels + superpoint masks)
   ``PointDetClassMappingS3DIS``     unidet3d/transforms_3d.py:86-146
   ``PointSample_``               unidet3d/transforms_3d.py:231-295
+  ``DenormalizePointsColor``     unidet3d/loading.py:109-146  (ARKitScenes: colours stored in 0..1 back to 0..255)
+  ``transform_boxes``            ground-truth boxes of a box-annotated scene through RandomFlip3D / GlobalRotScaleTrans, the host twin
+                                 of ``u3d_aug_boxes`` (csrc/augment.hip)
 
 Random draws come from numpy's global generator in the reference's order (``np.random.rand`` then three ``randn`` grids
 per elastic pass; ``np.random.choice`` for sampling), so a seeded run reproduces the reference's augmentation.  The noise
@@ -64,6 +67,57 @@ class NormalizePointsColor_(_Transform):
             pts[:, 3:6] = pts[:, 3:6] / np.asarray(self.color_std, dtype=np.float32)
         input_dict['points'] = pts
         return input_dict
+
+
+@TRANSFORMS.register_module()
+class DenormalizePointsColor(_Transform):
+    """``c * color_std + color_mean`` in float32, multiply then add (unidet3d/loading.py:138-143)."""
+
+    def __init__(self, color_mean, color_std):
+        self.color_mean, self.color_std = color_mean, color_std
+
+    def transform(self, input_dict):
+        pts = _points_array(input_dict['points']).astype(np.float32, copy=True)
+        if self.color_std is not None:
+            pts[:, 3:6] = pts[:, 3:6] * np.asarray(self.color_std, dtype=np.float32)
+        if self.color_mean is not None:
+            pts[:, 3:6] = pts[:, 3:6] + np.asarray(self.color_mean, dtype=np.float32)
+        input_dict['points'] = pts
+        return input_dict
+
+
+def transform_boxes(boxes, flip_h, flip_v, angle, scale, trans) -> np.ndarray:
+    """Boxes [G, 6 | 7] = (gravity centre, size[, yaw]) of ONE scene after the scene's flip / rotation / scale / translation, float32,
+    with the arithmetic of ``u3d_aug_boxes`` so that host and device agree bit for bit:
+
+      centre  ``((a00 x + a01 y) + a02 z) + t0`` in float32 with the float32 affine of ``augment.compose_affine`` (what the points get);
+      size    ``size * float32(scale)``;
+      yaw     in float64, rounded once: horizontal flip (x -> -x) ``pi - yaw``, vertical flip (y -> -y) ``-yaw``, then ``+ angle``; no
+              period wrapping.  The heading is measured counter-clockwise from +x, as ``criterion._box2corners`` reads it.
+
+    The flip rule is mmdet3d's for the depth frame as its documentation states it; mmdet3d is not installable next to this package,
+    so neither rule is checked against its code -- tests/test_augment_boxes_cpu.py checks that boxes and points move together.  Boxes
+    without a yaw column are not rotated (``angle`` must be 0: mmdet3d would enclose the rotated box)."""
+    from .augment import compose_affine
+    b = np.asarray(boxes, dtype=np.float32)
+    b = b.reshape(-1, b.shape[-1] if b.ndim == 2 else 6)
+    assert b.shape[1] in (6, 7), 'boxes: [G, 6] or [G, 7] expected'
+    if b.shape[1] == 6 and float(angle) != 0.0:
+        raise NotImplementedError('transform_boxes: a rotation of boxes without a heading')
+    A = compose_affine([flip_h], [flip_v], [angle], [scale], [trans])[0]
+    x, y, z = b[:, 0], b[:, 1], b[:, 2]
+    out = np.empty_like(b)
+    for r in range(3):
+        out[:, r] = ((A[r, 0] * x + A[r, 1] * y) + A[r, 2] * z) + A[r, 3]
+    out[:, 3:6] = b[:, 3:6] * np.float32(scale)
+    if b.shape[1] == 7:
+        yaw = b[:, 6].astype(np.float64)
+        if flip_h:
+            yaw = np.pi - yaw
+        if flip_v:
+            yaw = -yaw
+        out[:, 6] = (yaw + np.float64(angle)).astype(np.float32)
+    return out
 
 
 def _box_blur3(n: np.ndarray, axis: int) -> np.ndarray:
@@ -212,16 +266,25 @@ class PointSample_(_Transform):
 def to_batch_inputs(scene_dicts, device, dataset_dirs=None):
     """Pack transformed scene dicts into what ``UniDet3D.loss`` consumes (formatting.py:110-142 + data_preprocessor.py:30-42):
     ``(batch_inputs_dict, batch_data_samples)`` with every tensor on ``device``."""
-    from .structures import Det3DDataSample, InstanceData_, PointSegData
+    from .structures import DepthInstance3DBoxes, Det3DDataSample, InstanceData_, PointSegData
     pts, els, samples = [], [], []
     for d in scene_dicts:
         pts.append(torch.as_tensor(_points_array(d['points']), dtype=torch.float32).to(device))
         if 'elastic_coords' in d:
             els.append(torch.as_tensor(np.asarray(d['elastic_coords']), dtype=torch.float32).to(device))
-        inst = InstanceData_(labels_3d=torch.as_tensor(np.asarray(d['gt_labels_3d']), dtype=torch.long).to(device),
-                             sp_masks=torch.as_tensor(d['gt_sp_masks']).to(device))
-        seg = PointSegData(pts_instance_mask=torch.as_tensor(d['pts_instance_mask']).to(device),
-                           sp_pts_mask=torch.as_tensor(d['sp_pts_mask']).to(device))
+        if 'gt_bboxes_3d' in d and 'gt_sp_masks' not in d:
+            # a box-annotated scene: boxes (gravity centre, size[, yaw]) and labels, superpoint ids as the only per-point annotation
+            gb = np.asarray(d['gt_bboxes_3d'], dtype=np.float32)
+            gb = gb.reshape(-1, gb.shape[-1] if gb.ndim == 2 else 7)
+            inst = InstanceData_(labels_3d=torch.as_tensor(np.asarray(d['gt_labels_3d']), dtype=torch.long).reshape(-1).to(device),
+                                 bboxes_3d=DepthInstance3DBoxes(torch.from_numpy(gb), with_yaw=gb.shape[1] == 7, box_dim=gb.shape[1],
+                                                                origin=(0.5, 0.5, 0.5)).to(device))
+            seg = PointSegData(sp_pts_mask=torch.as_tensor(d['sp_pts_mask']).to(device))
+        else:
+            inst = InstanceData_(labels_3d=torch.as_tensor(np.asarray(d['gt_labels_3d']), dtype=torch.long).to(device),
+                                 sp_masks=torch.as_tensor(d['gt_sp_masks']).to(device))
+            seg = PointSegData(pts_instance_mask=torch.as_tensor(d['pts_instance_mask']).to(device),
+                               sp_pts_mask=torch.as_tensor(d['sp_pts_mask']).to(device))
         ds = Det3DDataSample(d.get('lidar_path', 'data/scannet/points/scene.bin'), seg, inst)
         ds.n_superpoints = int(np.asarray(d['sp_pts_mask']).max()) + 1
         samples.append(ds)

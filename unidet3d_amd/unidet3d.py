@@ -103,6 +103,7 @@ class UniDet3D(nn.Module):
         self._side_stream = None
         self._prefetched = None
         self._staged = None
+        self._centers = None
 
     def _init_layers(self, in_channels, num_channels):          # unidet3d.py:95-111
         self.input_conv = SparseSequential(
@@ -192,6 +193,31 @@ class UniDet3D(nn.Module):
         min_inds = torch.where(min_values < float_max, min_ids, n_boxes)
         return torch.nn.functional.one_hot(min_inds, num_classes=n_boxes + 1)[:, :-1].bool().T
 
+    def _distance_targets(self, insts, dsets, batch_offsets):
+        """``sp_masks`` of every ``target_by_distance`` scene of the batch from one kernel chain (``ops.targets_by_distance``: two
+        launches, one upload and at most one ``cat`` for the batch; ``get_targets`` above costs about ten launches per scene).  The
+        other scenes take part with zero boxes, so the batch-global centre tensor and ``batch_offsets`` are passed as they are.  A
+        scene without boxes gets an empty [0, S] matrix (``get_targets`` raises there, like the reference).  Beyond the kernel's
+        ``topk + 1 <= 16`` the per-scene torch path runs."""
+        topk = self.train_cfg['topk']
+        tbd = [bool(self.target_by_distance[d]) for d in dsets]
+        if not any(tbd):
+            return
+        if topk + 1 > ops.TARGETS_MAX_K:
+            for inst, t in zip(insts, tbd):
+                if t:
+                    inst.sp_masks = self.get_targets(inst.sp_centers, inst.bboxes_3d, topk)
+            return
+        parts, box_off = [], [0]
+        for inst, t in zip(insts, tbd):
+            if t:
+                parts.append(inst.bboxes_3d.gravity_center)      # a column view of the cached (centre, size[, heading]) rows
+            box_off.append(box_off[-1] + (len(parts[-1]) if t else 0))
+        packed, mask_off = ops.targets_by_distance(self._centers, batch_offsets, parts[0] if len(parts) == 1 else torch.cat(parts), box_off, topk)
+        for i, (inst, t) in enumerate(zip(insts, tbd)):
+            if t:
+                inst.sp_masks = packed[mask_off[i]:mask_off[i + 1]].view(box_off[i + 1] - box_off[i], batch_offsets[i + 1] - batch_offsets[i])
+
     # ------------------------------------------------------------------ shared front end
     def _front(self, batch_inputs_dict, batch_data_samples, training: bool):
         points = batch_inputs_dict['points']
@@ -214,6 +240,7 @@ class UniDet3D(nn.Module):
         else:
             centers = ops.superpoint_centers(vb.points, plan.sp_offsets, plan.sp_points, bias,
                                              vb.stats if training else None, vb.pt_offsets if training else None)
+        self._centers = centers                        # the batch-global tensor the per-scene views below are cut from
         sp_centers = [centers[batch_offsets[i]:batch_offsets[i + 1]] for i in range(B)]
         names = [self.get_dataset(ds.lidar_path) for ds in batch_data_samples]
         return vb, plan, batch_offsets, sp_centers, names
@@ -235,7 +262,8 @@ class UniDet3D(nn.Module):
             # this was two masked [instances x points x 3] min / max reductions (85 us each at 100 k points).
             ids = []
             for ds, m in zip(batch_data_samples, by_mask):
-                pm = ds.gt_pts_seg.pts_instance_mask.to(vb.points.device)
+                pm = ds.gt_pts_seg.pts_instance_mask          # None: a box-annotated scene (it needs no instance ids)
+                pm = (pm if pm is not None or m else ds.gt_pts_seg.sp_pts_mask).to(vb.points.device)
                 ids.append(pm if m else torch.full_like(pm, -1))
                 box_off.append(box_off[-1] + (len(ds.gt_instances_3d.labels_3d) if m else 0))
             if box_off[-1] > 0:
@@ -269,9 +297,8 @@ class UniDet3D(nn.Module):
                 inst.bboxes_3d._u3d_unshifted = b
                 inst.bboxes_3d.cache_gt_rows()             # (gravity centre, size[, heading]): read by get_targets below and by the criterion
             inst.sp_centers = sp_centers[i]
-            if self.target_by_distance[dataset]:
-                inst.sp_masks = self.get_targets(inst.sp_centers, inst.bboxes_3d, self.train_cfg['topk'])
             sp_gt_instances.append(inst)
+        self._distance_targets(sp_gt_instances, dsets, batch_offsets)
         x = self._sparse_input(B)
         if hasattr(self.unet, 'prepare_geometry'):
             self.unet.prepare_geometry(x)
