@@ -103,6 +103,9 @@ def _oriented_box_intersection_2d(c1, c2):
     verts = torch.cat((c1, c2, pts), -2)                                                    # (..., 24, 2)
     mask = torch.cat((_corners_inside(c1, c2), _corners_inside(c2, c1), m_int), -1)       # (..., 24)
     with torch.no_grad():
+        # a candidate that repeats an earlier one (coincident boxes) is passed over, as mmcv's vertex sort does: the first copy stays
+        same = ((verts[..., :, None, :] - verts[..., None, :, :]).abs() <= 1e-8).all(-1) & mask[..., None, :]
+        mask = mask & ~torch.tril(same, -1).any(-1)
         nv = mask.sum(-1, keepdim=True).clamp(min=1)
         mean = (verts * mask[..., None]).sum(-2, keepdim=True) / nv[..., None]
         d = verts - mean

@@ -100,7 +100,8 @@ __device__ __forceinline__ float centre_term(const Box6& p, const Box6& t) {    
 // gradient).  Same stages and constants as the tensor-op formulation in unidet3d_amd/criterion.py, which is pinned by the
 // reference's golden vectors (tests/golden/ref_criterion.npz F.rot, C2): corners, 16 edge-edge intersections with the strict
 // 0 < t, u < 1 test (point = a + t2 (b - a), t2 = den_t / (num + 1e-8)), corners of one rectangle inside the other (1e-6 slack),
-// candidates ordered by angle around their mean (no gradient through the order), shoelace area, |.|, zero below 3 vertices.
+// repeated candidates dropped (the first copy stays), the rest ordered by angle around their mean (no gradient through the order),
+// shoelace area, |.|, zero below 3 vertices.
 struct Dual {
     float v, d[7];
     __device__ __forceinline__ Dual() {}
@@ -180,6 +181,24 @@ __device__ __forceinline__ void corners_inside(const S (&x1)[4], const S (&y1)[4
     }
 }
 
+// A candidate that repeats an earlier one (coincident boxes: every corner of one is a corner of the other) is passed over, as mmcv's
+// vertex sort does (it only moves on to a vertex strictly after the previous one): the FIRST copy stays, so the predicted box's own
+// corner carries the gradient.  Left in, the copies share an angle and the polygon's visiting order -- and with it the gradient --
+// would depend on the order of equal keys.  Values only; kept out of line so that the callers' code does not grow with it.
+__device__ __noinline__ void drop_repeated_values(const float* x, const float* y, bool* ok) {
+    for (int k = 1; k < 24; ++k) {
+        if (!ok[k]) continue;
+        for (int j = 0; j < k; ++j)
+            if (ok[j] && fabsf(x[k] - x[j]) <= 1e-8f && fabsf(y[k] - y[j]) <= 1e-8f) { ok[k] = false; break; }
+    }
+}
+template <typename S> __device__ __forceinline__ void drop_repeated(const S (&vx)[24], const S (&vy)[24], bool (&ok)[24]) {
+    float x[24], y[24];
+#pragma unroll
+    for (int k = 0; k < 24; ++k) { x[k] = val(vx[k]); y[k] = val(vy[k]); }
+    drop_repeated_values(x, y, ok);
+}
+
 // 1 - DIoU of a predicted box p and a target t, both (x, y, z, w, h, l, alpha)
 template <typename S>
 __device__ S rotated_diou_loss(const S (&p)[7], const float (&tf)[7]) {
@@ -223,6 +242,7 @@ __device__ S rotated_diou_loss(const S (&p)[7], const float (&tf)[7]) {
             }
         }
     }
+    drop_repeated(vx, vy, ok);
     // ---- order the valid candidates by angle around their mean (values only), shoelace area ----
     int nvert = 0;
     float mx = 0.f, my = 0.f;
