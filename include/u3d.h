@@ -34,7 +34,8 @@ typedef void* u3d_stream_t; /* hipStream_t */
 #define U3D_EUNSUPPORTED (-3) /* channel combination not instantiated */
 
 /* Bumped with every change of an entry point's argument list; unidet3d_amd/_lib.py refuses a library whose version differs from
- * the one it was written against (a stale .so would misread shifted arguments instead of failing). */
+ * the one it was written against (a stale .so would misread shifted arguments instead of failing).  Entry points that are only
+ * ADDED (R15) leave it alone: no existing argument list moves, and _lib.py refuses a library that lacks a declared symbol. */
 #define U3D_ABI_VERSION 116
 int u3d_version(void);
 const char* u3d_last_error(void);
@@ -664,6 +665,36 @@ int u3d_targets_by_distance(const float* centers, int64_t n_sp, const int64_t* s
                             int64_t n_boxes, const int64_t* box_offsets, const int64_t* mask_offsets, int64_t mask_entries, int B,
                             int64_t max_boxes, int64_t max_sp, int topk, uint8_t* masks, void* ws, u3d_stream_t stream);
 int64_t u3d_targets_by_distance_ws_bytes(int64_t n_boxes);
+
+/* =====================================================================================
+ * R15  optimizer tail of a training step (csrc/optim.hip): global gradient norm, clipping and AdamW with decoupled weight decay
+ *      over every parameter tensor in two launches -- torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW of the reference's
+ *      optim_wrapper (configs/unidet3d_1xb8_scannet.py:710-715).  Both entry points read one device table `rows`, int64 [n_rows][8]:
+ *        0 parameter pointer (fp32)        1 gradient pointer (fp32; 0: the parameter is skipped this step)
+ *        2 offset of the row's moments in exp_avg / exp_avg_sq, in floats, a multiple of 4      3 numel
+ *        4 lr, 5 weight decay (the bit patterns of two doubles)
+ *        6 global steps the parameter has missed: its own step count, which the bias corrections use, is step - rows[i][6] >= 1
+ *        7 first block: row i owns blocks [rows[i][7], rows[i][7] + ceil(numel / U3D_OPTIM_CHUNK)), rows ascending, total_blocks in all
+ *      Block b serves the last row whose first block is <= b.  A row whose parameter and gradient pointers are 16-byte aligned moves
+ *      dwordx4, any other row dwords, with the same arithmetic per element: results do not depend on alignment.  No atomics, every
+ *      sum in a fixed order: results are bit-reproducible.  Gradients are only read (p.grad stays unclipped).
+ * ===================================================================================== */
+#define U3D_OPTIM_CHUNK 4096     /* elements of a row per block */
+#define U3D_OPTIM_PARTIALS 512   /* fp64 partial sums of squares in the workspace */
+int u3d_optim_chunk(void);       /* U3D_OPTIM_CHUNK of the library that was loaded */
+int64_t u3d_optim_ws_bytes(void);
+/* ws[j] (double) = sum over the gradient elements of chunk run j of g^2, squares and sums in fp64.  One launch. */
+int u3d_optim_grad_sumsq(const void* rows, int n_rows, int64_t total_blocks, void* ws, u3d_stream_t stream);
+/* One launch.  max_norm > 0: norm = sqrt(sum of ws) rounded to fp32 is stored to *total_norm (one thread) and every gradient is
+ * read as g * min(1, max_norm / (norm + 1e-6)) (fp32; ws from u3d_optim_grad_sumsq on the same table and stream);
+ * max_norm <= 0: no clipping, ws and total_norm are not touched.  Then, per element, in the order and mixed precision of torch's fused
+ * AdamW (doubles for the hyper-parameters, one rounding to fp32 per assignment), with t the row's own step count:
+ *   p -= lr wd p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
+ * step: the global step count INCLUDING this step (>= 1).  U3D_EINVAL, before any launch: rows NULL, n_rows or total_blocks
+ * negative, a moment buffer that is NULL or not 16-byte aligned, step < 1, clipping without ws / total_norm. */
+int u3d_optim_adamw(const void* rows, int n_rows, int64_t total_blocks, float* exp_avg, float* exp_avg_sq, double beta1, double beta2,
+                    double eps, float max_norm, int64_t step, const void* ws, float* total_norm, u3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,5 +13,6 @@ from .unidet3d import UniDet3D  # noqa: F401
 from .structures import InstanceData_  # noqa: F401
 from . import transforms, evaluation  # noqa: F401  (registers the pipeline transforms)
 from .augment import DeviceAugment, DeviceSceneCache, MixedDeviceAugment, AugmentDraws  # noqa: F401
+from .optim import FlatAdamW, OPTIMIZERS  # noqa: F401  (registers the optimizer)
 
 __version__ = '0.1.0'
