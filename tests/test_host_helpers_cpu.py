@@ -64,6 +64,70 @@ def test_async_weight_gradient_guard():
     sparse._ASYNC_DW_SEEN.clear()
 
 
+def test_async_weight_gradient_guard_forgets_an_aborted_pass_and_survives_a_nested_one():
+    """wgrad_stream counts the uses of a parameter per backward pass, here with real autograd passes on CPU leaves:
+    a pass that dies of an exception never runs its end-of-backward callback, and what it left behind must not make the next pass
+    refuse the same parameters; the callback of a pass NESTED in another one must not reset the count of the pass around it."""
+    from unidet3d_amd import wgrad_stream as WS
+    cpu = torch.device('cpu')
+    w, v = torch.zeros(3, requires_grad=True), torch.zeros(3, requires_grad=True)
+    answers = []
+
+    class Use(torch.autograd.Function):            # stands for a layer whose backward asks for the side stream, as dense._LinearFn does
+        @staticmethod
+        def forward(ctx, x, p, tag, inner=None):
+            ctx.p, ctx.tag, ctx.inner = p, tag, inner
+            return x * 1.0
+
+        @staticmethod
+        def backward(ctx, g):
+            if ctx.inner is not None:
+                ctx.inner()
+            ok = WS.async_dw_ok(ctx.p)
+            answers.append((ctx.tag, ok))
+            if ok:
+                WS.queue_join(cpu)
+            return g, None, None, None
+
+    def boom(g):
+        raise RuntimeError('hook')
+
+    WS._ASYNC_DW_SEEN.clear()
+    try:
+        # (1) an aborted pass: the layer nearest the loss has asked (and queued its callback) when the hook below it raises
+        x = torch.ones(3, requires_grad=True)
+        h = Use.apply(x, v, 'below')
+        h.register_hook(boom)
+        y = Use.apply(h, w, 'above')
+        try:
+            y.sum().backward()
+            raise AssertionError('the hook did not raise')
+        except RuntimeError as e:
+            assert 'hook' in str(e)
+        assert answers == [('above', True)] and id(w) in WS._ASYNC_DW_SEEN          # left behind: no callback ran
+        # (2) the next pass over the same parameters gets the side stream again, counts its own uses, and cleans up after itself
+        del answers[:]
+        x = torch.ones(3, requires_grad=True)
+        Use.apply(Use.apply(Use.apply(x, w, 'first'), v, 'other'), w, 'second').sum().backward()
+        assert answers == [('second', True), ('other', True), ('first', False)]     # the second use of w in ONE pass is still refused
+        assert not WS._ASYNC_DW_SEEN
+        # (3) a nested pass between two uses of w in the outer pass: its callback leaves the outer pass's count alone
+        del answers[:]
+
+        def inner():
+            with torch.enable_grad():
+                z = torch.ones(3, requires_grad=True)
+                Use.apply(z, v, 'nested').sum().backward()
+            assert id(w) in WS._ASYNC_DW_SEEN and id(v) not in WS._ASYNC_DW_SEEN     # the nested callback forgot its own entry only
+        x = torch.ones(3, requires_grad=True)
+        Use.apply(Use.apply(x, w, 'outer 2', inner), w, 'outer 1').sum().backward()
+        assert answers == [('outer 1', True), ('nested', True), ('outer 2', False)]
+        assert not WS._ASYNC_DW_SEEN
+    finally:
+        WS._ASYNC_DW_SEEN.clear()
+        WS._JOIN_PENDING.pop(cpu, None)
+
+
 def test_offset_ids_matches_the_per_scene_loop():
     from unidet3d_amd.ops import offset_ids
     g = torch.Generator().manual_seed(3)

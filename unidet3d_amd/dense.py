@@ -128,6 +128,10 @@ def _planes_of(mat):
     context; None outside one.  Callers keep the tensor (ctx) for as long as a launch may read it."""
     if _WT_ACTIVE is None or mat is None:
         return None
+    # a weight modified in place since the context was entered: its planes are stale, like its transposed copy (``_wt_of``) -> None,
+    # and the kernel splits the operand itself.  (A transposed copy has no entry in ``_versions``: ``_wt_of`` has vouched for it.)
+    if _WT_ACTIVE.get('_versions', {}).get(mat.data_ptr(), mat._version) != mat._version:
+        return None
     return _WT_ACTIVE.get('_planes', {}).get(mat.data_ptr())
 
 
@@ -331,6 +335,10 @@ class _MLPFn(torch.autograd.Function):
                 L.call('u3d_gelu_bwd', L.ptr(da), L.ptr(h), L.ptr(dh), da.numel(), L.stream())
         dw1, db1 = _weight_grad_overlapped(dh, x, ctx.bias[0] and need[2], ctx.bf, w1, ctx.bias_refs[0]) if need[1] else (None, None)
         dx = _input_grad(dh, w1, bf=ctx.bf, wt=ctx.wt1, wt_planes=ctx.wtp1) if need[0] else None
+        if db2 is None and ctx.bias[1] and need[4]:          # a trainable bias on a frozen weight: no u3d_gemm_tn to ride along with
+            db2 = dz.sum(0)
+        if db1 is None and ctx.bias[0] and need[2]:
+            db1 = dh.sum(0)
         return dx, dw1, db1, dw2, db2, None
 
 

@@ -206,6 +206,10 @@ class _MLP16Fn(torch.autograd.Function):
         if need[0]:
             wt1, _ = _transposed(w1, ctx.wt1)
             dx = gemm_nt(dh, wt1)
+        if db2 is None and ctx.bias[1] and need[4]:          # a trainable bias on a frozen weight: no u3d_gemm_tn_b16 to ride along with
+            db2 = dz.float().sum(0)
+        if db1 is None and ctx.bias[0] and need[2]:
+            db1 = dh.float().sum(0)
         return dx, dw1, db1, dw2, db2, None
 
 

@@ -23,7 +23,7 @@ _N_SIDE = max(1, int(os.environ.get('U3D_SIDE_STREAMS', '1') or 1))      # weigh
 _SIDE: Dict = {}
 _SIDE_RR: Dict = {}
 _JOIN_PENDING: Dict = {}
-_ASYNC_DW_SEEN: Dict = {}       # id(parameter) -> True for parameters whose dW of the running backward pass went to the side stream
+_ASYNC_DW_SEEN: Dict = {}       # id(parameter) -> pass (``_pass_id``) whose dW of that parameter went to the side stream
 
 
 def set_wgrad_overlap(mode: int) -> int:
@@ -66,6 +66,12 @@ def run_on_side_stream(device, launch, reads):
     return side, made
 
 
+def _pass_id() -> int:
+    """The running backward pass: the autograd engine's graph-task id (-1 outside a backward pass).  Ids grow for the life of the process,
+    and a nested pass (a backward call made inside a backward pass) has its own, larger than the pass around it."""
+    return torch._C._current_graph_task_id()
+
+
 def async_dw_ok(*params) -> bool:
     """May the weight gradients of ``params`` (a layer's weight and bias) stay on the side stream until the backward pass ends (mode 2)?
     Only when the ONLY consumer of each of them is autograd's AccumulateGrad storing the tensor: a leaf without an existing
@@ -73,17 +79,21 @@ def async_dw_ok(*params) -> bool:
     outside ``create_graph`` -- and used for the FIRST time in this backward pass: a parameter shared by two layers gets its two
     gradients summed by autograd on the main stream as soon as the second arrives.  In that case (and in every other refused one) the
     caller computes in line AND the main stream first waits for everything already queued on the side stream, so that the first
-    gradient is complete before autograd adds to it."""
+    gradient is complete before autograd adds to it.
+    Uses are counted PER PASS: an entry another pass left behind -- one that died of an exception before its end-of-backward callback
+    ran -- does not count, so the next pass gets the side stream again.  An entry of the pass AROUND a nested one is
+    not this pass's either; it is kept (the outer pass goes on counting with it) and still makes a refused caller join."""
     ok = not torch.is_grad_enabled()
+    task = _pass_id()
     for w in params:
         if w is None:
             continue
         ok = ok and w.is_leaf and w.grad is None and not getattr(w, '_backward_hooks', None) and \
-            not getattr(w, '_post_accumulate_grad_hooks', None) and id(w) not in _ASYNC_DW_SEEN
+            not getattr(w, '_post_accumulate_grad_hooks', None) and _ASYNC_DW_SEEN.get(id(w)) != task
     if ok:
         for w in params:
             if w is not None:
-                _ASYNC_DW_SEEN[id(w)] = True
+                _ASYNC_DW_SEEN[id(w)] = task
     elif any(w is not None and id(w) in _ASYNC_DW_SEEN for w in params):
         join_wgrad_stream()
     return ok
@@ -94,7 +104,7 @@ def join_wgrad_stream(device=None):
     callback at the end of a backward pass and by anything that reads ``.grad`` of a convolution weight earlier than that
     (``dist.FlatGradBucket`` before it copies a bucket).  A no-op when nothing is pending."""
     for dev in ([device] if device is not None else list(_JOIN_PENDING)):
-        if _JOIN_PENDING.pop(dev, None):
+        if _JOIN_PENDING.pop(dev, None) and dev in _SIDE:
             cur = torch.cuda.current_stream(dev)
             for st in _SIDE[dev]:
                 cur.wait_stream(st)
@@ -105,11 +115,18 @@ def queue_join(device):
     launch (the first one to run joins and clears the pending flag, the rest are no-ops): a flag-guarded single callback would be lost
     for good if a backward pass died between queueing and running it."""
     _JOIN_PENDING[device] = True
-    torch.autograd.Variable._execution_engine.queue_callback(lambda: end_of_backward(device))
+    task = _pass_id()
+    torch.autograd.Variable._execution_engine.queue_callback(lambda: end_of_backward(device, task))
 
 
-def end_of_backward(device=None):
-    """The autograd engine's callback when a backward pass ends: join the side stream(s) and forget which parameters sent their
-    gradient there (``async_dw_ok`` counts uses per pass; a join in the middle of a pass must NOT reset that)."""
+def end_of_backward(device=None, task=None):
+    """The autograd engine's callback when backward pass ``task`` ends: join the side stream(s) and forget which parameters sent their
+    gradient there in that pass (``async_dw_ok`` counts uses per pass; a join in the middle of a pass must NOT reset that) -- and in
+    the passes nested in it, all over by now (larger ids).  The entries of a pass AROUND it stay: the callback of a nested pass must
+    not reset the count of the pass it runs in.  ``task`` None (a direct call): forget everything."""
     join_wgrad_stream(device)
-    _ASYNC_DW_SEEN.clear()
+    if task is None:
+        _ASYNC_DW_SEEN.clear()
+    else:
+        for k in [k for k, t in _ASYNC_DW_SEEN.items() if t >= task]:
+            del _ASYNC_DW_SEEN[k]
