@@ -696,6 +696,48 @@ int u3d_optim_grad_sumsq(const void* rows, int n_rows, int64_t total_blocks, voi
 int u3d_optim_adamw(const void* rows, int n_rows, int64_t total_blocks, float* exp_avg, float* exp_avg_sq, double beta1, double beta2,
                     double eps, float max_norm, int64_t step, const void* ws, float* total_norm, u3d_stream_t stream);
 
+/* =====================================================================================
+ * R16  detection evaluation of a whole validation pass (csrc/evalmap.hip): mAP / mAR at IoU thresholds as the reference's
+ *      indoor_eval computes them (unidet3d/indoor_eval.py:56-161 eval_det_cls, :8-53 average_precision; the host restatement is
+ *      unidet3d_amd/evaluation.py).  One dataset's pass is packed image after image: det_boxes [D][7], det_scores [D], det_labels
+ *      int32 [D], det_off int32 [I+1]; gt_boxes [G][7], gt_labels int32 [G], gt_off int32 [I+1] (offsets ascending from 0).  Boxes
+ *      are bottom-centre depth boxes (x, y, z_bottom, dx, dy, dz, yaw), six-column boxes packed with yaw 0.  C classes
+ *      (<= U3D_EVAL_MAX_CLASSES), T thresholds (<= U3D_EVAL_MAX_THR); a label outside [0, C) matches nothing, is not counted and
+ *      sorts behind every class.  Zero sizes are valid; nothing is launched for an empty dimension.  Integer atomics only; every
+ *      floating-point sum has a fixed order: results are bit-reproducible.  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+#define U3D_EVAL_MAX_CLASSES 1024
+#define U3D_EVAL_MAX_THR 8
+#define U3D_EVAL_GT_CHUNK 128    /* ground truths of an image staged in LDS at a time (an image may have more) */
+int u3d_eval_gt_chunk(void);     /* U3D_EVAL_GT_CHUNK of the library that was loaded */
+/* iou_max [D]: the largest 3-D IoU (BEV intersection x height overlap over the union of the volumes, union clamped at 1e-8) of the
+ * detection with a ground truth of its class in its image, -inf when there is none; jmax int32 [D]: the packed index of that
+ * ground truth -- the first maximum of a strict '>' scan in ground-truth order (indoor_eval.py:132-139) -- or -1.  A pair whose
+ * two headings are both exactly 0 takes the axis-aligned fp32 expression in evaluation.boxes_iou_3d's operation order (bit-equal
+ * to it); any other pair the rotated-rectangle intersection, evaluated in fp64 and rounded once.  n_gt / n_det int32 [C]: the
+ * class histograms (zeroed here).  ws is not used (u3d_eval_match_ws_bytes returns 0; NULL is fine). */
+int u3d_eval_match(const float* det_boxes, const int32_t* det_labels, const int32_t* det_off, const float* gt_boxes, const int32_t* gt_labels,
+                   const int32_t* gt_off, int64_t D, int64_t G, int64_t I, int C, float* iou_max, int32_t* jmax, int32_t* n_gt, int32_t* n_det,
+                   void* ws, u3d_stream_t stream);
+int64_t u3d_eval_match_ws_bytes(int64_t D, int64_t G);
+/* perm int32 [D]: the detections in evaluation order -- class ascending, score descending, ties by packed index (stable): one
+ * u3d_sort_u64 over class << 32 | order-preserving uint of -score.  Any finite score orders correctly, -0 ties with +0, NaN scores
+ * come last in their class (where numpy's sort puts them). */
+int u3d_eval_order(const float* det_scores, const int32_t* det_labels, int64_t D, int C, int32_t* perm, void* ws, u3d_stream_t stream);
+int64_t u3d_eval_order_ws_bytes(int64_t D);
+/* Every (class, threshold) pair from the outputs of the two calls above.  The detection at sorted rank r is a true positive at
+ * threshold t iff iou_max > thr[t] and r is the smallest rank among the detections with iou_max > thr[t] that name the same jmax
+ * (integer atomicMin per (ground truth, threshold)); everything else is a false positive.  Cumulative counts, recall = tp / n_gt and
+ * precision = tp / max(tp + fp, eps) in fp64 over the class segment; AP = the all-points area of average_precision(mode='area').
+ * thr_host: T floats on the HOST (passed on as a kernel argument).  ap / rec float [T][C] (rec: the last recall of the segment): NaN
+ * for a class with detections and no ground truth (the host's 0 / 0), 0 for a class without detections.  tp_flag uint8 [T][D] and
+ * tp_cum int32 [T][D] (both nullable): flag and cumulative true positives inside the class segment, by sorted rank (the false
+ * positives up to rank r of a segment that starts at s are r - s + 1 - tp_cum); ranks of labels outside [0, C) are not written. */
+int u3d_eval_sweep(const float* iou_max, const int32_t* jmax, const int32_t* perm, const int32_t* n_gt, const int32_t* n_det,
+                   const float* thr_host, int64_t D, int64_t G, int C, int T, float* ap, float* rec, uint8_t* tp_flag, int32_t* tp_cum,
+                   void* ws, u3d_stream_t stream);
+int64_t u3d_eval_sweep_ws_bytes(int64_t D, int64_t G, int T);
+
 #ifdef __cplusplus
 }
 #endif

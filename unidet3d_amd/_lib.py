@@ -150,6 +150,13 @@ PROTOTYPES = {
     'u3d_optim_ws_bytes': (_i64, []),
     'u3d_optim_grad_sumsq': (_i32, [_vp, _i32, _i64, _vp, _vp]),
     'u3d_optim_adamw': (_i32, [_vp, _i32, _i64, _vp, _vp, _f64, _f64, _f64, _f32, _i64, _vp, _vp, _vp]),
+    'u3d_eval_gt_chunk': (_i32, []),
+    'u3d_eval_match': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_eval_match_ws_bytes': (_i64, [_i64, _i64]),
+    'u3d_eval_order': (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    'u3d_eval_order_ws_bytes': (_i64, [_i64]),
+    'u3d_eval_sweep': (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_eval_sweep_ws_bytes': (_i64, [_i64, _i64, _i32]),
 }
 
 ABI_VERSION = 116         # include/u3d.h U3D_ABI_VERSION this table was written against
@@ -179,7 +186,7 @@ def lib():
                            '(`python -m unidet3d_amd.csrc.build`); a stale library would misread the arguments')
         for name, (res, args) in PROTOTYPES.items():
             f = getattr(l, name, None)
-            if f is None:      # same version, older build: entry points added without a version change (u3d_optim_*)
+            if f is None:      # same version, older build: entry points added without a version change (u3d_optim_*, u3d_eval_*)
                 raise U3DError(f'{LIB_PATH} does not export {name}: rebuild it (`python -m unidet3d_amd.csrc.build`)')
             f.restype = res
             f.argtypes = args

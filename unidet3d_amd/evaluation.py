@@ -181,3 +181,143 @@ class IndoorMetric:
             preds = [p for a, p in self.results if p['dataset'] == name]
             out[name] = indoor_eval(anns, preds, self.iou_thr, self.datasets_classes[i])
         return out
+
+
+# ---- the same protocol on the device (csrc/evalmap.hip): no per-detection host loop, one device-to-host read per dataset ----
+def _upload(t: torch.Tensor, device) -> torch.Tensor:
+    """Host tensor -> ``device`` without draining the stream (pinned staging, non-blocking copy); device tensors pass through."""
+    if t.is_cuda or torch.device(device).type != 'cuda' or not t.numel():
+        return t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def _cat_to(ts: List[torch.Tensor], device, dtype, tail=()) -> torch.Tensor:
+    """``torch.cat`` of the non-empty tensors on ``device``; host tensors are joined on the host first and go up in one copy."""
+    ts = [t for t in ts if t.shape[0]]
+    if not ts:
+        return torch.zeros((0, *tail), dtype=dtype, device=device)
+    if not any(t.is_cuda for t in ts):
+        return _upload(torch.cat(ts).to(dtype), device)
+    return torch.cat([_upload(t, device) for t in ts]).to(dtype)
+
+
+def _rows7(boxes: List[torch.Tensor], device) -> torch.Tensor:
+    """Box tensors [n_i, 6 or 7] -> one float32 [sum n_i, 7]; six-column boxes get heading 0."""
+    boxes = [b for b in boxes if b.shape[0]]
+    if len({b.shape[1] for b in boxes}) > 1:
+        boxes = [b if b.shape[1] == 7 else torch.nn.functional.pad(b, (0, 1)) for b in boxes]
+    out = _cat_to(boxes, device, torch.float32, (7,))
+    return (torch.nn.functional.pad(out, (0, 1)) if out.shape[1] == 6 else out).contiguous()
+
+
+def _labels_tensor(x) -> torch.Tensor:
+    return x.reshape(-1) if torch.is_tensor(x) else torch.tensor([int(v) for v in x], dtype=torch.int64)
+
+
+def pack_annotations(gt_annos: List[dict], dt_annos: List[dict], device=None) -> Dict[str, torch.Tensor]:
+    """The flat arrays ``u3d_eval_match`` reads, image after image: ``det_boxes`` [D, 7], ``det_scores`` [D], ``det_labels`` int32 [D],
+    ``det_off`` int32 [I + 1], ``gt_boxes`` [G, 7], ``gt_labels`` int32 [G], ``gt_off`` int32 [I + 1].  Offsets come from the tensor
+    shapes (host metadata: no device read).  ``device`` None: the device of the first detection tensor (CPU tensors pack on the CPU)."""
+    assert len(dt_annos) == len(gt_annos)
+    db = [_box_tensor(d['bboxes_3d']) for d in dt_annos]
+    gb = [_box_tensor(g['gt_bboxes_3d']) for g in gt_annos]
+    ds = [torch.as_tensor(d['scores_3d']).reshape(-1) for d in dt_annos]
+    dl = [_labels_tensor(d['labels_3d']) for d in dt_annos]
+    gl = [_labels_tensor(g['gt_labels_3d']) for g in gt_annos]
+    device = torch.device(device if device is not None else (db[0].device if db else 'cpu'))
+    for i, (b, s, l, g, k) in enumerate(zip(db, ds, dl, gb, gl)):
+        assert b.shape[0] == s.numel() == l.numel() and g.shape[0] == k.numel(), f'image {i}: boxes, scores and labels differ in length'
+    det_off, gt_off = [0], [0]
+    for b, g in zip(db, gb):
+        det_off.append(det_off[-1] + b.shape[0])
+        gt_off.append(gt_off[-1] + g.shape[0])
+    if device.type == 'cuda':
+        from . import _lib as L
+        d_off, g_off = L.h2d_pack([(det_off, torch.int32), (gt_off, torch.int32)], device)
+    else:
+        d_off, g_off = torch.tensor(det_off, dtype=torch.int32), torch.tensor(gt_off, dtype=torch.int32)
+    return dict(det_boxes=_rows7(db, device), det_scores=_cat_to(ds, device, torch.float32), det_labels=_cat_to(dl, device, torch.int32), det_off=d_off,
+                gt_boxes=_rows7(gb, device), gt_labels=_cat_to(gl, device, torch.int32), gt_off=g_off)
+
+
+def _n_classes(label2cat) -> int:
+    return (max(label2cat) + 1 if len(label2cat) else 0) if isinstance(label2cat, dict) else len(label2cat)
+
+
+def indoor_eval_device(gt_annos: List[dict], dt_annos: List[dict], metric: Sequence[float], label2cat, logger=None):
+    """``indoor_eval`` on the device: same arguments, same result dictionary (keys in ascending class order).  The detections must be
+    device tensors (``U3DError`` otherwise: no fallback); annotations may live on the host and are uploaded asynchronously.  One launch
+    chain -- match, order, sweep -- and exactly one device-to-host read (the [T][C] AP / recall arrays with the class histograms)."""
+    from . import _lib as L
+    from . import ops
+    assert len(dt_annos) == len(gt_annos)
+    metric = [float(t) for t in metric]
+    T, C = len(metric), _n_classes(label2cat)
+    if dt_annos:
+        for d in dt_annos:
+            for t in (_box_tensor(d['bboxes_3d']), d['scores_3d'], d['labels_3d']):
+                if not (torch.is_tensor(t) and t.is_cuda):
+                    raise L.U3DError('indoor_eval_device needs the detections as CUDA (HIP) tensors: the product path has no CPU fallback')
+        p = pack_annotations(gt_annos, dt_annos)
+        dev = p['det_boxes'].device
+        res = torch.empty(2 * T * C + 2 * C, dtype=torch.int32, device=dev)        # AP | recall (float bits) | n_gt | n_det: one read
+        out, counts = res[:2 * T * C].view(torch.float32).view(2, T, C), res[2 * T * C:].view(2, C)
+        iou_max, jmax, n_gt, n_det = ops.eval_match(p['det_boxes'], p['det_labels'], p['det_off'], p['gt_boxes'], p['gt_labels'], p['gt_off'], C, counts)
+        perm = ops.eval_order(p['det_scores'], p['det_labels'], C)
+        ops.eval_sweep(iou_max, jmax, perm, n_gt, n_det, p['gt_boxes'].shape[0], metric, out)
+        host = res.cpu()
+        ap, rec = host[:2 * T * C].view(torch.float32).view(2, T, C).numpy()
+        n_gt_h, n_det_h = host[2 * T * C:].view(2, C).numpy()
+        classes = [c for c in range(C) if n_gt_h[c] > 0 or n_det_h[c] > 0]
+    else:
+        ap = rec = np.zeros((T, C), np.float32)
+        classes = []
+
+    def nanmean(v):
+        v = v[~np.isnan(v)]
+        return float(v.mean()) if v.size else float('nan')
+
+    ret = {}
+    rows = [['classes'] + [label2cat[c] for c in classes] + ['Overall']]
+    for i, thr in enumerate(metric):
+        for c in classes:
+            ret[f'{label2cat[c]}_AP_{thr:.2f}'] = float(ap[i, c])
+        ret[f'mAP_{thr:.2f}'] = nanmean(ap[i, classes].astype(np.float32))
+        for c in classes:
+            ret[f'{label2cat[c]}_rec_{thr:.2f}'] = float(rec[i, c])
+        ret[f'mAR_{thr:.2f}'] = nanmean(rec[i, classes].astype(np.float64))
+        rows.append([f'AP_{thr:.2f}'] + [f'{float(ap[i, c]):.4f}' for c in classes] + [f"{ret[f'mAP_{thr:.2f}']:.4f}"])
+        rows.append([f'AR_{thr:.2f}'] + [f'{float(rec[i, c]):.4f}' for c in classes] + [f"{ret[f'mAR_{thr:.2f}']:.4f}"])
+    if logger is not None:
+        table = '\n'.join('  '.join(f'{cell:>14}' for cell in col) for col in zip(*rows))
+        (logger.info if hasattr(logger, 'info') else print)('\n' + table)
+    return ret
+
+
+class DeviceIndoorMetric:
+    """``IndoorMetric`` without the host copies: ``process`` keeps the prediction tensors on the device and uploads the annotation's
+    boxes and labels asynchronously; ``compute_metrics`` packs each dataset's pairs and runs one launch chain per dataset."""
+
+    def __init__(self, datasets: List[str], datasets_classes: List[List[str]], iou_thr=(0.25, 0.5)):
+        self.datasets, self.datasets_classes, self.iou_thr = datasets, datasets_classes, list(iou_thr)
+        self.results: List = []
+
+    def process(self, eval_ann_info: dict, pred: dict):
+        from . import _lib as L
+        box = _box_tensor(pred['bboxes_3d'])
+        for t in (box, pred['scores_3d'], pred['labels_3d']):
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise L.U3DError('DeviceIndoorMetric needs the predictions as CUDA (HIP) tensors: the product path has no CPU fallback')
+        dev = box.device
+        gb, gl = _box_tensor(eval_ann_info['gt_bboxes_3d']), _labels_tensor(eval_ann_info['gt_labels_3d'])
+        ann = dict(eval_ann_info)
+        ann['gt_bboxes_3d'], ann['gt_labels_3d'] = _upload(gb, dev), _upload(gl, dev)
+        self.results.append((ann, dict(pred)))
+
+    def compute_metrics(self) -> Dict[str, dict]:
+        out = {}
+        for i, name in enumerate(self.datasets):
+            anns = [a for a, p in self.results if p['dataset'] == name]
+            preds = [p for a, p in self.results if p['dataset'] == name]
+            out[name] = indoor_eval_device(anns, preds, self.iou_thr, self.datasets_classes[i])
+        return out

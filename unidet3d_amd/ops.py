@@ -8,6 +8,7 @@
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -448,3 +449,70 @@ def offset_ids(ids, biases, keep_negative: bool = False) -> torch.Tensor:
     else:
         out = torch._foreach_add(ids, biases)
     return torch.cat(out) if len(out) > 1 else out[0]
+
+
+# ----------------------------------------------------------------------------------------
+# detection evaluation of a whole validation pass (csrc/evalmap.hip)
+# ----------------------------------------------------------------------------------------
+EVAL_MAX_CLASSES, EVAL_MAX_THR = 1024, 8    # include/u3d.h U3D_EVAL_MAX_CLASSES / U3D_EVAL_MAX_THR
+
+
+def _eval_check(name, t, dtype, cols=None):
+    if not t.is_cuda:
+        raise L.U3DError('u3d kernels need CUDA (HIP) tensors: the product path has no CPU fallback')
+    if t.dtype != dtype or not t.is_contiguous() or (cols is not None and (t.dim() != 2 or t.shape[1] != cols)):
+        raise L.U3DError(f'eval: {name} must be a contiguous {dtype} tensor' + (f' [n, {cols}]' if cols else ''))
+
+
+def eval_match(det_boxes, det_labels, det_off, gt_boxes, gt_labels, gt_off, n_classes: int, counts: Optional[torch.Tensor] = None):
+    """Best same-class ground truth of every detection of a packed validation pass (``u3d_eval_match``): ``(iou_max float32 [D],
+    jmax int32 [D], n_gt int32 [C], n_det int32 [C])``.  ``counts``: an int32 [2, C] buffer the two histograms are written to."""
+    for name, t, dt, cols in (('det_boxes', det_boxes, torch.float32, 7), ('det_labels', det_labels, torch.int32, None),
+                              ('det_off', det_off, torch.int32, None), ('gt_boxes', gt_boxes, torch.float32, 7),
+                              ('gt_labels', gt_labels, torch.int32, None), ('gt_off', gt_off, torch.int32, None)):
+        _eval_check(name, t, dt, cols)
+    D, G, I, C = det_boxes.shape[0], gt_boxes.shape[0], det_off.numel() - 1, int(n_classes)
+    if det_labels.numel() != D or gt_labels.numel() != G or gt_off.numel() != I + 1 or I < 0:
+        raise L.U3DError('eval_match: labels / offsets do not fit the boxes')
+    dev = det_boxes.device
+    iou_max = torch.empty(D, dtype=torch.float32, device=dev)
+    jmax = torch.empty(D, dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.empty((2, C), dtype=torch.int32, device=dev)
+    _eval_check('counts', counts, torch.int32, C)
+    L.call('u3d_eval_match', L.ptr(det_boxes), L.ptr(det_labels), L.ptr(det_off), L.ptr(gt_boxes), L.ptr(gt_labels), L.ptr(gt_off), D, G, I, C,
+           L.ptr(iou_max), L.ptr(jmax), L.ptr(counts[0]), L.ptr(counts[1]), None, L.stream())
+    return iou_max, jmax, counts[0], counts[1]
+
+
+def eval_order(det_scores: torch.Tensor, det_labels: torch.Tensor, n_classes: int) -> torch.Tensor:
+    """Evaluation order of the detections (``u3d_eval_order``): class ascending, score descending, ties by packed index.  int32 [D]."""
+    _eval_check('det_scores', det_scores, torch.float32)
+    _eval_check('det_labels', det_labels, torch.int32)
+    D = det_scores.numel()
+    perm = torch.empty(D, dtype=torch.int32, device=det_scores.device)
+    ws = L.scratch(L.lib().u3d_eval_order_ws_bytes(D), det_scores.device)
+    L.call('u3d_eval_order', L.ptr(det_scores), L.ptr(det_labels), D, int(n_classes), L.ptr(perm), L.ptr(ws), L.stream())
+    return perm
+
+
+def eval_sweep(iou_max, jmax, perm, n_gt, n_det, n_gts: int, thresholds, out: Optional[torch.Tensor] = None, with_flags: bool = False):
+    """True-positive sweep and AP / last recall of every (threshold, class) (``u3d_eval_sweep``): ``(ap, rec)`` float32 [T, C];
+    ``out``: a float32 [2, T, C] buffer they are written to.  ``with_flags``: also ``(tp_flag uint8 [T, D], tp_cum int32 [T, D])`` by
+    sorted rank (zero where the kernel writes nothing)."""
+    thresholds = [float(t) for t in thresholds]
+    D, G, C, T = iou_max.numel(), int(n_gts), n_gt.numel(), len(thresholds)
+    for name, t, dt in (('iou_max', iou_max, torch.float32), ('jmax', jmax, torch.int32), ('perm', perm, torch.int32),
+                        ('n_gt', n_gt, torch.int32), ('n_det', n_det, torch.int32)):
+        _eval_check(name, t, dt)
+    dev = iou_max.device
+    if out is None:
+        out = torch.empty((2, T, C), dtype=torch.float32, device=dev)
+    _eval_check('out', out, torch.float32)
+    flag = torch.zeros((T, D), dtype=torch.uint8, device=dev) if with_flags else None
+    cum = torch.zeros((T, D), dtype=torch.int32, device=dev) if with_flags else None
+    ws = L.scratch(L.lib().u3d_eval_sweep_ws_bytes(D, G, T), dev)
+    thr = (ctypes.c_float * max(T, 1))(*thresholds)
+    L.call('u3d_eval_sweep', L.ptr(iou_max), L.ptr(jmax), L.ptr(perm), L.ptr(n_gt), L.ptr(n_det), thr, D, G, C, T, L.ptr(out[0]), L.ptr(out[1]),
+           L.ptr(flag), L.ptr(cum), L.ptr(ws), L.stream())
+    return (out[0], out[1], flag, cum) if with_flags else (out[0], out[1])
