@@ -562,17 +562,36 @@ int u3d_trim_boxes_batched(const float* points, int64_t pt_ld, const int32_t* sp
  *  P = qm_off[B]); scene_meta int32 [B][4] = {classes + 1 of the scene's dataset (the last one is "no object"), top-k,
  *  1 if the scene's boxes carry a heading, offset of the scene's class-column list in cidx}; scene_w float [B] dataset weight;
  *  cidx int32 (nullable): concatenated class-column lists (logit of class c of scene b = cls[..][cidx[off_b + c]]); NULL = the
- *  scene's classes are columns 0 .. C1-1.  max_gt = max g_b (<= 64); min_query_slack = min over scenes with g_b > 0 of
- *  n_b - (topk_b + 1) (must be >= 0, as torch.topk requires in the reference).
+ *  scene's classes are columns 0 .. C1-1.  max_gt = max g_b, any value: the matched set of a (layer, query) is kept in
+ *  ceil(max_gt / 64) 64-bit words, and a batch with max_gt > 64 computes its cost matrix with one thread per (layer, query, GT)
+ *  entry instead of one per (layer, query) (one more launch).  With max_gt <= 64 the launches and the arithmetic are what they
+ *  were with the one-word mask, bit for bit.  What bounds a scene is 32-bit indexing: n_tot, G, L * G and
+ *  min(P, n_tot * max_gt) -- an upper bound of every scene's n_b * g_b -- must fit an int; otherwise U3D_EUNSUPPORTED before
+ *  anything is launched.  min_query_slack = min over scenes with g_b > 0 of n_b - (topk_b + 1) (must be >= 0, as torch.topk
+ *  requires in the reference).
  *  loss [1] = sum over layers of lw_cls * mean_b(w_b CE_b) + lw_box * mean over scenes with matches (w_b DIoU_b);
  *  dcls [L][n_tot][CU] / dbox [L][n_tot][BD] receive d loss / d cls (zero in columns outside the scene's class list), d loss / d box.
- *  ws: u3d_criterion_ws_bytes. */
+ *  ws: u3d_criterion_ws_bytes_gt for the same max_gt (u3d_criterion_ws_bytes: the size for max_gt <= 64; the _gt query is an
+ *  ADDED entry point and no argument list moved, so U3D_ABI_VERSION is unchanged).  NOTE for callers of the C interface: with
+ *  max_gt > 64 the entry point used to refuse; it now runs and needs the larger workspace, and it cannot see how ws was sized -- a
+ *  workspace sized by the five-argument query and used with max_gt > 64 is overrun.  Size ws with the _gt query whenever max_gt can
+ *  exceed 64.  The five-argument query itself returns L * n_tot * 8 bytes (rounded up to 64) more than it did for the same
+ *  arguments: the block of the log-sum-exp pre-pass is always part of the layout.
+ *  Errors: U3D_EINVAL with a message for max_gt outside [0, G]; U3D_EUNSUPPORTED with a message for L > 65535 and for the 32-bit
+ *  bound above -- that message names the bound and the batch totals, not the scene: the scene sizes are device arrays here (the
+ *  Python host, which knows them, names the scene).
+ *  Environment: U3D_CRITERION_COST=query | pair (read once per process) forces the per-query or the per-entry cost kernel
+ *  whatever max_gt is, for A/B timing (tools/criterion_time.py); both evaluate the same expression per entry.
+ *  Unset: per-entry iff max_gt > 64.
+ *  Layout: cost [L][P], logz [L][n_tot], kth [L][G], match words uint64 [L][n_tot][W], W = max(1, ceil(max_gt / 64)) (GT j of the
+ *  query's scene = bit j & 63 of word j >> 6), statistics; every block starts on a multiple of 64 bytes. */
 int u3d_criterion_packed(const float* cls, const float* box, const int32_t* cu, const int32_t* gt_off, const int64_t* gt_labels,
                          const float* gt_boxes, const uint8_t* qmask, const int64_t* qm_off, const int32_t* scene_meta,
                          const float* scene_w, const int32_t* cidx, int L, int B, int64_t n_tot, int CU, int BD, int64_t G, int64_t P,
                          int max_gt, int min_query_slack, float w_cls, float w_box, float non_obj_w, float lw_cls, float lw_box,
                          float* loss, float* dcls, float* dbox, void* ws, u3d_stream_t stream);
 int64_t u3d_criterion_ws_bytes(int L, int B, int64_t n_tot, int64_t G, int64_t P);
+int64_t u3d_criterion_ws_bytes_gt(int L, int B, int64_t n_tot, int64_t G, int64_t P, int max_gt);
 /* box decode of a yaw-free head in one pass each way: PredBBox's exp of the six face distances + _bbox_pred_to_bbox
  * (unidet3d/encoder.py:99-111, :241-271): raw [M][8] (Linear output), centers [M][3] -> box [M][6] (centre, size);
  * backward: draw [M][8] from dbox [M][6] (the angle columns receive 0). */

@@ -104,6 +104,7 @@ PROTOTYPES = {
     'u3d_box_decode7_fwd': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     'u3d_box_decode7_bwd': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     'u3d_criterion_ws_bytes': (_i64, [_i32, _i32, _i64, _i64, _i64]),
+    'u3d_criterion_ws_bytes_gt': (_i64, [_i32, _i32, _i64, _i64, _i64, _i32]),
     'u3d_gemm_nt': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _vp]),
     'u3d_linear_act': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _f64, _vp]),
     'u3d_linear_dact': (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _f64, _vp]),

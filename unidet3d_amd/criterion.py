@@ -221,7 +221,8 @@ class UniMatcher:
 
 
 class _FusedCriterionFn(torch.autograd.Function):
-    """include/u3d.h u3d_criterion_packed: the loss AND its gradients w.r.t. the stacked head outputs in five launches."""
+    """include/u3d.h u3d_criterion_packed: the loss AND its gradients w.r.t. the stacked head outputs in five launches (six when a
+    scene has more than 64 GTs)."""
 
     @staticmethod
     def forward(ctx, cls, box, g, consts):
@@ -231,7 +232,7 @@ class _FusedCriterionFn(torch.autograd.Function):
         dev = cls.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dcls, dbox = torch.empty_like(cls), torch.empty_like(box)
-        ws = L.scratch(L.lib().u3d_criterion_ws_bytes(Ln, g['B'], n_tot, g['G'], g['P']), dev)
+        ws = L.scratch(L.lib().u3d_criterion_ws_bytes_gt(Ln, g['B'], n_tot, g['G'], g['P'], g['max_gt']), dev)
         L.call('u3d_criterion_packed', L.ptr(cls), L.ptr(box), L.ptr(g['cu']), L.ptr(g['gt_off']), L.ptr(g['labels']), L.ptr(g['boxes']),
                L.ptr(g['qmask']), L.ptr(g['qm_off']), L.ptr(g['meta']), L.ptr(g['scene_w']), L.ptr(g['cidx']), Ln, g['B'], n_tot, CU, BD,
                g['G'], g['P'], g['max_gt'], g['slack'], *consts, L.ptr(loss), L.ptr(dcls), L.ptr(dbox), L.ptr(ws), L.stream())
@@ -406,11 +407,14 @@ class UniDet3DCriterion:
     # ---- fused device path (csrc/criterion.hip) ---------------------------------------------------
     def _flat_gt(self, insts, sizes, device, topks, weights, c1s, yaw, cidx, bd):
         """Ragged GT and per-scene dataset constants of the batch as flat device arrays for u3d_criterion_packed; None when the
-        kernel's limits do not hold (> 64 GTs in a scene, or a scene with GT but fewer than topk + 1 queries -- left to the
-        per-scene path, which raises like the reference)."""
+        kernel's one condition does not hold (a scene with GT but fewer than topk + 1 queries -- left to the per-scene path, which
+        raises like the reference).  The number of GTs of a scene is not limited: the kernel keeps ceil(max_gt / 64) mask words."""
         gs = [len(i) for i in insts]
-        if max(gs, default=0) > 64 or any(g and n < k + 1 for g, n, k in zip(gs, sizes, topks)):
+        if any(g and n < k + 1 for g, n, k in zip(gs, sizes, topks)):
             return None
+        for b, (n, g) in enumerate(zip(sizes, gs)):
+            if n * g > 0x7fffffff:
+                raise ValueError(f'criterion: scene {b} has {n} queries x {g} ground-truth boxes, beyond the 32-bit index range of the kernel')
         cu, go, qo = [0], [0], [0]
         for n, g in zip(sizes, gs):
             cu.append(cu[-1] + n); go.append(go[-1] + g); qo.append(qo[-1] + n * g)

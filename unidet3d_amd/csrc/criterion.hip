@@ -1,9 +1,10 @@
-// R12 on the device in five launches: matcher + classification / box losses of all decoder layers and scenes of a batch,
-// forward AND gradients (the reference: unidet3d/criterion.py:44-178 UniDet3DCriterion.get_layer_loss / __call__, :200-320 the
-// cost classes and UniMatcher, unidet3d/axis_aligned_iou_loss.py:14-53 axis_aligned_diou_loss, unidet3d/rotated_iou_loss.py:14-82
-// diff_diou_rotated_3d / rotated_diou_3d_loss over mmcv's rectangle intersection).  Round 3: MIXED batches of the joint config --
-// every scene carries its own class-column list (dataset), top-k, dataset weight and box parametrisation (6-dof axis-aligned or
-// 7-dof with a heading: the rotated DIoU for both the matcher cost and the loss, with analytic gradients).
+// R12 on the device in five launches (six for a batch with a scene of more than 64 GTs): matcher + classification / box losses
+// of all decoder layers and scenes of a batch, forward AND gradients.  The reference: unidet3d/criterion.py:44-178
+// UniDet3DCriterion.get_layer_loss / __call__, :200-320 the cost classes and UniMatcher, unidet3d/axis_aligned_iou_loss.py:14-53
+// axis_aligned_diou_loss, unidet3d/rotated_iou_loss.py:14-82 diff_diou_rotated_3d / rotated_diou_3d_loss over mmcv's rectangle
+// intersection.  Round 3: MIXED batches of the joint config -- every scene carries its own class-column list (dataset), top-k,
+// dataset weight and box parametrisation (6-dof axis-aligned or 7-dof with a heading: the rotated DIoU for both the matcher cost
+// and the loss, with analytic gradients).
 // The torch-op formulation of the same arithmetic costs ~380 launches of [layers, scenes, n, g] tensor ops per step for one
 // dataset and a Python loop of ~70 launches per (layer, scene) for a mixed batch; here
 //   crit_cost_k   one thread per (layer, query): log-sum-exp of the scene's class columns, cost[q][j] of every GT of the query's
@@ -11,9 +12,13 @@
 //                 1 - IoU + centre term of GT 0 (the reference's `[:, 0]` quirk of the axis-aligned form) or 1 - rotated DIoU;
 //   crit_kth_k    one wave per (layer, scene, GT): the (topk+1)-th smallest cost of the column by k rounds of lexicographic
 //                 (value, index) minimum extraction -- the threshold of `cost < values` (:316-319);
-//   crit_stats_k  one workgroup per (layer, scene): matched set (a 64-bit GT mask per query), class target = label of the LAST
-//                 matched GT (:98-99 index assignment), weighted cross-entropy sums and the DIoU sum over matched pairs, reduced in a
-//                 fixed order (no atomics);
+//   crit_lse_k + crit_cost_pair_k   the same cost matrix for a batch with a crowded scene (max_gt > 64), where one thread per
+//                 query would loop over hundreds of GTs on a grid of a few hundred waves: a pre-pass per (layer, query) stores the
+//                 row maximum, the exponential sum and logz, then one thread per (layer, query, GT) entry evaluates the identical
+//                 expression (same prob, same box cost, same GT-0 term, same 1e8 sentinel);
+//   crit_stats_k  one workgroup per (layer, scene): matched set (W = ceil(max_gt / 64) 64-bit words per query, GT j = bit j & 63
+//                 of word j >> 6), class target = label of the LAST matched GT (:98-99 index assignment), weighted cross-entropy
+//                 sums and the DIoU sum over matched pairs, reduced in a fixed order (no atomics);
 //   crit_final_k  one thread: the scalar loss (means over scenes / scenes with matches, sum over layers) and the per-layer scale
 //                 factors of the gradients;
 //   crit_grad_k   one thread per (layer, query): d loss / d logits (softmax - one-hot, weighted; zero in the columns of other
@@ -22,6 +27,8 @@
 //                 is run on dual numbers (value + 7 tangents), i.e. forward-mode differentiation of exactly the branch taken --
 //                 what autograd does to the reference's tensor program.
 #include <math.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include "u3d_common.h"
 
@@ -40,15 +47,17 @@ struct CritParams {
     const float* scene_w;      // [B] dataset weight
     const int32_t* cidx;       // class columns of every scene in the CU-wide logit rows (concatenated); nullptr = columns 0..C1-1
     int L, B, CU, BD;
+    int W;                     // 64-bit words of a query's matched-GT set: ceil(max_gt / 64), at least 1
     int64_t n_tot, G, P;       // P = sum n_b g_b
     float w_cls, w_box, non_obj_w, lw_cls, lw_box;
     // workspace
     float* cost;               // [L][P]
     float* logz;               // [L][n_tot]
     float* kth;                // [L][G]
-    unsigned long long* mm;    // [L][n_tot] matched-GT bit mask
+    unsigned long long* mm;    // [L][n_tot][W] matched-GT bit mask
     float* stats;              // [L][B][4]: sum w, sum w nll, matched pairs, sum diou
     float* scale;              // [L][2]: (unused, number of scenes with matches) -- written by crit_final_k
+    float* mxse;               // [L][n_tot][2]: (row maximum, exponential sum) of crit_lse_k; only with max_gt > 64
     float* loss;               // [1]
     float* dcls;
     float* dbox;
@@ -322,6 +331,61 @@ __global__ __launch_bounds__(256) void crit_cost_k(CritParams p) {
     }
 }
 
+// ---- the cost matrix of a batch with a crowded scene (max_gt > 64): the log-sum-exp pre-pass, then one thread per entry ----
+__global__ __launch_bounds__(256) void crit_lse_k(CritParams p) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)p.L * p.n_tot) return;
+    const int q = (int)(idx % p.n_tot);
+    const int b = scene_of(p.cu, p.B, q);
+    const int C1 = p.meta[b * 4];
+    const float* x = p.cls + idx * p.CU;
+    float mx = -INFINITY;
+    for (int c = 0; c < C1; ++c) mx = fmaxf(mx, x[col_of(p, b, c)]);
+    float se = 0.f;
+    for (int c = 0; c < C1; ++c) se += expf(x[col_of(p, b, c)] - mx);
+    p.logz[idx] = mx + logf(se);
+    p.mxse[idx * 2] = mx;
+    p.mxse[idx * 2 + 1] = se;
+}
+
+// One thread per (layer, query, GT) entry of `cost`, entries in storage order ([L][P]; scene b's [n_b][g_b] block at qm_off[b]), so
+// the 64 lanes of a wave hold consecutive GTs of one query (or of neighbouring queries): coalesced stores and GT box loads, the query's
+// own row is a broadcast.  Blocks of one wave: a rotated pair is a long, divergent, register-heavy evaluation with no cooperation
+// between threads, so the wave is the natural scheduling unit and a crowded scene's few thousand waves spread over every CU.
+__global__ __launch_bounds__(64) void crit_cost_pair_k(CritParams p) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.P) return;
+    const int l = blockIdx.y;
+    int b = 0;
+    {
+        int hi = p.B;                          // qm_off[b] <= e < qm_off[hi]; scenes without GT are empty ranges and are passed over
+        while (hi - b > 1) {
+            const int mid = (b + hi) >> 1;
+            if (p.qm_off[mid] <= e) b = mid; else hi = mid;
+        }
+    }
+    const int g0 = p.gt_off[b], g = p.gt_off[b + 1] - g0;
+    const int n = p.cu[b + 1] - p.cu[b];
+    const int64_t r = e - p.qm_off[b];
+    if (g <= 0 || r >= (int64_t)n * g) return;       // P and qm_off disagree: nothing to index
+    const int ql = (int)(r / g), j = (int)(r % g);
+    float c = 1e8f;
+    if (p.qmask[p.qm_off[b] + (int64_t)j * n + ql]) {
+        const int yaw = p.meta[b * 4 + 2];
+        const int64_t idx = (int64_t)l * p.n_tot + p.cu[b] + ql;
+        const float* x = p.cls + idx * p.CU;
+        const float mx = p.mxse[idx * 2], se = p.mxse[idx * 2 + 1];
+        const float* pbox = p.box + idx * p.BD;
+        const Box6 pb = corners(pbox);
+        const float rc0 = yaw ? 0.f : centre_term(pb, corners(p.gt_boxes + (int64_t)g0 * p.BD));       // the `[:, 0]` term, as in crit_cost_k
+        const float prob = expf(x[col_of(p, b, (int)p.gt_labels[g0 + j])] - mx) / se;
+        const float* gb = p.gt_boxes + (int64_t)(g0 + j) * p.BD;
+        const float box_cost = yaw ? rot_cost(pbox, gb) : (1.f - iou3(pb, corners(gb))) + rc0;
+        c = -prob * p.w_cls + box_cost * p.w_box;
+    }
+    p.cost[(int64_t)l * p.P + e] = c;
+}
+
 // one wave per (layer, GT): kth = (topk+1)-th smallest cost of the GT's column
 __global__ __launch_bounds__(64) void crit_kth_k(CritParams p) {
     const int64_t wid = blockIdx.x;
@@ -363,16 +427,17 @@ __global__ __launch_bounds__(256) void crit_stats_k(CritParams p) {
     float sw = 0.f, swn = 0.f, cnt = 0.f, sd = 0.f;
     for (int ql = threadIdx.x; ql < n; ql += 256) {
         const int64_t idx = (int64_t)l * p.n_tot + q0 + ql;
-        unsigned long long m = 0ull;
         int last = -1;
-        if (g) {
-            const float* crow = p.cost + (int64_t)l * p.P + p.qm_off[b] + (int64_t)ql * g;
-            const float* kth = p.kth + (int64_t)l * p.G + g0;
-            const float* pbox = p.box + idx * p.BD;
-            const Box6 pb = corners(pbox);
-            for (int j = 0; j < g; ++j)
+        const float* crow = p.cost + (int64_t)l * p.P + p.qm_off[b] + (int64_t)ql * g;
+        const float* kth = p.kth + (int64_t)l * p.G + g0;
+        const float* pbox = p.box + idx * p.BD;
+        const Box6 pb = corners(pbox);
+        for (int w = 0; w < p.W; ++w) {              // GTs in ascending order, 64 to a word; a word past the scene's GTs is written as 0
+            unsigned long long m = 0ull;
+            const int j1 = min(g, (w + 1) * 64);
+            for (int j = w * 64; j < j1; ++j)
                 if (crow[j] < kth[j]) {
-                    m |= 1ull << j;
+                    m |= 1ull << (j & 63);
                     last = j;
                     const float* gb = p.gt_boxes + (int64_t)(g0 + j) * p.BD;
                     if (yaw) {
@@ -383,8 +448,8 @@ __global__ __launch_bounds__(256) void crit_stats_k(CritParams p) {
                     }
                     cnt += 1.f;
                 }
+            p.mm[idx * p.W + w] = m;
         }
-        p.mm[idx] = m;
         const int target = last >= 0 ? (int)p.gt_labels[g0 + last] : n_cls;
         const float w = target == n_cls ? p.non_obj_w : 1.f;
         sw += w;
@@ -422,6 +487,11 @@ __global__ void crit_final_k(CritParams p) {
 __device__ __forceinline__ float pick_gt(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }     // d max(a, b) / d a
 __device__ __forceinline__ float pick_lt(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }     // d min(a, b) / d a
 
+// MULTI = false: one mask word per query (max_gt <= 64) -- the statements of the kernel as it was before the multi-word masks, so
+// that the compiler sees the same program and loss / dcls / dbox of such batches keep their bits (the rotated branch is sensitive
+// to how the surrounding code is shaped: DESIGN.md 4.8).  MULTI = true: W words, scanned from the top for the last matched GT and
+// walked in ascending order for the box gradient.
+template <bool MULTI>
 __global__ __launch_bounds__(256) void crit_grad_k(CritParams p) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)p.L * p.n_tot) return;
@@ -431,9 +501,17 @@ __global__ __launch_bounds__(256) void crit_grad_k(CritParams p) {
     const int C1 = p.meta[b * 4], n_cls = C1 - 1, yaw = p.meta[b * 4 + 2];
     const float ds_w = p.scene_w[b];
     const float* st = p.stats + ((int64_t)l * p.B + b) * 4;
-    const unsigned long long m = p.mm[idx];
+    const unsigned long long* mq = p.mm + idx * (MULTI ? p.W : 1);
+    const unsigned long long m = MULTI ? 0ull : mq[0];
     // ---- classification: lw_cls * ds_w / B * w_q / sum_w * (softmax - onehot(target)); zero in the other datasets' columns ----
-    const int last = m ? 63 - __clzll(m) : -1;
+    int last = m ? 63 - __clzll(m) : -1;
+    if constexpr (MULTI) {                          // the highest matched GT: the words from the top
+        for (int w = p.W - 1; w >= 0; --w) {
+            const unsigned long long mw = mq[w];
+            if (mw) { last = w * 64 + 63 - __clzll(mw); break; }
+        }
+    }
+    const bool any = MULTI ? last >= 0 : m != 0ull;
     const int target = last >= 0 ? (int)p.gt_labels[g0 + last] : n_cls;
     const float w = target == n_cls ? p.non_obj_w : 1.f;
     const float kc = p.lw_cls * ds_w / p.B * w / st[0];
@@ -450,19 +528,24 @@ __global__ __launch_bounds__(256) void crit_grad_k(CritParams p) {
     float* db = p.dbox + idx * p.BD;
     if (yaw) {
         float gacc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (m) {
+        if (any) {
             const float kb = p.lw_box * ds_w / (fmaxf(p.scale[l * 2 + 1], 1.f) * st[2]);
             Dual pd[7];
 #pragma unroll
             for (int i = 0; i < 7; ++i) pd[i] = dual_var(p.box[idx * 7 + i], i);
-            for (unsigned long long mmask = m; mmask; mmask &= mmask - 1) {
-                const int j = __ffsll((long long)mmask) - 1;
+            auto add_gt = [&](int j) {
                 float t[7];
 #pragma unroll
                 for (int i = 0; i < 7; ++i) t[i] = p.gt_boxes[(int64_t)(g0 + j) * 7 + i];
                 const Dual r = rotated_diou_loss<Dual>(pd, t);
 #pragma unroll
                 for (int i = 0; i < 7; ++i) gacc[i] += r.d[i];
+            };
+            if constexpr (MULTI) {                   // ascending GT order: words in ascending order, bits from the lowest
+                for (int w = 0; w < p.W; ++w)
+                    for (unsigned long long mmask = mq[w]; mmask; mmask &= mmask - 1) add_gt(w * 64 + __ffsll((long long)mmask) - 1);
+            } else {
+                for (unsigned long long mmask = m; mmask; mmask &= mmask - 1) add_gt(__ffsll((long long)mmask) - 1);
             }
 #pragma unroll
             for (int i = 0; i < 7; ++i) gacc[i] *= kb;
@@ -472,11 +555,12 @@ __global__ __launch_bounds__(256) void crit_grad_k(CritParams p) {
         return;
     }
     float gc[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f};
-    if (m) {
+    if (any) {
         const float kb = p.lw_box * ds_w / (fmaxf(p.scale[l * 2 + 1], 1.f) * st[2]);
         const Box6 pb = corners(p.box + idx * p.BD);
-        for (unsigned long long mmask = m; mmask; mmask &= mmask - 1) {
-            const int j = __ffsll((long long)mmask) - 1;
+        for (int w = 0; w < (MULTI ? p.W : 1); ++w)
+        for (unsigned long long mmask = MULTI ? mq[w] : m; mmask; mmask &= mmask - 1) {
+            const int j = (MULTI ? w * 64 : 0) + __ffsll((long long)mmask) - 1;
             const Box6 tb = corners(p.gt_boxes + (int64_t)(g0 + j) * p.BD);
             float wh[3], dd[3], lo[3], hi[3];
             float inter = 1.f, vp = 1.f, vt = 1.f, r2 = 0.f, c2 = 0.f;
@@ -650,9 +734,27 @@ int u3d_box_decode7_bwd(const float* raw, const float* dbox, const uint8_t* yaw_
 
 static inline int64_t al64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 
-int64_t u3d_criterion_ws_bytes(int L, int B, int64_t n_tot, int64_t G, int64_t P) {
-    return al64((int64_t)L * P * 4) + al64((int64_t)L * n_tot * 4) + al64((int64_t)L * G * 4) + al64((int64_t)L * n_tot * 8) +
-           al64((int64_t)L * B * 16) + al64((int64_t)L * 8) + 256;
+static inline int crit_words(int max_gt) { return max_gt > 64 ? (max_gt + 63) / 64 : 1; }
+
+// 0 = by the batch (pair-parallel cost kernel when max_gt > 64), 1 = always the per-query kernel, 2 = always the pair kernel.
+// Host state for A/B timing (tools/criterion_time.py); both kernels evaluate the same expression per entry.
+static int crit_cost_mode() {
+    static const int mode = [] {
+        const char* e = getenv("U3D_CRITERION_COST");
+        return !e ? 0 : (!strcmp(e, "query") ? 1 : (!strcmp(e, "pair") ? 2 : 0));
+    }();
+    return mode;
+}
+
+int64_t u3d_criterion_ws_bytes_gt(int L, int B, int64_t n_tot, int64_t G, int64_t P, int max_gt) {
+    if (L <= 0 || B <= 0 || n_tot < 0 || G < 0 || P < 0 || max_gt < 0) return U3D_EINVAL;
+    return al64((int64_t)L * P * 4) + al64((int64_t)L * n_tot * 4) + al64((int64_t)L * G * 4) +
+           al64((int64_t)L * n_tot * 8 * crit_words(max_gt)) + al64((int64_t)L * B * 16) + al64((int64_t)L * 8) +
+           al64((int64_t)L * n_tot * 8) + 256;
+}
+
+int64_t u3d_criterion_ws_bytes(int L, int B, int64_t n_tot, int64_t G, int64_t P) {      // max_gt <= 64: one word per query
+    return u3d_criterion_ws_bytes_gt(L, B, n_tot, G, P, 64);
 }
 
 int u3d_criterion_packed(const float* cls, const float* box, const int32_t* cu, const int32_t* gt_off, const int64_t* gt_labels,
@@ -664,7 +766,20 @@ int u3d_criterion_packed(const float* cls, const float* box, const int32_t* cu, 
         n_tot <= 0 || CU < 2 || (BD != 6 && BD != 7) || G < 0 || P < 0)
         return U3D_EINVAL;
     if (G > 0 && (!gt_labels || !gt_boxes || !qmask)) return U3D_EINVAL;
-    if (max_gt > 64) { set_error("criterion: %d ground-truth boxes in one scene exceed the 64-bit match mask", max_gt); return U3D_EUNSUPPORTED; }
+    if (max_gt < 0 || max_gt > G) { set_error("criterion: max_gt %d is not in [0, G = %lld]", max_gt, (long long)G); return U3D_EINVAL; }
+    if (L > 65535) { set_error("criterion: %d layers exceed the 65535 rows of the launch grid", L); return U3D_EUNSUPPORTED; }
+    // What bounds a scene is 32-bit indexing: queries, GTs and the (query, GT) entries of one scene are counted in int.  The scene
+    // sizes themselves live in device arrays; n_tot * max_gt and P bound every scene's n_b * g_b from above.
+    {
+        const int64_t lim = 0x7fffffff;
+        const int64_t pairs = P < n_tot * (int64_t)max_gt ? P : n_tot * (int64_t)max_gt;
+        if (n_tot > lim || G > lim || pairs > lim || (int64_t)L * G > lim) {
+            set_error("criterion: the scene with the most ground truth (max_gt %d of G %lld boxes, n_tot %lld queries, P %lld entries, "
+                      "L %d) may hold up to %lld (query, GT) entries: beyond the 32-bit index range of the kernels",
+                      max_gt, (long long)G, (long long)n_tot, (long long)P, L, (long long)pairs);
+            return U3D_EUNSUPPORTED;
+        }
+    }
     if (G > 0 && min_query_slack < 0) {        // torch.topk(cost, topk + 1, dim=0) of the reference raises here as well
         set_error("criterion: a scene with ground truth has fewer queries than its topk + 1 (slack %d)", min_query_slack);
         return U3D_EINVAL;
@@ -674,21 +789,30 @@ int u3d_criterion_packed(const float* cls, const float* box, const int32_t* cu, 
     p.cls = cls; p.box = box; p.cu = cu; p.gt_off = gt_off; p.gt_labels = gt_labels; p.gt_boxes = gt_boxes; p.qmask = qmask; p.qm_off = qm_off;
     p.meta = scene_meta; p.scene_w = scene_w; p.cidx = cidx;
     p.L = L; p.B = B; p.CU = CU; p.BD = BD; p.n_tot = n_tot; p.G = G; p.P = P;
+    p.W = crit_words(max_gt);
     p.w_cls = w_cls; p.w_box = w_box; p.non_obj_w = non_obj_w; p.lw_cls = lw_cls; p.lw_box = lw_box;
     char* w = (char*)ws;
     p.cost = (float*)w; w += al64((int64_t)L * P * 4);
     p.logz = (float*)w; w += al64((int64_t)L * n_tot * 4);
     p.kth = (float*)w; w += al64((int64_t)L * G * 4);
-    p.mm = (unsigned long long*)w; w += al64((int64_t)L * n_tot * 8);
+    p.mm = (unsigned long long*)w; w += al64((int64_t)L * n_tot * 8 * p.W);
     p.stats = (float*)w; w += al64((int64_t)L * B * 16);
-    p.scale = (float*)w;
+    p.scale = (float*)w; w += al64((int64_t)L * 8);
+    p.mxse = (float*)w;
     p.loss = loss; p.dcls = dcls; p.dbox = dbox;
     const unsigned gq = (unsigned)ceil_div((int64_t)L * n_tot, 256);
-    hipLaunchKernelGGL(crit_cost_k, dim3(gq), dim3(256), 0, s, p);
+    const int mode = crit_cost_mode();
+    if (mode == 2 || (mode == 0 && max_gt > 64)) {
+        hipLaunchKernelGGL(crit_lse_k, dim3(gq), dim3(256), 0, s, p);
+        if (P > 0) hipLaunchKernelGGL(crit_cost_pair_k, dim3((unsigned)ceil_div(P, 64), (unsigned)L), dim3(64), 0, s, p);
+    } else {
+        hipLaunchKernelGGL(crit_cost_k, dim3(gq), dim3(256), 0, s, p);
+    }
     if (G > 0) hipLaunchKernelGGL(crit_kth_k, dim3((unsigned)((int64_t)L * G)), dim3(64), 0, s, p);
     hipLaunchKernelGGL(crit_stats_k, dim3((unsigned)(L * B)), dim3(256), 0, s, p);
     hipLaunchKernelGGL(crit_final_k, dim3(1), dim3(1), 0, s, p);
-    hipLaunchKernelGGL(crit_grad_k, dim3(gq), dim3(256), 0, s, p);
+    if (p.W > 1) hipLaunchKernelGGL(crit_grad_k<true>, dim3(gq), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(crit_grad_k<false>, dim3(gq), dim3(256), 0, s, p);
     return check_launch("criterion_packed");
 }
 
