@@ -214,3 +214,36 @@ def test_gravity_center_forms_agree_bit_for_bit():
     part = b[3:9]
     assert torch.equal(part.gravity_center, want[3:9]) and torch.equal(part.gt_rows, rows[3:9])
     assert b[torch.tensor([1, 5])].gt_rows is None and torch.equal(b[torch.tensor([1, 5])].gravity_center, want[[1, 5]])
+
+
+def test_dense_padding_helpers_pad_with_exact_zeros_and_copy_nothing_that_is_aligned():
+    """dense._transposed / dense._pad_cols, shared by both data flows of the decoder's dense ops: the [K, N] weight copy and the
+    columns of dy are zero-padded to the kernel's granule for the tiny heads (N = 19, 8); aligned operands are returned as they are."""
+    import pytest
+    from unidet3d_amd import dense
+    g = torch.Generator().manual_seed(0)
+    K = 32
+    for N in (8, 19, 20):
+        weight = torch.randn(N, K, generator=g)
+        for q in (4, 8, 16, 32):
+            Np = (N + q - 1) // q * q
+            given = weight.t().contiguous()                # stands for the copy transposed_weights() made
+            planes = object()
+            if N % q == 0:
+                wt, pl = dense._transposed(weight, q, given, planes)
+                assert wt is given and pl is planes
+            else:
+                for have in (None, given):
+                    wt, pl = dense._transposed(weight, q, have, planes if have is not None else None)
+                    assert pl is None and wt.shape == (K, Np) and wt.dtype == torch.float32 and wt.is_contiguous()
+                    assert torch.equal(wt[:, :N], weight.t()) and not wt[:, N:].any()
+            for M in (0, 1, 5):
+                for dtype in (torch.float32, torch.bfloat16):
+                    dy = torch.randn(M, N, generator=g).to(dtype)
+                    dyp = dense._pad_cols(dy, q)
+                    if N % q == 0:
+                        assert dyp is dy
+                    else:
+                        assert dyp.shape == (M, Np) and dyp.dtype == dtype and torch.equal(dyp[:, :N], dy) and not dyp[:, N:].any()
+    with pytest.raises(Exception):                        # aligned and no copy at hand: a u3d_transpose launch, not a torch fallback
+        dense._transposed(torch.randn(32, K), 32)

@@ -4,7 +4,7 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from unidet3d_amd import precision as P
-from unidet3d_amd.dense import _gemm_nt
+from unidet3d_amd.dense import FP32
 dev = torch.device('cuda:0')
 g = torch.Generator().manual_seed(1)
 for K in (32, 256, 2048):
@@ -13,7 +13,7 @@ for K in (32, 256, 2048):
     line = f'K={K:5d}:'
     for mode in ('mfma', 'bf16x3'):
         with P.fp32_math(mode):
-            y = _gemm_nt(a.to(dev), w.to(dev), b.to(dev)).double().cpu()
+            y = FP32.nt(a.to(dev), w.to(dev), b.to(dev)).double().cpu()
         e = (y - ref) / ref
         line += f'  {mode}: mean {e.mean():+.3e} rms {e.pow(2).mean().sqrt():.3e} max {e.abs().max():.3e}'
     yt = (a.to(dev) @ w.to(dev).t()).double().cpu(); e = (yt - ref) / ref

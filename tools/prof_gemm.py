@@ -5,7 +5,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from unidet3d_amd import _lib as L
 from unidet3d_amd import precision as P
-from unidet3d_amd.dense import _gemm_nt
+from unidet3d_amd.dense import FP32
 dev = torch.device('cuda:0')
 SHAPES = [(256, 256), (768, 256), (1024, 256), (256, 1024), (256, 32)]
 if os.environ.get('PROF_SHAPES'):            # e.g. PROF_SHAPES=768,256;256,1024
@@ -30,7 +30,7 @@ for M in [int(a) for a in sys.argv[1:]] or [41000]:
         line = f'M={M:6d} N={N:5d} K={K:5d} ({fl / 1e9:5.1f} GF):'
         for mode in ('mfma', 'bf16x3'):
             with P.fp32_math(mode):
-                t1 = bench(lambda: _gemm_nt(a, w, b))
+                t1 = bench(lambda: FP32.nt(a, w, b))
                 t3 = bench(lambda: L.call('u3d_gemm_tn', L.ptr(dy), L.ptr(a), L.ptr(dw), L.ptr(db), M, N, K, L.ptr(ws), 0.0, L.stream()))
             line += f' | {mode}: nt {t1 * 1e6:6.1f} us {fl / t1 / 1e12:6.1f} TF/s, tn {t3 * 1e6:6.1f} us {fl / t3 / 1e12:6.1f}'
         t2 = bench(lambda: torch.nn.functional.linear(a, w, b)); t4 = bench(lambda: dy.t() @ a)

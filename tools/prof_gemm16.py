@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from unidet3d_amd import _lib as L
 from unidet3d_amd import precision as P
 from unidet3d_amd import dense16 as D16
-from unidet3d_amd.dense import _gemm_nt
+from unidet3d_amd.dense import BF16
 dev = torch.device('cuda:0')
 SHAPES = [(256, 256), (768, 256), (1024, 256), (256, 1024), (256, 32)]
 
@@ -29,7 +29,7 @@ for M in [int(a) for a in sys.argv[1:]] or [24600]:
         fl = 2.0 * M * N * K
         us = lambda t: f'{t * 1e6:6.1f}'
         with P.operands('bf16'):
-            t_old = bench(lambda: _gemm_nt(a, w, b, True))
+            t_old = bench(lambda: BF16.nt(a, w, b))
         t_ff = bench(lambda: D16.gemm_nt(a, w, b))
         t_hf = bench(lambda: D16.gemm_nt(a16, w, b))
         t_fh = bench(lambda: D16.gemm_nt(a, w, b, out_bf16=True))

@@ -17,14 +17,15 @@ for N, K in ((256, 256), (768, 256), (1024, 256), (256, 1024), (256, 32), (20, 2
     dy = torch.randn(M, N, generator=g).to(dev)
     x = torch.randn(M, K, generator=g).to(dev)
     for bf in (False, True):
-        dw, db = dense._weight_grad(dy, x, True, bf)
+        flow = dense.BF16 if bf else dense.FP32
+        dw, db = dense._weight_grad(flow, dy, x, True)
         ref = dy.double().t() @ x.double()
         err = float((dw.double() - ref).abs().max() / ref.abs().max())
         eb = float((db.double() - dy.double().sum(0)).abs().max() / dy.double().sum(0).abs().max())
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for it in range(50):
-            dense._weight_grad(dy, x, True, bf)
+            dense._weight_grad(flow, dy, x, True)
         torch.cuda.synchronize()
         us = (time.perf_counter() - t0) / 50 * 1e6
         print(f'tn M={M} N={N} K={K} {"bf16" if bf else "fp32"}: {us:7.1f} us  {2.0 * M * N * K / us * 1e-6:6.1f} TF/s  err {err:.1e} bias {eb:.1e}')

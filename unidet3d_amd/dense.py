@@ -19,31 +19,30 @@ def set_profile_flops(on: bool):
     _PROFILE_FLOPS = bool(on)
 
 
-def _pad_k(t, mult):
-    """zero-pad the last (reduction) dim of a 2-D tensor to a multiple of ``mult``"""
-    k = t.shape[1]
-    return t if k % mult == 0 else torch.nn.functional.pad(t, (0, mult - k % mult))
-
-
-def _gemm_nt(a, w, bias, bf=False, planes=None):
-    """a [M,K] . w[N,K]^T (+ bias); ``bf``: bf16 MFMA operands (K is zero-padded to a multiple of 32 when needed);
-    ``planes``: the pre-split planes of ``w`` (three-plane products only)."""
-    M = a.shape[0]
-    N = w.shape[0]
-    c = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    if M:
-        if bf:
-            a, w = _pad_k(a, 32), _pad_k(w, 32)
-            L.call('u3d_linear_act', L.ptr(a), L.ptr(w), L.ptr(bias), P.BF16_FLAG, None, L.ptr(c), M, N, a.shape[1],
-                   _flops(M, N, a.shape[1]), L.stream())
-        else:
-            K = a.shape[1]
-            _use_planes(w, planes)
-            L.call('u3d_gemm_nt', L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(c), M, N, K, _flops(M, N, K), L.stream())
-    return c
-
-
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+# Epilogue of a data flow's NT product (``nt`` of the flow objects below; the values are the epi codes of u3d_gemm_nt_b16):
+# + bias | relu(+ bias) | times relu'(aux), aux = the ReLU output | + aux.  EPI_GELU_MASK: times gelu'(aux), aux = the GELU
+# pre-activation -- the fp32-tensor flow under FUSE_GELU only.
+EPI_BIAS, EPI_RELU, EPI_RELU_MASK, EPI_ADD = 0, 1, 3, 5
+EPI_GELU_MASK = 4
+
+
+def _book(M, N, K, nbytes=None, extra_mn=0):
+    """algorithmic flops of an [M,K] x [K,N] product, booked with its bytes (``nbytes``; default: fp32 operands + result (+ extra
+    [M,N] streams))"""
+    if not _PROFILE_FLOPS:
+        return 0.0
+    if nbytes is None:
+        nbytes = 4.0 * (M * K + N * K + M * N * (1 + extra_mn))
+    account.add('gemm', 2.0 * M * N * K, float(nbytes))
+    return 2.0 * M * N * K
+
+
+def _pad_cols(t, q):
+    """the last dim of a 2-D tensor zero-padded to a multiple of ``q`` (``t`` itself when it is one): the reduction depth of an NT
+    product, or the columns of dy in front of a TN product (tiny heads: N = 19, 8)"""
+    n = t.shape[1]
+    return t if n % q == 0 else torch.nn.functional.pad(t, (0, q - n % q))
 
 
 # ---- transposed weight copies of a whole forward pass in one launch ----------------------------------------------------------------
@@ -126,7 +125,7 @@ _W_PLANES = os.environ.get('U3D_W_PLANES', '0') == '1'
 def _planes_of(mat):
     """bf16 [3 * N * K] planes of an fp32 matrix (a weight or its transposed copy) made by the enclosing transposed_weights()
     context; None outside one.  Callers keep the tensor (ctx) for as long as a launch may read it."""
-    if _WT_ACTIVE is None or mat is None:
+    if _WT_ACTIVE is None or mat is None or '_planes' not in _WT_ACTIVE:
         return None
     # a weight modified in place since the context was entered: its planes are stale, like its transposed copy (``_wt_of``) -> None,
     # and the kernel splits the operand itself.  (A transposed copy has no entry in ``_versions``: ``_wt_of`` has vouched for it.)
@@ -154,83 +153,200 @@ def _wt_of(weight):
     return wt if _WT_ACTIVE.get('_versions', {}).get(weight.data_ptr()) == weight._version else None
 
 
-def _flops(M, N, K, extra_mn=0):
-    """algorithmic flops of an [M,K] x [K,N] product, booked with its bytes (operands + result (+ extra [M,N] streams))"""
-    if not _PROFILE_FLOPS:
-        return 0.0
-    account.add('gemm', 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N * (1 + extra_mn)))
-    return 2.0 * M * N * K
-
-
-def _input_grad(dy, weight, act=ACT_NONE, aux=None, bf=False, wt=None, wt_planes=None):
-    """dX[M,K] = dY[M,N] . W[N,K], optionally times act'(aux) in the GEMM epilogue (u3d_linear_dact): the input gradient
-    THROUGH the activation that produced this layer's input (aux = its ReLU output / GELU pre-activation)."""
-    M, N = dy.shape
-    K = weight.shape[1]
-    dev = dy.device
-    q = 32 if bf else 16                                # reduction-depth granule of the kernel
+def _transposed(weight, q, wt=None, planes=None):
+    """([K, Np] copy of ``weight`` [N, K] with the reduction dim N zero-padded to a multiple of ``q``, its pre-split planes or None).
+    ``wt`` / ``planes``: the copy transposed_weights() made for this forward pass and its planes; they serve when no padding is needed."""
+    N, K = weight.shape
     if N % q == 0:
-        if wt is None:              # (``wt``: the copy transposed_weights() made for this forward pass; ``wt_planes``: its planes)
-            wt = torch.empty(K, N, dtype=torch.float32, device=dev)
-            L.call('u3d_transpose', L.ptr(weight.contiguous()), L.ptr(wt), N, K, L.stream())
-            wt_planes = None
-    else:
-        wt_planes = None                                               # tiny heads (N = 19, 8): pad the reduction dim with zero columns
-        Np = (N + q - 1) // q * q
-        wt = torch.zeros(K, Np, dtype=torch.float32, device=dev)
-        wt[:, :N] = weight.t()
-        dyp = torch.zeros(M, Np, dtype=torch.float32, device=dev)
-        dyp[:, :N] = dy
-        dy, N = dyp, Np
-    if act == ACT_NONE:
-        return _gemm_nt(dy, wt, None, bf, None if bf else wt_planes)
-    dx = torch.empty(M, K, dtype=torch.float32, device=dev)
-    if M:
-        if not bf:
-            _use_planes(wt, wt_planes)
-        L.call('u3d_linear_dact', L.ptr(dy), L.ptr(wt), L.ptr(aux), act | (P.BF16_FLAG if bf else 0), L.ptr(dx), M, K, N,
-               _flops(M, K, N, extra_mn=1), L.stream())
-    return dx
+        if wt is not None:
+            return wt, planes
+        wt = torch.empty(K, N, dtype=torch.float32, device=weight.device)
+        L.call('u3d_transpose', L.ptr(weight.contiguous()), L.ptr(wt), N, K, L.stream())
+        return wt, None
+    wt = torch.zeros(K, (N + q - 1) // q * q, dtype=torch.float32, device=weight.device)       # tiny heads (N = 19, 8)
+    wt[:, :N] = weight.t()
+    return wt, None
 
 
-def _weight_grad(dy, x, want_bias, bf=False):
-    """(dW[N,K] = dY^T X, db[N] = column sums of dY or None): one pass of u3d_gemm_tn (+ fixed-order reduce)."""
-    tn = 'u3d_gemm_tn_bf16' if bf else 'u3d_gemm_tn'
-    M, N = dy.shape
-    K = x.shape[1]
-    dev = dy.device
-    db = None
-    dw = torch.empty(N, K, dtype=torch.float32, device=dev)
-    if M and N % 4 == 0:
-        ws = L.scratch(L.lib().u3d_gemm_tn_ws_bytes(M, N, K), dev)
-        if want_bias:                                   # the bias gradient (column sums of dy) rides along
-            db = torch.empty(N, dtype=torch.float32, device=dev)
-        L.call(tn, L.ptr(dy), L.ptr(x), L.ptr(dw), L.ptr(db), M, N, K, L.ptr(ws), _flops(M, N, K), L.stream())
+# ---- the two data flows ------------------------------------------------------------------------------------------------------------
+# Every op below exists once; what differs between fp32 tensors in HBM and the bf16 activations of precision.bf16_act() is behind a
+# flow object: ``operand(t)`` (the tensor a GEMM streams for t), ``nt`` / ``tn`` (the products), ``ffn`` / ``ln_linear`` (the forward
+# entry points that fuse two steps), ``gelu`` (the names of the stand-alone GELU passes), ``q`` / ``tn_q(dy)`` (padding granules of
+# the NT reduction depth / of dy's columns in a TN product), ``b16_like(t)`` (the bf16 copy a LayerNorm writes next to t, or None).
+# The fp32-tensor flow is here (FP32, and BF16 with bf16 MFMA operands); the bf16-activation flow is dense16.FLOW.
+class _Flow32:
+    """every activation and gradient is an fp32 tensor; ``bf``: the MFMA operands are rounded to bf16 in flight (precision.bf16())"""
+    act16 = False
+    gelu = ('u3d_gelu_fwd', 'u3d_gelu_bwd')
+
+    def __init__(self, bf):
+        self.bf = bf
+        self.flag = P.BF16_FLAG if bf else 0
+        self.q = 32 if bf else 16                       # reduction-depth granule of the NT kernels
+
+    @staticmethod
+    def operand(t):
+        return t
+
+    @staticmethod
+    def tn_q(dy):
+        return 4
+
+    @staticmethod
+    def b16_like(t):
+        return None
+
+    def nt(self, a, w, bias=None, epi=EPI_BIAS, aux=None, out_bf16=False, planes=None):
+        """epi(a [M,K] . w [N,K]^T), fp32 (``out_bf16`` is for the other flow); ``planes``: the pre-split planes of ``w`` (three-plane
+        products only).  Under bf16 operands K of the plain product is zero-padded to a multiple of 32 when needed."""
+        M, K = a.shape
+        N = w.shape[0]
+        c = torch.empty(M, N, dtype=torch.float32, device=a.device)
+        if not M:
+            return c
+        if epi == EPI_BIAS:
+            if self.bf:
+                a, w = _pad_cols(a, 32), _pad_cols(w, 32)
+                L.call('u3d_linear_act', L.ptr(a), L.ptr(w), L.ptr(bias), P.BF16_FLAG, None, L.ptr(c), M, N, a.shape[1],
+                       _book(M, N, a.shape[1]), L.stream())
+            else:
+                _use_planes(w, planes)
+                L.call('u3d_gemm_nt', L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(c), M, N, K, _book(M, N, K), L.stream())
+        elif epi == EPI_ADD:
+            L.call('u3d_gemm_nt_add', L.ptr(a), L.ptr(w), L.ptr(aux), self.flag, L.ptr(c), M, N, K, _book(M, N, K, extra_mn=1), L.stream())
+        else:                                            # the input gradient THROUGH the activation (u3d_linear_dact)
+            act = {EPI_RELU_MASK: ACT_RELU, EPI_GELU_MASK: ACT_GELU}[epi]
+            if not self.bf:
+                _use_planes(w, planes)
+            L.call('u3d_linear_dact', L.ptr(a), L.ptr(w), L.ptr(aux), act | self.flag, L.ptr(c), M, N, K, _book(M, N, K, extra_mn=1),
+                   L.stream())
+        return c
+
+    def tn(self, dy, x, want_bias):
+        """(dy^T x [N,K], column sums of dy [N] or None): one pass of u3d_gemm_tn (+ fixed-order reduce); N % 4 == 0"""
+        M, N = dy.shape
+        K = x.shape[1]
+        dw = torch.empty(N, K, dtype=torch.float32, device=dy.device)
+        db = torch.empty(N, dtype=torch.float32, device=dy.device) if want_bias else None       # rides along
+        if M:
+            ws = L.scratch(L.lib().u3d_gemm_tn_ws_bytes(M, N, K), dy.device)
+            L.call('u3d_gemm_tn_bf16' if self.bf else 'u3d_gemm_tn', L.ptr(dy), L.ptr(x), L.ptr(dw), L.ptr(db), M, N, K, L.ptr(ws),
+                   _book(M, N, K), L.stream())
+        else:
+            dw.zero_()
+            if db is not None:
+                db.zero_()
+        return dw, db
+
+    def ffn(self, x, w1, b1, w2, b2, act, p1, p2):
+        """(h, a, z) of z = act(x W1^T + b1) W2^T + b2 (include/u3d.h u3d_ffn_fwd): bias and activation live in the first GEMM's
+        epilogue; a = the activation, h = the GELU pre-activation (None for ReLU)"""
+        M, d_in = x.shape
+        hid, d_out = w1.shape[0], w2.shape[0]
+        a = torch.empty(M, hid, dtype=torch.float32, device=x.device)
+        h = torch.empty(M, hid, dtype=torch.float32, device=x.device) if act == ACT_GELU else None
+        z = torch.empty(M, d_out, dtype=torch.float32, device=x.device)
+        if M:
+            _book(M, hid, d_in, extra_mn=1 if act == ACT_GELU else 0)
+            _book(M, d_out, hid)
+            if not self.bf:
+                _use_planes(w1, p1, w2, p2)
+            L.call('u3d_ffn_fwd', L.ptr(x), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), act | self.flag, L.ptr(h), L.ptr(a), L.ptr(z),
+                   M, d_in, hid, d_out, 1.0 if _PROFILE_FLOPS else 0.0, L.stream())
+        return h, a, z
+
+    def ln_linear(self, x, gamma, beta, eps, w, bias):
+        """(nq, None, stats, y) = (LayerNorm(x), no bf16 copy, row statistics, nq W^T + b): include/u3d.h u3d_ln_linear"""
+        M, C = x.shape
+        N = w.shape[0]
+        nq = torch.empty_like(x)
+        stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
+        y = torch.empty(M, N, dtype=torch.float32, device=x.device)
+        if M:
+            L.call('u3d_ln_linear', L.ptr(x), None, L.ptr(gamma), L.ptr(beta), float(eps), None, L.ptr(nq), L.ptr(stats), L.ptr(w),
+                   L.ptr(bias), self.flag, None, L.ptr(y), M, C, N, _book(M, N, C), L.stream())
+        return nq, None, stats, y
+
+
+FP32, BF16 = _Flow32(False), _Flow32(True)
+
+
+def _act16(x, *reduction_dims):
+    """the bf16-activation data flow of dense16.py applies: precision.bf16_act(), a device tensor, every reduction depth % 32 == 0"""
+    return P.bf16_act() and x.is_cuda and all(d % 32 == 0 for d in reduction_dims)
+
+
+def _flow(x, *reduction_dims):
+    """The data flow of one op: chosen ONCE, by its public wrapper, and kept on ctx -- backward runs the flow its forward ran, whatever
+    the precision settings are by then."""
+    if _act16(x, *reduction_dims):
+        from . import dense16                           # (imports this module)
+        return dense16.FLOW
+    return BF16 if P.bf16() else FP32
+
+
+def _layer_norm_fwd(flow, x, res, gamma, beta, eps, s):
+    """(y, y16, stats) = (LayerNorm(x + res), its bf16 copy where the flow keeps one, row statistics); ``s`` receives x + res"""
+    M, C = x.shape
+    y = torch.empty_like(x)
+    y16 = flow.b16_like(x)
+    stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
+    if M and y16 is None:
+        L.call('u3d_layer_norm_fwd', L.ptr(x), L.ptr(res), L.ptr(gamma), L.ptr(beta), M, C, float(eps), L.ptr(s), L.ptr(y),
+               L.ptr(stats), L.stream())
     elif M:
-        Np = (N + 3) // 4 * 4
-        dyp = torch.zeros(M, Np, dtype=torch.float32, device=dev)
-        dyp[:, :N] = dy
-        dwp = torch.empty(Np, K, dtype=torch.float32, device=dev)
-        ws = L.scratch(L.lib().u3d_gemm_tn_ws_bytes(M, Np, K), dev)
-        dbp = torch.empty(Np, dtype=torch.float32, device=dev) if want_bias else None
-        L.call(tn, L.ptr(dyp), L.ptr(x), L.ptr(dwp), L.ptr(dbp), M, Np, K, L.ptr(ws), 0.0, L.stream())
-        dw = dwp[:N].contiguous()
-        if dbp is not None:
-            db = dbp[:N].contiguous()
+        L.call('u3d_layer_norm_fwd_b16', L.ptr(x), L.ptr(res), L.ptr(gamma), L.ptr(beta), M, C, float(eps), L.ptr(s), L.ptr(y),
+               L.ptr(y16), L.ptr(stats), L.stream())
+    return y, y16, stats
+
+
+def _layer_norm_bwd(x, dy, gamma, stats):
+    """(dx, dgamma, dbeta) of y = LayerNorm(x) for ONE incoming gradient (the tail of ``_LNLinearFn.backward``)"""
+    M, C = x.shape
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    if M:
+        ws = L.scratch(L.lib().u3d_layer_norm_ws_bytes(M, C), x.device)
+        L.call('u3d_layer_norm_bwd', L.ptr(x), L.ptr(dy), L.ptr(gamma), L.ptr(stats), M, C, L.ptr(dx), L.ptr(dg), L.ptr(db), L.ptr(ws),
+               L.stream())
     else:
-        dw.zero_()
-        if want_bias:
-            db = torch.zeros(N, dtype=torch.float32, device=dev)
+        dg.zero_(); db.zero_()
+    return dx, dg, db
+
+
+def _gelu_pass(name, *ts):
+    """a stand-alone GELU pass over whole tensors: a = gelu(h) for (h,), dh = da * gelu'(h) for (da, h)"""
+    out = torch.empty_like(ts[0])
+    if out.numel():
+        L.call(name, *[L.ptr(t) for t in ts], L.ptr(out), out.numel(), L.stream())
+    return out
+
+
+def _input_grad(flow, dy, weight, wt=None, wt_planes=None, epi=EPI_BIAS, aux=None, out_bf16=False):
+    """dX[M,K] = epi(dY[M,N] . W[N,K]): an NT product over the transposed (and, for the tiny heads, zero-padded) weight.  EPI_*_MASK:
+    the input gradient THROUGH the activation that produced this layer's input (aux = its ReLU output / GELU pre-activation)."""
+    wt, wt_planes = _transposed(weight, flow.q, wt, wt_planes)
+    return flow.nt(_pad_cols(dy, flow.q), wt, None, epi, aux, out_bf16, wt_planes)
+
+
+def _weight_grad(flow, dy, x, want_bias):
+    """(dW[N,K] = dY^T X, db[N] = column sums of dY or None); the columns of dY zero-padded to the TN kernel's granule (N = 19)"""
+    N = dy.shape[1]
+    dyp = _pad_cols(dy, flow.tn_q(dy))
+    dw, db = flow.tn(dyp, x, want_bias)
+    if dyp is not dy:
+        dw, db = dw[:N].contiguous(), (db[:N].contiguous() if db is not None else None)
     return dw, db
 
 
-def _weight_grad_overlapped(dy, x, want_bias, bf, weight, bias):
+def _weight_grad_overlapped(flow, dy, x, want_bias, weight, bias):
     """``_weight_grad`` on the weight-gradient side stream when set_wgrad_overlap(2) is on (wgrad_stream.py; nothing downstream of a
     Linear needs its dW: the GEMM joins the sparse convolutions' weight-gradient chain and the dX chain goes on without it).  Only for
     leaf parameters without an existing .grad -- autograd then just stores the tensor; anything else is computed in line."""
     if not (WS.mode() == 2 and _OVERLAP_TN and dy.is_cuda and WS.async_dw_ok(weight, bias)):
-        return _weight_grad(dy, x, want_bias, bf)
-    _, grads = WS.run_on_side_stream(dy.device, lambda: _weight_grad(dy, x, want_bias, bf), reads=(dy, x))
+        return _weight_grad(flow, dy, x, want_bias)
+    _, grads = WS.run_on_side_stream(dy.device, lambda: _weight_grad(flow, dy, x, want_bias), reads=(dy, x))
     WS.queue_join(dy.device)
     return grads
 
@@ -239,115 +355,105 @@ _OVERLAP_TN = os.environ.get('U3D_OVERLAP_TN', '1') != '0'
 
 
 class _LinearFn(torch.autograd.Function):
+    """y = x W^T + b.  x and (in backward) dy are streamed as ``flow.operand`` gives them.  Under dense16.FLOW the result is fp32, or
+    -- ``out_bf16``: the packed q / k / v projection, whose only consumer is the attention kernel -- a bf16 tensor (its gradient then
+    arrives as one); a bf16 INPUT (the attention output in front of ``out_proj``) gets a bf16 gradient back."""
+
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, flow, x, weight, bias, out_bf16):
         x = x.contiguous()
-        ctx.save_for_backward(x, weight)
+        xa = flow.operand(x)
+        w = weight.contiguous()
+        ctx.save_for_backward(xa, w)
+        ctx.flow = flow
         ctx.has_bias = bias is not None
         ctx.bias_ref = bias
-        ctx.bf = P.bf16()
         ctx.wt = _wt_of(weight)
         ctx.wt_planes = _planes_of(ctx.wt)
-        return _gemm_nt(x, weight.contiguous(), bias, ctx.bf, None if ctx.bf else _planes_of(weight))
+        ctx.dx_bf16 = x.dtype == torch.bfloat16
+        return flow.nt(xa, w, bias, out_bf16=bool(out_bf16) and w.shape[0] % 2 == 0, planes=_planes_of(weight))
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
+        xa, weight = ctx.saved_tensors
+        flow = ctx.flow
         dy = dy.contiguous()
+        da = flow.operand(dy)
         dx = dw = db = None
-        if ctx.needs_input_grad[1]:           # first: on the side stream it then waits for dy only, not for the dX product below
-            dw, db = _weight_grad_overlapped(dy, x, ctx.has_bias and ctx.needs_input_grad[2], ctx.bf, weight, ctx.bias_ref)
-        if ctx.needs_input_grad[0]:
-            dx = _input_grad(dy, weight, bf=ctx.bf, wt=ctx.wt, wt_planes=ctx.wt_planes)
-        if db is None and ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy.sum(0)
-        return dx, dw, db
-
-
-def _act16(x, *reduction_dims):
-    """the bf16-activation data flow of dense16.py applies: precision.bf16_act(), a device tensor, every reduction depth % 32 == 0"""
-    return P.bf16_act() and x.is_cuda and all(d % 32 == 0 for d in reduction_dims)
+        if ctx.needs_input_grad[2]:           # first: on the side stream it then waits for dy only, not for the dX product below
+            dw, db = _weight_grad_overlapped(flow, da, xa, ctx.has_bias and ctx.needs_input_grad[3], weight, ctx.bias_ref)
+        if ctx.needs_input_grad[1]:
+            dx = _input_grad(flow, da, weight, ctx.wt, ctx.wt_planes, out_bf16=ctx.dx_bf16)
+        if db is None and ctx.has_bias and ctx.needs_input_grad[3]:
+            db = dy.float().sum(0)
+        return None, dx, dw, db, None
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias=None, out_bf16: bool = False) -> torch.Tensor:
     """y = x W^T + b for 2-D x [M, K] (K % 16 == 0).  ``out_bf16``: under precision.bf16_act() the result is a bf16 tensor (for a
     consumer that reads one: the attention kernels); ignored otherwise."""
-    if _act16(x, x.shape[1]):
-        from . import dense16
-        return dense16.linear(x, weight, bias, out_bf16)
-    return _LinearFn.apply(x, weight, bias)
+    return _LinearFn.apply(_flow(x, x.shape[1]), x, weight, bias, out_bf16)
 
 
 # GELU in the GEMM epilogues (True) or as stand-alone passes u3d_gelu_fwd / u3d_gelu_bwd between plain GEMMs (False).  ReLU is
 # always fused (one v_max / one compare per element).  Measured on MI355X (tools/prof_mlp.py, FFN 256 -> 1024 -> 256 over 16.8 k
 # rows, forward + backward): fused 0.761 ms, stand-alone passes 0.682 ms (bf16 operands: 0.487 / 0.438) -- the ~15 VALU
 # instructions per element of the erf GELU are not hidden in a GEMM epilogue (one wave per SIMD), while the stand-alone pass
-# runs at HBM speed; so the default is the stand-alone pass.
+# runs at HBM speed; so the default is the stand-alone pass.  (The bf16-activation flow has the stand-alone pass only.)
 FUSE_GELU = os.environ.get('U3D_FUSE_GELU', '0') == '1'
 
 
 class _MLPFn(torch.autograd.Function):
-    """z = act(x W1^T + b1) W2^T + b2 (include/u3d.h u3d_ffn_fwd): bias and activation live in the first GEMM's epilogue, the
-    activation's derivative in the epilogue of the GEMM that produces the hidden gradient -- no elementwise kernels."""
+    """z = act(x W1^T + b1) W2^T + b2.  Fused (ReLU always, GELU under FUSE_GELU): bias and activation live in the first GEMM's
+    epilogue (``flow.ffn``), the activation's derivative in the epilogue of the GEMM that produces the hidden gradient -- no
+    elementwise kernels.  Under dense16.FLOW the hidden tensors (and their gradients) exist in bf16 only; z is fp32."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, act):
+    def forward(ctx, flow, x, w1, b1, w2, b2, act):
         x = x.contiguous()
-        M, d_in = x.shape
-        hid, d_out = w1.shape[0], w2.shape[0]
-        dev = x.device
-        a = torch.empty(M, hid, dtype=torch.float32, device=dev)
-        h = torch.empty(M, hid, dtype=torch.float32, device=dev) if act == ACT_GELU else None
-        z = torch.empty(M, d_out, dtype=torch.float32, device=dev)
+        xa = flow.operand(x)
         w1c, w2c = w1.contiguous(), w2.contiguous()
-        ctx.bf = P.bf16()
+        ctx.flow = flow
         ctx.wt1, ctx.wt2 = _wt_of(w1c), _wt_of(w2c)
         ctx.wtp1, ctx.wtp2 = _planes_of(ctx.wt1), _planes_of(ctx.wt2)
-        p1, p2 = (None, None) if ctx.bf else (_planes_of(w1c), _planes_of(w2c))
-        ctx.fused = act != ACT_GELU or FUSE_GELU
-        if M and not ctx.fused:                      # plain GEMM (+bias) -> GELU pass -> plain GEMM
-            h = _gemm_nt(x, w1c, b1, ctx.bf, p1)
-            L.call('u3d_gelu_fwd', L.ptr(h), L.ptr(a), M * hid, L.stream())
-            z = _gemm_nt(a, w2c, b2, ctx.bf, p2)
-        elif M:
-            _flops(M, hid, d_in, extra_mn=1 if act == ACT_GELU else 0)
-            _flops(M, d_out, hid)
-            _use_planes(w1c, p1, w2c, p2)
-            L.call('u3d_ffn_fwd', L.ptr(x), L.ptr(w1c), L.ptr(b1), L.ptr(w2c), L.ptr(b2), act | (P.BF16_FLAG if ctx.bf else 0),
-                   L.ptr(h), L.ptr(a), L.ptr(z), M, d_in, hid, d_out, 1.0 if _PROFILE_FLOPS else 0.0, L.stream())
-        ctx.save_for_backward(x, w1c, w2c, a, h)
+        p1, p2 = _planes_of(w1c), _planes_of(w2c)
+        ctx.fused = act != ACT_GELU or (FUSE_GELU and not flow.act16)
+        if ctx.fused:
+            h, a, z = flow.ffn(xa, w1c, b1, w2c, b2, act, p1, p2)
+        else:                                           # plain GEMM (+bias) -> GELU pass -> plain GEMM
+            h = flow.nt(xa, w1c, b1, out_bf16=True, planes=p1)
+            a = _gelu_pass(flow.gelu[0], h)
+            z = flow.nt(a, w2c, b2, planes=p2)
+        ctx.save_for_backward(xa, w1c, w2c, a, h)
         ctx.act, ctx.bias = act, (b1 is not None, b2 is not None)
         ctx.bias_refs = (b1, b2)
         return z
 
     @staticmethod
     def backward(ctx, dz):
-        x, w1, w2, a, h = ctx.saved_tensors
+        xa, w1, w2, a, h = ctx.saved_tensors
+        flow = ctx.flow
         dz = dz.contiguous()
-        need = ctx.needs_input_grad
-        dw2, db2 = _weight_grad_overlapped(dz, a, ctx.bias[1] and need[4], ctx.bf, w2, ctx.bias_refs[1]) if need[3] else (None, None)
+        dza = flow.operand(dz)
+        need = ctx.needs_input_grad[1:]
+        dw2, db2 = _weight_grad_overlapped(flow, dza, a, ctx.bias[1] and need[4], w2, ctx.bias_refs[1]) if need[3] else (None, None)
         if ctx.fused:
-            dh = _input_grad(dz, w2, ctx.act, h if ctx.act == ACT_GELU else a, bf=ctx.bf, wt=ctx.wt2, wt_planes=ctx.wtp2)
+            epi, aux = (EPI_GELU_MASK, h) if ctx.act == ACT_GELU else (EPI_RELU_MASK, a)
+            dh = _input_grad(flow, dza, w2, ctx.wt2, ctx.wtp2, epi, aux, out_bf16=True)
         else:
-            da = _input_grad(dz, w2, bf=ctx.bf, wt=ctx.wt2, wt_planes=ctx.wtp2)
-            dh = torch.empty_like(da)
-            if da.numel():
-                L.call('u3d_gelu_bwd', L.ptr(da), L.ptr(h), L.ptr(dh), da.numel(), L.stream())
-        dw1, db1 = _weight_grad_overlapped(dh, x, ctx.bias[0] and need[2], ctx.bf, w1, ctx.bias_refs[0]) if need[1] else (None, None)
-        dx = _input_grad(dh, w1, bf=ctx.bf, wt=ctx.wt1, wt_planes=ctx.wtp1) if need[0] else None
-        if db2 is None and ctx.bias[1] and need[4]:          # a trainable bias on a frozen weight: no u3d_gemm_tn to ride along with
-            db2 = dz.sum(0)
+            dh = _gelu_pass(flow.gelu[1], _input_grad(flow, dza, w2, ctx.wt2, ctx.wtp2, out_bf16=True), h)
+        dw1, db1 = _weight_grad_overlapped(flow, dh, xa, ctx.bias[0] and need[2], w1, ctx.bias_refs[0]) if need[1] else (None, None)
+        dx = _input_grad(flow, dh, w1, ctx.wt1, ctx.wtp1) if need[0] else None
+        if db2 is None and ctx.bias[1] and need[4]:          # a trainable bias on a frozen weight: no TN product to ride along with
+            db2 = dz.float().sum(0)
         if db1 is None and ctx.bias[0] and need[2]:
-            db1 = dh.sum(0)
-        return dx, dw1, db1, dw2, db2, None
+            db1 = dh.float().sum(0)
+        return None, dx, dw1, db1, dw2, db2, None
 
 
 def mlp(x, w1, b1, w2, b2, act: str) -> torch.Tensor:
     """Linear -> ReLU / GELU -> Linear on 2-D x (d_in, hidden % 16 == 0)."""
-    if _act16(x, x.shape[1], w1.shape[0]):
-        from . import dense16
-        return dense16.mlp(x, w1, b1, w2, b2, {'relu': ACT_RELU, 'gelu': ACT_GELU}[act])
-    return _MLPFn.apply(x, w1, b1, w2, b2, {'relu': ACT_RELU, 'gelu': ACT_GELU}[act])
+    return _MLPFn.apply(_flow(x, x.shape[1], w1.shape[0]), x, w1, b1, w2, b2, {'relu': ACT_RELU, 'gelu': ACT_GELU}[act])
 
 
 def _aliases(y, n_out):
@@ -366,119 +472,107 @@ def _grads_in(dys):
 
 class _LayerNormFn(torch.autograd.Function):
     """y = LayerNorm(x + res) over the last dimension (include/u3d.h K15); the gradient of x and res is the same tensor.  ``n_out`` > 1:
-    the result is returned that many times (one output per consumer) and the backward kernel sums their gradients (u3d_layer_norm_bwd_sum)."""
+    the result is returned that many times (one output per consumer) and the backward kernel sums their gradients (u3d_layer_norm_bwd_sum).
+    Under dense16.FLOW the outputs are (y, ..., y16) -- the bf16 copy, not differentiable, which ``layer_norm`` attaches to every y --
+    and backward attaches the copy of dx it writes."""
 
     @staticmethod
-    def forward(ctx, x, res, weight, bias, eps, n_out=1):
+    def forward(ctx, flow, x, res, weight, bias, eps, n_out=1):
         x = x.contiguous()
-        M, C = x.shape
-        y = torch.empty_like(x)
-        stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
         s = x
         if res is not None:
             res = res.contiguous()
             s = torch.empty_like(x)
-        if M:
-            L.call('u3d_layer_norm_fwd', L.ptr(x), L.ptr(res), L.ptr(weight), L.ptr(bias), M, C, float(eps),
-                   L.ptr(s) if res is not None else None, L.ptr(y), L.ptr(stats), L.stream())
+        y, y16, stats = _layer_norm_fwd(flow, x, res, weight, bias, eps, s if res is not None else None)
         ctx.save_for_backward(s, weight, stats)
+        ctx.flow = flow
         ctx.has_res = res is not None
         ctx.set_materialize_grads(False)
-        return _aliases(y, n_out)
+        ys = _aliases(y, n_out)
+        if y16 is None:
+            return ys
+        ctx.mark_non_differentiable(y16)
+        return (ys if n_out > 1 else (ys,)) + (y16,)
 
     @staticmethod
     def backward(ctx, *dys):
         s, weight, stats = ctx.saved_tensors
-        dy, dy2, dy3 = _grads_in(dys)
+        dy, dy2, dy3 = _grads_in(dys[:-1] if ctx.flow.act16 else dys)
         if dy is None:
-            return (None,) * 6
+            return (None,) * 7
         M, C = s.shape
         dx = torch.empty_like(s)
+        dx16 = ctx.flow.b16_like(s)
         dg = torch.empty(C, dtype=torch.float32, device=s.device)
         db = torch.empty(C, dtype=torch.float32, device=s.device)
         if M:
             ws = L.scratch(L.lib().u3d_layer_norm_ws_bytes(M, C), s.device)
-            L.call('u3d_layer_norm_bwd_sum', L.ptr(s), L.ptr(dy), L.ptr(dy2), L.ptr(dy3), L.ptr(weight), L.ptr(stats), M, C, L.ptr(dx), None,
-                   L.ptr(dg), L.ptr(db), L.ptr(ws), L.stream())
+            L.call('u3d_layer_norm_bwd_sum', L.ptr(s), L.ptr(dy), L.ptr(dy2), L.ptr(dy3), L.ptr(weight), L.ptr(stats), M, C, L.ptr(dx),
+                   L.ptr(dx16), L.ptr(dg), L.ptr(db), L.ptr(ws), L.stream())
         else:
             dg.zero_(); db.zero_()
-        return dx, (dx if ctx.has_res else None), dg, db, None, None
+        if dx16 is not None:
+            ctx.flow.attach(dx, dx16)
+        return None, dx, (dx if ctx.has_res else None), dg, db, None, None
 
 
 def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5, res: torch.Tensor = None, n_out: int = 1):
     """LayerNorm(x + res) for 2-D x [M, C] (C % 4 == 0, C <= 1024).  ``n_out`` in (2, 3): a tuple of that many tensors, all THE result
     (shared storage) -- hand each consumer its own and the backward kernel sums their gradients (no elementwise add passes)."""
-    if _act16(x, x.shape[1]):
-        from . import dense16
-        return dense16.layer_norm(x, weight, bias, eps, res, n_out)
-    return _LayerNormFn.apply(x, res, weight, bias, eps, n_out)
+    flow = _flow(x, x.shape[1])
+    out = _LayerNormFn.apply(flow, x, res, weight, bias, eps, n_out)
+    if not flow.act16:
+        return out
+    *ys, y16 = out
+    for y in ys:
+        flow.attach(y, y16)
+    return ys[0] if n_out == 1 else tuple(ys)
 
 
 class _LNLinearFn(torch.autograd.Function):
-    """(nq, y) = (LayerNorm(x), nq W^T + b)  -- include/u3d.h u3d_ln_linear.  Backward folds the two gradient contributions of
-    ``nq`` (its own consumers + this Linear) into the GEMM that produces the second (u3d_gemm_nt_add), then runs the
-    LayerNorm backward once."""
+    """(nq, nq16, y) = (LayerNorm(x), its bf16 copy or None, nq W^T + b): the head (out_norm -> out_bboxes.linear,
+    unidet3d/encoder.py:187-196).  The Linear and its weight gradient stream nq16 where there is one.  Backward folds the two
+    gradient contributions of ``nq`` (its own consumers + this Linear) into the GEMM that produces the second (EPI_ADD), then runs
+    the LayerNorm backward once."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, weight, bias):
+    def forward(ctx, flow, x, gamma, beta, eps, weight, bias):
         x = x.contiguous()
-        M, C = x.shape
-        N = weight.shape[0]
-        dev = x.device
-        nq = torch.empty_like(x)
-        stats = torch.empty(M, 2, dtype=torch.float32, device=dev)
-        y = torch.empty(M, N, dtype=torch.float32, device=dev)
         w = weight.contiguous()
-        ctx.bf = P.bf16() and C % 32 == 0
-        if M:
-            L.call('u3d_ln_linear', L.ptr(x), None, L.ptr(gamma), L.ptr(beta), float(eps), None, L.ptr(nq), L.ptr(stats), L.ptr(w),
-                   L.ptr(bias), P.BF16_FLAG if ctx.bf else 0, None, L.ptr(y), M, C, N, _flops(M, N, C), L.stream())
-        ctx.save_for_backward(x, gamma, stats, nq, w)
+        nq, nq16, stats, y = flow.ln_linear(x, gamma, beta, eps, w, bias)
+        ctx.save_for_backward(x, gamma, stats, nq if nq16 is None else nq16, w)
+        ctx.flow = flow
         ctx.has_bias = bias is not None
-        return nq, y
+        if nq16 is not None:
+            ctx.mark_non_differentiable(nq16)
+        return nq, nq16, y
 
     @staticmethod
-    def backward(ctx, dnq, dy):
-        x, gamma, stats, nq, w = ctx.saved_tensors
-        M, C = x.shape
-        N = w.shape[0]
-        dev = x.device
+    def backward(ctx, dnq, _unused, dy):
+        x, gamma, stats, nqa, w = ctx.saved_tensors
         dw = db = None
         if dy is not None:
             dy = dy.contiguous()
-            dw, db = _weight_grad(dy, nq, ctx.has_bias, ctx.bf)
+            dw, db = _weight_grad(ctx.flow, dy, nqa, ctx.has_bias)
             if dnq is None:
-                dtot = _input_grad(dy, w, bf=ctx.bf)
+                dtot = _input_grad(ctx.flow, dy, w)
             else:                                        # dtot = dy W + dnq in one GEMM
-                q = 32 if ctx.bf else 16
-                Np = (N + q - 1) // q * q
-                wt = torch.zeros(C, Np, dtype=torch.float32, device=dev)
-                wt[:, :N] = w.t()
-                dyp = dy if Np == N else torch.nn.functional.pad(dy, (0, Np - N))
-                dtot = torch.empty(M, C, dtype=torch.float32, device=dev)
-                if M:
-                    L.call('u3d_gemm_nt_add', L.ptr(dyp), L.ptr(wt), L.ptr(dnq.contiguous()), P.BF16_FLAG if ctx.bf else 0, L.ptr(dtot),
-                           M, C, Np, _flops(M, C, Np, extra_mn=1), L.stream())
+                dtot = _input_grad(ctx.flow, dy, w, epi=EPI_ADD, aux=dnq.contiguous())
         else:
             dtot = dnq.contiguous()
-        dx = torch.empty_like(x)
-        dg = torch.empty(C, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(C, dtype=torch.float32, device=dev)
-        if M:
-            ws = L.scratch(L.lib().u3d_layer_norm_ws_bytes(M, C), dev)
-            L.call('u3d_layer_norm_bwd', L.ptr(x), L.ptr(dtot), L.ptr(gamma), L.ptr(stats), M, C, L.ptr(dx), L.ptr(dg), L.ptr(dbeta),
-                   L.ptr(ws), L.stream())
-        else:
-            dg.zero_(); dbeta.zero_()
-        return dx, dg, dbeta, None, dw, db
+        dx, dg, dbeta = _layer_norm_bwd(x, dtot, gamma, stats)
+        return None, dx, dg, dbeta, None, dw, db
 
 
 def ln_linear(x, gamma, beta, eps, weight, bias):
     """-> (LayerNorm(x), LayerNorm(x) W^T + b) for 2-D x [M, C]."""
-    if _act16(x, x.shape[1]):
-        from . import dense16
-        return dense16.ln_linear(x, gamma, beta, eps, weight, bias)
-    return _LNLinearFn.apply(x, gamma, beta, eps, weight, bias)
+    flow = _flow(x, x.shape[1])
+    if flow is BF16 and x.shape[1] % 32:                # the fused entry point pads no reduction depth
+        flow = FP32
+    nq, nq16, y = _LNLinearFn.apply(flow, x, gamma, beta, eps, weight, bias)
+    if nq16 is not None:
+        flow.attach(nq, nq16)
+    return nq, y
 
 
 class LayerNorm(torch.nn.LayerNorm):
