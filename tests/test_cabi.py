@@ -149,3 +149,29 @@ def test_fp32_math_switch_is_host_state_and_drives_the_conv_format():
         P.set_fp32_math(prev)
     from unidet3d_amd import sparse
     assert [sparse._pack_floats(96, f) for f in (0, 1, 2)] == [96, 48, 144]               # fp32 | bf16 | three bf16 planes
+
+
+@pytest.mark.parametrize('suffix', ['', '_bf16', '_b16'])
+@pytest.mark.parametrize('direction', ['fwd', 'bwd'])
+def test_attention_entry_points_validate_before_any_hip_call(direction, suffix):
+    """The six attention entry points share one forward and one backward body: a NULL tensor is U3D_EINVAL, a head dim other than 32
+    is U3D_EUNSUPPORTED with the head-dim message -- both decided before the first HIP call, so neither needs a GPU."""
+    from unidet3d_amd import _lib
+    l = _lib.lib()
+    fn = getattr(l, f'u3d_attn_varlen_{direction}{suffix}')
+    buf = ctypes.create_string_buffer(64)               # never dereferenced: the calls return before anything reads a tensor
+    p = ctypes.addressof(buf)
+    n_ptr = 2 if direction == 'fwd' else 5              # leading tensors: qkv, cu | qkv, out, dout, lse, cu; then B, max_len, n_total, H, hd, scale
+    tail = [p, p, 0.0, None]                            # out, lse | dqkv, delta_ws; flops_hint, stream
+
+    def call(ptrs, hd):
+        return fn(*ptrs, 1, 64, 64, 8, hd, 0.25, *tail)
+
+    for i in range(n_ptr):
+        assert call([None if j == i else p for j in range(n_ptr)], 32) == -1, f'NULL tensor {i}'        # U3D_EINVAL
+    for i in (0, 1):
+        t = list(tail)
+        t[i] = None
+        assert fn(*[p] * n_ptr, 1, 64, 64, 8, 32, 0.25, *t) == -1, f'NULL output {i}'
+    assert call([p] * n_ptr, 16) == -3                                                                   # U3D_EUNSUPPORTED
+    assert b'head_dim 16 unsupported' in l.u3d_last_error()

@@ -247,3 +247,60 @@ def test_dense_padding_helpers_pad_with_exact_zeros_and_copy_nothing_that_is_ali
                         assert dyp.shape == (M, Np) and dyp.dtype == dtype and torch.equal(dyp[:, :N], dy) and not dyp[:, N:].any()
     with pytest.raises(Exception):                        # aligned and no copy at hand: a u3d_transpose launch, not a torch fallback
         dense._transposed(torch.randn(32, K), 32)
+
+
+def test_one_command_line_per_source_for_the_build_and_for_variants(tmp_path, monkeypatch):
+    """csrc/build.py command() is the one place that says how a source is compiled: the build, variant libraries
+    (tools/build_variant.sh -> build_variant) and ISA comparisons all get a file's own options from it."""
+    from unidet3d_amd.csrc import build as B
+    fp_off = {'postproc.hip', 'augment.hip', 'targets.hip', 'optim.hip', 'evalmap.hip'}          # bit-exact against their references
+    vgpr_form = {'spconv.hip', 'spconv_wg.hip', 'attn_x3.hip'}
+    assert fp_off | vgpr_form <= set(B.SOURCES)
+    for s in B.SOURCES:
+        cmd = B.command(s)
+        assert ('-ffp-contract=off' in cmd) == (s in fp_off), s
+        assert ('-amdgpu-mfma-vgpr-form' in cmd) == (s in vgpr_form), s
+        assert '--offload-arch=gfx950' in cmd and '-c' in cmd and cmd[-3] == os.path.join(B.HERE, s) and cmd[-2] == '-o'
+        assert all(f in cmd for f in B.FLAGS) and all(f in cmd for f in B.EXTRA.get(s, []))
+        # a variant: the same flags, then the caller's, another output; nothing of the file's own options is lost
+        var = B.command(s, ['-DU3D_SPLIT_ABL'], str(tmp_path / 'x.o'))
+        assert var[:-4] == cmd[:-4] + ['-DU3D_SPLIT_ABL'] and var[-4:] == ['-c', cmd[-3], '-o', str(tmp_path / 'x.o')]
+        asm = B.command(s, kind=['--offload-device-only', '-S'])
+        assert asm[:-5] == cmd[:-4] and asm[-5:-3] == ['--offload-device-only', '-S']
+    # the variant path compiles through command(): record what it would run
+    ran = []
+    monkeypatch.setattr(B, 'build', lambda **kw: B.LIB)
+    monkeypatch.setattr(B, '_compile', lambda jobs, verbose=True: ran.extend(jobs))
+    monkeypatch.setattr(B, '_link', lambda lib, objs: ran.append(('link', lib, objs)))
+    B.build_variant(str(tmp_path / 'v.so'), ['augment.hip', 'spconv_wg.hip'], ['-DX=1'], str(tmp_path))
+    assert ran[0] == B.command('augment.hip', ['-DX=1'], str(tmp_path / 'augment.o')) and '-ffp-contract=off' in ran[0]
+    assert ran[1] == B.command('spconv_wg.hip', ['-DX=1'], str(tmp_path / 'spconv_wg.o')) and '-amdgpu-mfma-vgpr-form' in ran[1]
+    objs = ran[2][2]
+    assert len(objs) == len(B.SOURCES) and str(tmp_path / 'augment.o') in objs and os.path.join(B.HERE, 'gemm.o') in objs
+    script = [l for l in open(os.path.join(ROOT, 'tools', 'build_variant.sh')) if not l.startswith('#')]
+    assert any('unidet3d_amd.csrc.build --variant' in l for l in script) and not any('hipcc' in l or '-mllvm' in l or 'contract' in l for l in script)
+
+
+def test_an_object_is_stale_after_any_header_changes(tmp_path, monkeypatch):
+    """_stale depends on every *.h next to the sources and on include/u3d.h, not on a hand-kept list of two."""
+    from unidet3d_amd.csrc import build as B
+    here = tmp_path / 'csrc'
+    (tmp_path / 'include').mkdir()
+    here.mkdir()
+    monkeypatch.setattr(B, 'HERE', str(here))
+    monkeypatch.setattr(B, 'ROOT', str(tmp_path))
+    old, new = 1_000_000_000, 1_000_000_100
+    paths = {n: here / n for n in ('a.hip', 'a.o', 'u3d_common.h', 'spconv_gmm.h', 'attn_common.h')}
+    paths['u3d.h'] = tmp_path / 'include' / 'u3d.h'
+    for n, p in paths.items():
+        p.write_text('')
+        os.utime(p, (old, old))
+    os.utime(paths['a.o'], (new, new))
+    monkeypatch.setattr(B, '__file__', str(paths['a.hip']))               # build.py's own mtime is a dependency as well
+    assert not B._stale(str(paths['a.hip']), str(paths['a.o']))
+    for n in ('attn_common.h', 'u3d.h', 'a.hip'):                         # a header that is none of the two once named | the ABI header | the source
+        os.utime(paths[n], (new + 1, new + 1))
+        assert B._stale(str(paths['a.hip']), str(paths['a.o'])), n
+        os.utime(paths[n], (old, old))
+    assert not B._stale(str(paths['a.hip']), str(paths['a.o']))
+    assert B._stale(str(paths['a.hip']), str(here / 'missing.o'))

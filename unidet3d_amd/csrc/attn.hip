@@ -10,7 +10,7 @@
 //   dQ:       S^T, dP^T = V dO^T (same orientation) -> dS is the A operand of dQ += dS K.
 //   dK/dV:    S = Q K^T, dP = dO V^T (A = Q / dO tile from LDS, B = own K / V rows in registers)
 //             -> P^T, dS^T are the A operands of dV += P^T dO and dK += dS^T Q.
-#include "u3d_common.h"
+#include "attn_common.h"
 
 namespace u3d {
 
@@ -31,21 +31,6 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ base, int l
         *reinterpret_cast<float4*>(dst + r * ATT_LD + c4 * 4) = v;
     }
 }
-
-// 1-D launch decode: workgroup b runs on XCD b % 8 (private L2).  XCD x takes the (scene, head) pairs x, x+8, ...
-// and all their 64-row tiles back to back, so the K/V (or Q/dO) rows of one (scene, head) stay in that XCD's
-// L2 while its tiles stream them (PMC before: 321 MB fetched per forward launch for 49 MB of qkv).
-struct AttnWork { int b, h, tile; };
-__device__ __forceinline__ AttnWork attn_decode(int H, int B, int n_tiles) {
-    const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int hb = (j / n_tiles) * 8 + x;
-    AttnWork w;
-    w.tile = j % n_tiles;
-    w.h = hb % H;
-    w.b = hb / H;          // >= B for the padding workgroups of the last group
-    return w;
-}
-static inline unsigned attn_grid(int H, int B, int n_tiles) { return (unsigned)(((H * B + 7) / 8) * 8 * n_tiles); }
 
 __global__ __launch_bounds__(256) void attn_fwd_k(const float* __restrict__ qkv, const int32_t* __restrict__ cu, int H, float scale,
                                                   float* __restrict__ out, float* __restrict__ lse, int64_t n_total, int B, int n_tiles) {
@@ -147,23 +132,6 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const float* __restrict__ qkv,
         }
     }
     if (qd == 0 && qrow < len) lse[(int64_t)h * n_total + start + qrow] = m * LN2 + __logf(l);      // natural-log units
-}
-
-// delta[h][i] = sum_d dO[i][h*32+d] * O[i][h*32+d]
-__global__ __launch_bounds__(256) void attn_delta_k(const float* __restrict__ o, const float* __restrict__ dout, int64_t n, int H, float* delta) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * H) return;
-    const int64_t i = idx / H;
-    const int h = (int)(idx % H);
-    const float4* a = reinterpret_cast<const float4*>(o + i * H * 32 + h * 32);
-    const float4* b = reinterpret_cast<const float4*>(dout + i * H * 32 + h * 32);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float4 x = a[j], y = b[j];
-        s += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    delta[(int64_t)h * n + i] = s;
 }
 
 __global__ __launch_bounds__(256) void attn_bwd_dq_k(const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ lse,
@@ -322,10 +290,45 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(const float* __restrict__ 
     }
 }
 
-void attn_fwd_x3_launch(const float* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, float scale, float* out, float* lse,
-                        hipStream_t s, int planes);
-void attn_bwd_x3_launch(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu, int B, int max_len,
-                        int64_t n_total, int H, float scale, float* dqkv, float* delta_ws, hipStream_t s, int planes);
+static const char* const ATTN_FWD_LABEL[] = {"attn_fwd", "attn_fwd_x3", "attn_fwd_bf16", "attn_fwd_b16"};        // by AttnMode
+static const char* const ATTN_BWD_LABEL[] = {"attn_bwd", "attn_bwd_x3", "attn_bwd_bf16", "attn_bwd_b16"};
+
+int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
+             float* lse, double flops_hint, u3d_stream_t stream) {
+    if (!qkv || !cu || !out || !lse || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
+    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(U3D_K_ATTN_FWD, s, flops_hint);
+    if (max_len <= 0) return U3D_OK;
+    if (mode == ATTN_NATIVE) {
+        const int n_tiles = (max_len + 63) / 64;
+        hipLaunchKernelGGL(attn_fwd_k, dim3(attn_grid(H, B, n_tiles)), dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
+    } else {
+        attn_fwd_x3_launch(mode, qkv, cu, B, max_len, n_total, H, scale, out, lse, s);
+    }
+    return check_launch(ATTN_FWD_LABEL[mode]);
+}
+
+int attn_bwd(AttnMode mode, const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
+             int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream) {
+    if (!qkv || !out || !dout || !lse || !cu || !dqkv || !delta_ws || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
+    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(U3D_K_ATTN_BWD, s, flops_hint);
+    if (max_len <= 0) return U3D_OK;
+    const dim3 dgrid((unsigned)ceil_div(n_total * H, 256));
+    if (mode == ATTN_B16) hipLaunchKernelGGL(attn_delta_k<__bf16>, dgrid, dim3(256), 0, s, (const __bf16*)out, (const __bf16*)dout, n_total, H, delta_ws);
+    else hipLaunchKernelGGL(attn_delta_k<float>, dgrid, dim3(256), 0, s, (const float*)out, (const float*)dout, n_total, H, delta_ws);
+    if (mode == ATTN_NATIVE) {
+        const int n_tiles = (max_len + 63) / 64;
+        const dim3 grid(attn_grid(H, B, n_tiles));
+        hipLaunchKernelGGL(attn_bwd_dq_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
+        hipLaunchKernelGGL(attn_bwd_dkv_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
+    } else {
+        attn_bwd_x3_launch(mode, qkv, dout, lse, cu, B, max_len, n_total, H, scale, dqkv, delta_ws, s);
+    }
+    return check_launch(ATTN_BWD_LABEL[mode]);
+}
 
 }  // namespace u3d
 
@@ -333,40 +336,16 @@ using namespace u3d;
 
 extern "C" {
 
+// fp32 tensors; the default forms every product from three bf16 planes (attn_x3.hip), U3D_FP32_MATH=mfma runs the kernels above
 int u3d_attn_varlen_fwd(const float* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
                         float scale, float* out, float* lse, double flops_hint, u3d_stream_t stream) {
-    if (!qkv || !cu_seqlens || !out || !lse || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(U3D_K_ATTN_FWD, s, flops_hint);
-    if (max_len <= 0) return U3D_OK;
-    if (fp32_x3()) {                       // default: fp32 products from three bf16 planes (attn_x3.hip)
-        attn_fwd_x3_launch(qkv, cu_seqlens, B, max_len, n_total, H, scale, out, lse, s, 3);
-        return check_launch("attn_fwd_x3");
-    }
-    const int n_tiles = (max_len + 63) / 64;
-    hipLaunchKernelGGL(attn_fwd_k, dim3(attn_grid(H, B, n_tiles)), dim3(256), 0, s, qkv, cu_seqlens, H, scale, out, lse, n_total, B, n_tiles);
-    return check_launch("attn_fwd");
+    return attn_fwd(fp32_x3() ? ATTN_X3 : ATTN_NATIVE, qkv, cu_seqlens, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream);
 }
 
 int u3d_attn_varlen_bwd(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu_seqlens,
                         int B, int max_len, int64_t n_total, int H, int hd, float scale, float* dqkv, float* delta_ws,
                         double flops_hint, u3d_stream_t stream) {
-    if (!qkv || !out || !dout || !lse || !cu_seqlens || !dqkv || !delta_ws || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(U3D_K_ATTN_BWD, s, flops_hint);
-    if (max_len <= 0) return U3D_OK;
-    if (fp32_x3()) {
-        attn_bwd_x3_launch(qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, scale, dqkv, delta_ws, s, 3);
-        return check_launch("attn_bwd_x3");
-    }
-    hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)ceil_div(n_total * H, 256)), dim3(256), 0, s, out, dout, n_total, H, delta_ws);
-    const int n_tiles = (max_len + 63) / 64;
-    const dim3 grid(attn_grid(H, B, n_tiles));
-    hipLaunchKernelGGL(attn_bwd_dq_k, grid, dim3(256), 0, s, qkv, dout, lse, (const float*)delta_ws, cu_seqlens, H, scale, dqkv, n_total, B, n_tiles);
-    hipLaunchKernelGGL(attn_bwd_dkv_k, grid, dim3(256), 0, s, qkv, dout, lse, (const float*)delta_ws, cu_seqlens, H, scale, dqkv, n_total, B, n_tiles);
-    return check_launch("attn_bwd");
+    return attn_bwd(fp32_x3() ? ATTN_X3 : ATTN_NATIVE, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream);
 }
 
 }  // extern "C"

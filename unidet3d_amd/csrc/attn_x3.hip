@@ -22,11 +22,9 @@
 #include <mutex>
 #include <stdlib.h>
 
-#include "u3d_common.h"
+#include "attn_common.h"
 
 namespace u3d {
-
-typedef bf16x8_t bf16x8;
 
 constexpr float X_LOG2E = 1.44269504088896340736f, X_LN2 = 0.69314718055994530942f;
 constexpr int XLD = 32;                  // halves per row of a natural plane: unpadded, the 16-byte chunk index is XORed with (row >> 1) & 3
@@ -79,11 +77,10 @@ __device__ __forceinline__ void mfma_x3_2c(const bf16x8 (&a)[NP], const bf16x8 (
 
 // NP planes of a pair / of eight values: NP = 3 the exact split (u3d_common.h), NP = 1 one bf16 value rounded to nearest even
 // (bf16 operands, BASELINE configs[2])
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_r;
 template <int NP>
 __device__ __forceinline__ void planes_pair(float a, float b, unsigned (&w)[NP]) {
     if constexpr (NP == 3) split3_pair(a, b, w[0], w[1], w[2]);
-    else w[0] = __builtin_bit_cast(unsigned, bf16x2_r{(__bf16)a, (__bf16)b});
+    else w[0] = pack_bf16(a, b);
 }
 template <int NP>
 __device__ __forceinline__ void planes_x8(const f32x4& lo, const f32x4& hi, bf16x8 (&out)[NP]) {
@@ -191,29 +188,12 @@ __device__ __forceinline__ void nat_frag_x3(const __bf16* nat, int kb, int i16, 
 // natural planes read by COLUMN: dim 16 cb + i16 over rows {4g..4g+3} and {16+4g..16+4g+3} of the 32-row block t (the k order of
 // pair_frag_x3).  ds_read_b64_tr_b16: lane i16 of a 16-lane group passes the address of 4 halves -- row (i16 >> 2) of the group's four,
 // dims 16 cb + 4 (i16 & 3) .. -- and receives dim 16 cb + i16 of the four rows.
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 template <int NP>
 __device__ __forceinline__ void tr_col_frag_x3(const __bf16* nat, int t, int g, int i16, int cb, bf16x8 (&out)[NP]) {
     const int row = 32 * t + 4 * g + (i16 >> 2), pc = i16 & 3;
     const __bf16* s = nat + row * XLD + (((2 * cb + (pc >> 1)) ^ ((row >> 1) & 3)) * 8) + 4 * (pc & 1);      // row + 16 has the same chunk XOR
 #pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const s16x4_t r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(s + q * XN));
-        const s16x4_t r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(s + q * XN + 16 * XLD));
-        out[q] = __builtin_bit_cast(bf16x8, s16x8_t{r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]});
-    }
-}
-
-struct AttnWorkX { int b, h, tile; };
-__device__ __forceinline__ AttnWorkX attn_decode_x(int H, int B, int n_tiles) {      // (scene, head) -> XCD, see attn.hip
-    const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int hb = (j / n_tiles) * 8 + x;
-    AttnWorkX w;
-    w.tile = j % n_tiles;
-    w.h = hb % H;
-    w.b = hb / H;
-    return w;
+    for (int q = 0; q < NP; ++q) out[q] = tr16_pair(s + q * XN, s + q * XN + 16 * XLD);
 }
 
 template <int NP, bool IO16 = false>
@@ -223,7 +203,7 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const typename IoT<IO16>::t
     typedef typename IoT<IO16>::t io_t;
     __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN];
     __shared__ __attribute__((aligned(16))) __bf16 Vn[NP * XN];
-    const AttnWorkX wk_ = attn_decode_x(H, B, n_tiles);
+    const AttnWork wk_ = attn_decode(H, B, n_tiles);
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
@@ -326,41 +306,6 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const typename IoT<IO16>::t
     if (g == 0 && qrow < len) lse[(int64_t)h * n_total + start + qrow] = m * X_LN2 + __logf(l);      // natural-log units
 }
 
-__global__ __launch_bounds__(256) void attn_delta_x16_k(const __bf16* __restrict__ o, const __bf16* __restrict__ dout, int64_t n, int H, float* delta) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * H) return;
-    const int64_t i = idx / H;
-    const int h = (int)(idx % H);
-    const u32x4* a = reinterpret_cast<const u32x4*>(o + i * H * 32 + h * 32);
-    const u32x4* b = reinterpret_cast<const u32x4*>(dout + i * H * 32 + h * 32);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const u32x4 x = a[j], y = b[j];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            s += __builtin_bit_cast(float, x[c] << 16) * __builtin_bit_cast(float, y[c] << 16) +
-                 __builtin_bit_cast(float, x[c] & 0xffff0000u) * __builtin_bit_cast(float, y[c] & 0xffff0000u);
-    }
-    delta[(int64_t)h * n + i] = s;
-}
-
-__global__ __launch_bounds__(256) void attn_delta_x3_k(const float* __restrict__ o, const float* __restrict__ dout, int64_t n, int H, float* delta) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * H) return;
-    const int64_t i = idx / H;
-    const int h = (int)(idx % H);
-    const float4* a = reinterpret_cast<const float4*>(o + i * H * 32 + h * 32);
-    const float4* b = reinterpret_cast<const float4*>(dout + i * H * 32 + h * 32);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float4 x = a[j], y = b[j];
-        s += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    delta[(int64_t)h * n + i] = s;
-}
-
 // dQ: one workgroup per 64-query tile, keys streamed.  K is read by rows for S and by columns for dQ += dS . K.
 template <int NP, bool IO16 = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const typename IoT<IO16>::t* __restrict__ qkv, const typename IoT<IO16>::t* __restrict__ dout, const float* __restrict__ lse,
@@ -370,7 +315,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const typename IoT<IO16>
     typedef typename IoT<IO16>::t io_t;
     __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN];
     __shared__ __attribute__((aligned(16))) __bf16 Vn[NP * XN];
-    const AttnWorkX wk_ = attn_decode_x(H, B, n_tiles);
+    const AttnWork wk_ = attn_decode(H, B, n_tiles);
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
@@ -454,7 +399,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3
     __shared__ __attribute__((aligned(16))) __bf16 Qn[NP * XN];
     __shared__ __attribute__((aligned(16))) __bf16 On[NP * XN];
     __shared__ float lse_s[64], del_s[64];
-    const AttnWorkX wk_ = attn_decode_x(H, B, n_tiles);
+    const AttnWork wk_ = attn_decode(H, B, n_tiles);
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
@@ -537,14 +482,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3
     }
 }
 
-// launchers, called from attn.hip's entry points when fp32_x3() (arguments already validated there)
-void attn_fwd_x3_launch(const float* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, float scale, float* out, float* lse,
-                        hipStream_t s, int planes) {
+// launchers, called from attn.hip's attn_fwd / attn_bwd for every mode but ATTN_NATIVE (arguments already validated there)
+void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, float scale, void* out,
+                        float* lse, hipStream_t s) {
     const int n_tiles = (max_len + 63) / 64;
-    const unsigned grid = (unsigned)(((H * B + 7) / 8) * 8 * n_tiles);
-    if (planes == 16) hipLaunchKernelGGL((attn_fwd_x3_k<1, true>), dim3(grid), dim3(256), 0, s, (const __bf16*)qkv, cu, H, scale, (__bf16*)out, lse, n_total, B, n_tiles);      // bf16 tensors
-    else if (planes == 1) hipLaunchKernelGGL((attn_fwd_x3_k<1>), dim3(grid), dim3(256), 0, s, qkv, cu, H, scale, out, lse, n_total, B, n_tiles);
-    else hipLaunchKernelGGL((attn_fwd_x3_k<3>), dim3(grid), dim3(256), 0, s, qkv, cu, H, scale, out, lse, n_total, B, n_tiles);
+    const dim3 grid(attn_grid(H, B, n_tiles));
+    if (mode == ATTN_B16) hipLaunchKernelGGL((attn_fwd_x3_k<1, true>), grid, dim3(256), 0, s, (const __bf16*)qkv, cu, H, scale, (__bf16*)out, lse, n_total, B, n_tiles);
+    else if (mode == ATTN_BF16_OPS) hipLaunchKernelGGL((attn_fwd_x3_k<1>), grid, dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
+    else hipLaunchKernelGGL((attn_fwd_x3_k<3>), grid, dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
 }
 
 // dQ and dK / dV are independent given delta: with U3D_ATTN_FORK=1 the dQ kernel is forked onto a per-device side stream and joined
@@ -563,7 +508,8 @@ static AttnFork* attn_fork_of_device() {
     if (!on) return nullptr;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    AttnFork& f = forks[dev & 63];
+    if ((unsigned)dev >= 64u) return nullptr;        // as DeviceOnce: an ordinal past the table gets no fork instead of another device's
+    AttnFork& f = forks[dev];
     std::lock_guard<std::mutex> lk(mu);
     if (!f.side) {
         if (hipStreamCreateWithFlags(&f.side, hipStreamNonBlocking) != hipSuccess) { f.side = nullptr; return nullptr; }
@@ -573,12 +519,10 @@ static AttnFork* attn_fork_of_device() {
     return &f;
 }
 
-void attn_bwd_x3_launch(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu, int B, int max_len,
-                        int64_t n_total, int H, float scale, float* dqkv, float* delta_ws, hipStream_t s, int planes) {
-    if (planes == 16) hipLaunchKernelGGL(attn_delta_x16_k, dim3((unsigned)ceil_div(n_total * H, 256)), dim3(256), 0, s, (const __bf16*)out, (const __bf16*)dout, n_total, H, delta_ws);
-    else hipLaunchKernelGGL(attn_delta_x3_k, dim3((unsigned)ceil_div(n_total * H, 256)), dim3(256), 0, s, out, dout, n_total, H, delta_ws);
+void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
+                        int64_t n_total, int H, float scale, void* dqkv, const float* delta, hipStream_t s) {
     const int n_tiles = (max_len + 63) / 64;
-    const dim3 grid((unsigned)(((H * B + 7) / 8) * 8 * n_tiles));
+    const dim3 grid(attn_grid(H, B, n_tiles));
     AttnFork* f = attn_fork_of_device();
     hipStream_t sq = s;
     if (f) {
@@ -586,15 +530,15 @@ void attn_bwd_x3_launch(const float* qkv, const float* out, const float* dout, c
         hipStreamWaitEvent(f->side, f->fork, 0);
         sq = f->side;
     }
-    if (planes == 16) {
-        hipLaunchKernelGGL((attn_bwd_dq_x3_k<1, true>), grid, dim3(256), 0, sq, (const __bf16*)qkv, (const __bf16*)dout, lse, (const float*)delta_ws, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
-        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<1, true>), grid, dim3(256), 0, s, (const __bf16*)qkv, (const __bf16*)dout, lse, (const float*)delta_ws, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
-    } else if (planes == 1) {
-        hipLaunchKernelGGL((attn_bwd_dq_x3_k<1>), grid, dim3(256), 0, sq, qkv, dout, lse, (const float*)delta_ws, cu, H, scale, dqkv, n_total, B, n_tiles);
-        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<1>), grid, dim3(256), 0, s, qkv, dout, lse, (const float*)delta_ws, cu, H, scale, dqkv, n_total, B, n_tiles);
+    if (mode == ATTN_B16) {
+        hipLaunchKernelGGL((attn_bwd_dq_x3_k<1, true>), grid, dim3(256), 0, sq, (const __bf16*)qkv, (const __bf16*)dout, lse, delta, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
+        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<1, true>), grid, dim3(256), 0, s, (const __bf16*)qkv, (const __bf16*)dout, lse, delta, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
+    } else if (mode == ATTN_BF16_OPS) {
+        hipLaunchKernelGGL((attn_bwd_dq_x3_k<1>), grid, dim3(256), 0, sq, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
+        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<1>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
     } else {
-        hipLaunchKernelGGL((attn_bwd_dq_x3_k<3>), grid, dim3(256), 0, sq, qkv, dout, lse, (const float*)delta_ws, cu, H, scale, dqkv, n_total, B, n_tiles);
-        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<3>), grid, dim3(256), 0, s, qkv, dout, lse, (const float*)delta_ws, cu, H, scale, dqkv, n_total, B, n_tiles);
+        hipLaunchKernelGGL((attn_bwd_dq_x3_k<3>), grid, dim3(256), 0, sq, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
+        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<3>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
     }
     if (f) {
         hipEventRecord(f->join, f->side);
@@ -613,50 +557,26 @@ extern "C" {
 // fp32 in HBM, accumulation and softmax stay fp32.
 int u3d_attn_varlen_fwd_bf16(const float* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
                              float scale, float* out, float* lse, double flops_hint, u3d_stream_t stream) {
-    if (!qkv || !cu_seqlens || !out || !lse || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(U3D_K_ATTN_FWD, s, flops_hint);
-    if (max_len <= 0) return U3D_OK;
-    attn_fwd_x3_launch(qkv, cu_seqlens, B, max_len, n_total, H, scale, out, lse, s, 1);
-    return check_launch("attn_fwd_bf16");
+    return attn_fwd(ATTN_BF16_OPS, qkv, cu_seqlens, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream);
 }
 
 int u3d_attn_varlen_bwd_bf16(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu_seqlens,
                              int B, int max_len, int64_t n_total, int H, int hd, float scale, float* dqkv, float* delta_ws,
                              double flops_hint, u3d_stream_t stream) {
-    if (!qkv || !out || !dout || !lse || !cu_seqlens || !dqkv || !delta_ws || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(U3D_K_ATTN_BWD, s, flops_hint);
-    if (max_len <= 0) return U3D_OK;
-    attn_bwd_x3_launch(qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, scale, dqkv, delta_ws, s, 1);
-    return check_launch("attn_bwd_bf16");
+    return attn_bwd(ATTN_BF16_OPS, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream);
 }
 
 // bf16 TENSORS (include/u3d.h K14b): qkv / out / dout / dqkv are bf16 in HBM -- what the reference's autocast hands to and takes from
 // nn.MultiheadAttention (tools/train.py:86-99, unidet3d/encoder.py:19-21); lse / delta, softmax and all accumulators fp32.
 int u3d_attn_varlen_fwd_b16(const void* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
                             float scale, void* out, float* lse, double flops_hint, u3d_stream_t stream) {
-    if (!qkv || !cu_seqlens || !out || !lse || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(U3D_K_ATTN_FWD, s, flops_hint);
-    if (max_len <= 0) return U3D_OK;
-    attn_fwd_x3_launch((const float*)qkv, cu_seqlens, B, max_len, n_total, H, scale, (float*)out, lse, s, 16);
-    return check_launch("attn_fwd_b16");
+    return attn_fwd(ATTN_B16, qkv, cu_seqlens, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream);
 }
 
 int u3d_attn_varlen_bwd_b16(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu_seqlens,
                             int B, int max_len, int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws,
                             double flops_hint, u3d_stream_t stream) {
-    if (!qkv || !out || !dout || !lse || !cu_seqlens || !dqkv || !delta_ws || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(U3D_K_ATTN_BWD, s, flops_hint);
-    if (max_len <= 0) return U3D_OK;
-    attn_bwd_x3_launch((const float*)qkv, (const float*)out, (const float*)dout, lse, cu_seqlens, B, max_len, n_total, H, scale, (float*)dqkv, delta_ws, s, 16);
-    return check_launch("attn_bwd_b16");
+    return attn_bwd(ATTN_B16, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream);
 }
 
 }  // extern "C"

@@ -211,10 +211,9 @@ __global__ void bn_finalize_k(const double* __restrict__ sums, double count, con
 // 16 + 4q .. 16 + 4q + 3 -- the eight reduction elements lane group q of v_mfma_f32_16x16x32_bf16 takes in the fp32-row kernels
 // (spconv.hip: k = 8q + e <-> channel 16 (e >> 2) + 4q + (e & 3)), so both kinds of kernel multiply the same operands in the same
 // k slots, share the packed weights, and return identical bits.
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
 __device__ __forceinline__ void store_shadow(__bf16* dst, int64_t row, int c4, int C4, const float4& o) {
     const int g32 = c4 >> 3, half = (c4 >> 2) & 1, q = c4 & 3;          // channels 4 c4 .. 4 c4 + 3 = group g32, 16-channel half, quad q
-    reinterpret_cast<bf16x4_t*>(dst)[row * C4 + g32 * 8 + q * 2 + half] = bf16x4_t{(__bf16)o.x, (__bf16)o.y, (__bf16)o.z, (__bf16)o.w};
+    reinterpret_cast<bf16x4*>(dst)[row * C4 + g32 * 8 + q * 2 + half] = bf16x4{(__bf16)o.x, (__bf16)o.y, (__bf16)o.z, (__bf16)o.w};
 }
 
 __global__ __launch_bounds__(256) void bn_apply_k(const float* __restrict__ x, const float* __restrict__ scale,

@@ -1,5 +1,6 @@
 """Build libu3d_hip.so (gfx950) in-tree with hipcc.  `python -m unidet3d_amd.csrc.build`."""
 import concurrent.futures as cf
+import glob
 import os
 import subprocess
 import sys
@@ -31,36 +32,66 @@ def _hipcc():
     return 'hipcc'
 
 
+def command(source, extra=(), out=None, kind='-c'):
+    """THE hipcc command line of one source file of the library: FLAGS, the file's EXTRA, then the caller's `extra` flags.
+    `kind` is the output kind (['-c'] object, ['--offload-device-only', '-S'] device assembly, ...); build(), variant
+    libraries (`--variant`, tools/build_variant.sh) and ISA comparisons all compile through this one function."""
+    kind = [kind] if isinstance(kind, str) else list(kind)
+    out = out or os.path.join(HERE, source.replace('.hip', '.o'))
+    return [_hipcc(), *FLAGS, *EXTRA.get(source, []), *extra, *kind, os.path.join(HERE, source), '-o', out]
+
+
+def _deps(src):
+    return [src, *glob.glob(os.path.join(HERE, '*.h')), os.path.join(ROOT, 'include', 'u3d.h'), __file__]
+
+
 def _stale(src, obj):
-    if not os.path.exists(obj):
-        return True
-    deps = [src, os.path.join(HERE, 'u3d_common.h'), os.path.join(HERE, 'spconv_gmm.h'), os.path.join(ROOT, 'include', 'u3d.h'), __file__]
-    return any(os.path.getmtime(d) > os.path.getmtime(obj) for d in deps)
+    return not os.path.exists(obj) or any(os.path.getmtime(d) > os.path.getmtime(obj) for d in _deps(src))
+
+
+def _compile(jobs, verbose=True):
+    with cf.ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
+        for cmd, res in zip(jobs, ex.map(lambda c: subprocess.run(c, capture_output=True, text=True), jobs)):
+            if verbose and (res.stdout or res.stderr):
+                sys.stderr.write(res.stdout + res.stderr)
+            if res.returncode != 0:
+                raise RuntimeError('hipcc failed: ' + ' '.join(cmd))
+
+
+def _link(lib, objs):
+    res = subprocess.run([_hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib, *objs], capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError('link failed: ' + res.stdout + res.stderr)
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    hipcc = _hipcc()
     objs, jobs = [], []
     for s in SOURCES:
-        src = os.path.join(HERE, s)
         obj = os.path.join(HERE, s.replace('.hip', '.o'))
         objs.append(obj)
-        if force or _stale(src, obj):
-            jobs.append([hipcc, *FLAGS, *EXTRA.get(s, []), '-c', src, '-o', obj])
+        if force or _stale(os.path.join(HERE, s), obj):
+            jobs.append(command(s))
     if jobs:
-        with cf.ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
-            for cmd, res in zip(jobs, ex.map(lambda c: subprocess.run(c, capture_output=True, text=True), jobs)):
-                if verbose and (res.stdout or res.stderr):
-                    sys.stderr.write(res.stdout + res.stderr)
-                if res.returncode != 0:
-                    raise RuntimeError('hipcc failed: ' + ' '.join(cmd))
+        _compile(jobs, verbose)
     if jobs or not os.path.exists(LIB):
-        res = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB, *objs],
-                             capture_output=True, text=True)
-        if res.returncode != 0:
-            raise RuntimeError('link failed: ' + res.stdout + res.stderr)
+        _link(LIB, objs)
     return LIB
 
 
+def build_variant(out, sources, extra, tmp):
+    """A/B library: `sources` recompiled into `tmp` with the `extra` flags, every other object from the in-tree build."""
+    build(verbose=False)
+    redo = {s: os.path.join(tmp, s.replace('.hip', '.o')) for s in sources}
+    _compile([command(s, extra, o) for s, o in redo.items()])
+    _link(out, [redo.get(s, os.path.join(HERE, s.replace('.hip', '.o'))) for s in SOURCES])
+    return out
+
+
 if __name__ == '__main__':
-    print(build(force='--force' in sys.argv))
+    if '--variant' in sys.argv:         # --variant <out.so> <file.hip[,file2.hip...]> <extra hipcc flags...>
+        import tempfile
+        a = sys.argv[sys.argv.index('--variant') + 1:]
+        with tempfile.TemporaryDirectory() as tmp:
+            print(build_variant(a[0], a[1].split(','), a[2:], tmp))
+    else:
+        print(build(force='--force' in sys.argv))

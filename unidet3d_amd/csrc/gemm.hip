@@ -15,8 +15,6 @@
 
 namespace u3d {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define U3D_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 constexpr int GT = 128;        // macro tile (both dims)
@@ -38,20 +36,7 @@ constexpr int GLD = GK + 4;    // padded LDS row of the NT tiles
 //   3  C = aux > 0 ? acc : 0                            input gradient through ReLU   (aux = the ReLU output)
 //   4  C = acc * gelu'(aux)                             input gradient through GELU   (aux = the pre-activation)
 //   5  C = acc + aux                                    a second gradient contribution added in place of a separate add kernel
-// erf GELU with ONE exponential per element: erf(z) = 1 - (a1 t + ... + a5 t^5) exp(-z^2), t = 1 / (1 + p z), z = |x| / sqrt 2
-// (Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below fp32 resolution of the products it enters), and exp(-z^2) =
-// exp(-x^2 / 2) is also the Gaussian of the derivative.  libm's erff costs ~3x the VALU instructions, and VALU time in a
-// GEMM epilogue is not hidden (one wave per SIMD): measured +95 us on the [16k x 1024] hidden-gradient GEMM with erff.
-__device__ __forceinline__ void gelu_parts(float x, float& cdf, float& pdf) {
-    const float ax = fabsf(x), e = __expf(-0.5f * x * x);
-    const float t = __frcp_rn(1.f + 0.3275911f * 0.70710678118654752440f * ax);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float tail = 0.5f * poly * e;                     // 0.5 * erfc(|x| / sqrt 2): Phi(-|x|) without cancellation
-    cdf = x >= 0.f ? 1.f - tail : tail;
-    pdf = 0.39894228040143267794f * e;
-}
-__device__ __forceinline__ float gelu_f(float x) { float c, p; gelu_parts(x, c, p); return x * c; }
-__device__ __forceinline__ float gelu_grad_f(float x) { float c, p; gelu_parts(x, c, p); return c + x * p; }
+// The erf GELU (gelu_f, gelu_grad_f) is u3d_common.h's.
 
 // Shared epilogue of the NT kernels.  D layout of 32x32 MFMAs (dtype independent): col = lane & 31,
 // row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
@@ -575,8 +560,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TA == 128 ?
     __shared__ __attribute__((aligned(16))) __bf16 As[3 * PA];
     __shared__ __attribute__((aligned(16))) __bf16 Bs[3 * PB];
     __shared__ float csum_s[RPA][TA];
-    typedef __attribute__((ext_vector_type(4))) short s16x4;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     const int tiles_n = (N + TA - 1) / TA, tiles = tiles_n * ((K + TB - 1) / TB);
     const int slot = blockIdx.x >> 3, tile = slot % tiles;                     // XCD placement as in gemm_tn_k
     const int split = (slot / tiles) * 8 + (blockIdx.x & 7);
@@ -621,9 +604,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TA == 128 ?
     // column blk * 16 + t16 of a plane tile over rows {4g .. 4g+3} and {16+4g .. 16+4g+3}
     auto frag = [&](const __bf16* tile, int L, int blk) -> bf16x8 {
         const __bf16* s0 = tile + (4 * g + (t16 >> 2)) * L + blk * 16 + 4 * (t16 & 3);
-        const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)s0);
-        const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(s0 + 16 * L));
-        return __builtin_bit_cast(bf16x8, s16x8{r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]});
+        return tr16_pair(s0, s0 + 16 * L);
     };
     f32x4 acc[NA][NB], lo[NA][NB];
 #pragma unroll
@@ -709,7 +690,6 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_k(const float* __restrict__ 
     __shared__ __attribute__((aligned(16))) __bf16 As[2][TKH * TLH];
     __shared__ __attribute__((aligned(16))) __bf16 Bs[2][TKH * TLH];
     __shared__ float csum_s[8][GT];
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1, i32 = lane & 31, kh = lane >> 5;
@@ -741,14 +721,10 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_k(const float* __restrict__ 
             *reinterpret_cast<bf16x4*>(&Bs[buf][(srow + 8 * j) * TLH + sc4 * 4]) = bf16x4{(__bf16)rb[j][0], (__bf16)rb[j][1], (__bf16)rb[j][2], (__bf16)rb[j][3]};
         }
     };
-    typedef __attribute__((ext_vector_type(4))) short s16x4;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     const int troff = ((lane & 15) >> 2) * TLH + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);      // this lane's 8 bytes of its group's [4 rows][16 cols] block
     auto colfrag = [&](const __bf16* t, int row0, int col32) {       // column col32 + i32 over rows row0 .. row0 + 7
         const __bf16* p = t + row0 * TLH + col32 + troff;
-        const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-        const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + 4 * TLH));
-        return __builtin_bit_cast(bf16x8, s16x8{r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]});
+        return tr16_pair(p, p + 4 * TLH);
     };
     f32x16 acc[2][2];
 #pragma unroll

@@ -18,27 +18,9 @@
 
 namespace u3d {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
 constexpr int HT = 128;        // macro tile
 constexpr int HK = 32;         // K-step
 constexpr int HL = HK + 8;     // padded LDS row of the NT tiles (halves): 80-byte rows, conflict-free 16-byte reads of 32 rows
-
-__device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return __builtin_bit_cast(unsigned, bf16x2{(__bf16)lo, (__bf16)hi}); }
-
-// erf GELU with one exponential (gemm.hip gelu_parts: Abramowitz-Stegun 7.1.26)
-__device__ __forceinline__ void gelu_parts16(float x, float& cdf, float& pdf) {
-    const float ax = fabsf(x), e = __expf(-0.5f * x * x);
-    const float t = __frcp_rn(1.f + 0.3275911f * 0.70710678118654752440f * ax);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float tail = 0.5f * poly * e;
-    cdf = x >= 0.f ? 1.f - tail : tail;
-    pdf = 0.39894228040143267794f * e;
-}
 
 #ifndef U3D_NT16_ABL
 #define U3D_NT16_ABL 0          // timing ablations (wrong results): 1 no result stores, 2 no MFMAs, 4 no global loads in the loop, 8 no LDS stores in the loop
@@ -293,14 +275,10 @@ __global__ __launch_bounds__(256) void gemm_tn_b16_k(const void* __restrict__ A_
             else *reinterpret_cast<bf16x4*>(&Bs[buf][(srow + 8 * j) * WLH + sc4 * 4]) = sb32[j];
         }
     };
-    typedef __attribute__((ext_vector_type(4))) short s16x4;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     const int troff = ((lane & 15) >> 2) * WLH + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);      // this lane's 8 bytes of its group's [4 rows][16 cols] block
     auto colfrag = [&](const __bf16* t, int row0, int col32) {       // column col32 + i32 over rows row0 .. row0 + 7
         const __bf16* p = t + row0 * WLH + col32 + troff;
-        const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-        const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + 4 * WLH));
-        return __builtin_bit_cast(bf16x8, s16x8{r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]});
+        return tr16_pair(p, p + 4 * WLH);
     };
     f32x16 acc[2][2];
 #pragma unroll
@@ -418,8 +396,8 @@ __global__ __launch_bounds__(256) void gelu_fwd_b16_k(const u32x4* __restrict__ 
         for (int c = 0; c < 4; ++c) {
             const float x0 = __builtin_bit_cast(float, v[c] << 16), x1 = __builtin_bit_cast(float, v[c] & 0xffff0000u);
             float c0, p0, c1, p1;
-            gelu_parts16(x0, c0, p0);
-            gelu_parts16(x1, c1, p1);
+            gelu_parts(x0, c0, p0);
+            gelu_parts(x1, c1, p1);
             o[c] = pack_bf16(x0 * c0, x1 * c1);
         }
         a[i] = o;
@@ -434,8 +412,8 @@ __global__ __launch_bounds__(256) void gelu_bwd_b16_k(const u32x4* __restrict__ 
             const float x0 = __builtin_bit_cast(float, v[c] << 16), x1 = __builtin_bit_cast(float, v[c] & 0xffff0000u);
             const float g0 = __builtin_bit_cast(float, g[c] << 16), g1 = __builtin_bit_cast(float, g[c] & 0xffff0000u);
             float c0, p0, c1, p1;
-            gelu_parts16(x0, c0, p0);
-            gelu_parts16(x1, c1, p1);
+            gelu_parts(x0, c0, p0);
+            gelu_parts(x1, c1, p1);
             o[c] = pack_bf16(g0 * (c0 + x0 * p0), g1 * (c1 + x1 * p1));
         }
         dh[i] = o;

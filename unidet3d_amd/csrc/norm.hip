@@ -11,9 +11,6 @@ namespace u3d {
 
 constexpr int LN_MAXV = 4;       // float4 per lane: C <= 1024
 
-typedef __attribute__((ext_vector_type(2))) __bf16 ln_bf16x2;
-__device__ __forceinline__ unsigned ln_pack_bf16(float lo, float hi) { return __builtin_bit_cast(unsigned, ln_bf16x2{(__bf16)lo, (__bf16)hi}); }
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -62,7 +59,7 @@ __global__ __launch_bounds__(256) void layer_norm_fwd_k(const float* __restrict_
             o.x = (v[i].x - mean) * rstd * g.x + b.x; o.y = (v[i].y - mean) * rstd * g.y + b.y;
             o.z = (v[i].z - mean) * rstd * g.z + b.z; o.w = (v[i].w - mean) * rstd * g.w + b.w;
             reinterpret_cast<float4*>(y + row * C)[j] = o;
-            if (y16) y16[row * c4 + j] = make_uint2(ln_pack_bf16(o.x, o.y), ln_pack_bf16(o.z, o.w));      // the copy the next GEMM streams (K14b)
+            if (y16) y16[row * c4 + j] = make_uint2(pack_bf16(o.x, o.y), pack_bf16(o.z, o.w));      // the copy the next GEMM streams (K14b)
         }
     }
     if (lane == 0) { stats[row * 2] = mean; stats[row * 2 + 1] = rstd; }
@@ -120,7 +117,7 @@ __global__ __launch_bounds__(256) void layer_norm_bwd_k(const float* __restrict_
                 const float4 o = make_float4(rstd * (g[i].x - mg - xh[i].x * mgx), rstd * (g[i].y - mg - xh[i].y * mgx),
                                              rstd * (g[i].z - mg - xh[i].z * mgx), rstd * (g[i].w - mg - xh[i].w * mgx));
                 reinterpret_cast<float4*>(dx + row * C)[j] = o;
-                if (dx16) dx16[row * c4 + j] = make_uint2(ln_pack_bf16(o.x, o.y), ln_pack_bf16(o.z, o.w));
+                if (dx16) dx16[row * c4 + j] = make_uint2(pack_bf16(o.x, o.y), pack_bf16(o.z, o.w));
             }
         }
     }

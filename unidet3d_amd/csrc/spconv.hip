@@ -71,7 +71,6 @@ struct GmmItem {
     bool valid;
 };
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 // BF: bf16 MFMA operands (BASELINE configs[2], "MFMA bf16 on rule GEMM").  Rows are gathered as fp32 exactly as below and
 // rounded to bf16 (RNE) only when the MFMA operand is formed: two 16-channel pieces of a unit make one
@@ -876,18 +875,22 @@ static int launch_wgrad(const WgParams& p0, float* dW, hipStream_t s) {
     return check_launch("spconv_wgrad");
 }
 
-// wp[(((slice*K + k)*CS16 + j)*2 + nb)*256 + lane*4 + t] = W(n = slice*32 + nb*16 + (lane&15), k, c = j*16 + (lane>>4)*4 + t)
-// i.e. the B fragments of spconv_gmm_k in the order the kernel reads them (one contiguous 1 KB block per wave load).
+// Packed weights, three layouts (format 0 fp32, 1 bf16, 2 x3).  Each layout's thread-to-element map is written ONCE, as a function
+// of (src, dst, idx = the thread's vector, Cd, K, Cs, transposed) that guards idx itself; the single-weight kernels (tests, cache
+// misses) and the batch kernel (every step) call the same three functions.
 // transposed = 0: W(n,k,c) = w[(n*K + k)*Cs + c]  (forward, w = [Cd][K][Cs]);
 // transposed = 1: W(n,k,c) = w[(c*K + k)*Cd + n]  (input gradient: w = [Cs][K][Cd] is the forward weight).
-__global__ __launch_bounds__(256) void weight_pack_k(const float* __restrict__ w, float* __restrict__ wp, int Cd, int K, int Cs, int transposed) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // one float4 per thread
-    const int cs16 = Cs / 16;
-    const int64_t total = (int64_t)(Cd / 32) * K * cs16 * 2 * 64;
-    if (idx >= total) return;
+// vectors (= threads) of a layout: one float4 per (lane, 16-channel group j, column block nb), one bf16x8 (x3: three) per 32-channel group jj
+static inline int64_t weight_pack_vectors(int format, int Cd, int K, int Cs) { return (int64_t)(Cd / 32) * K * (Cs / (format ? 32 : 16)) * 2 * 64; }
+
+// fp32: wp[(((slice*K + k)*CS16 + j)*2 + nb)*256 + lane*4 + t] = W(n = slice*32 + nb*16 + (lane&15), k, c = j*16 + (lane>>4)*4 + t)
+// i.e. the B fragments of spconv_gmm_k in the order the kernel reads them (one contiguous 1 KB block per wave load).
+__device__ __forceinline__ void weight_f32_vector(const float* __restrict__ w, float* __restrict__ wp, int64_t idx, int Cd, int K, int Cs, int transposed) {
     const int lane = (int)(idx & 63);
     int64_t t = idx >> 6;
     const int nb = (int)(t & 1); t >>= 1;
+    const int cs16 = Cs / 16;
+    if (idx >= (int64_t)(Cd / 32) * K * cs16 * 2 * 64) return;
     const int j = (int)(t % cs16); t /= cs16;
     const int k = (int)(t % K);
     const int slice = (int)(t / K);
@@ -904,16 +907,14 @@ __global__ __launch_bounds__(256) void weight_pack_k(const float* __restrict__ w
     reinterpret_cast<float4*>(wp)[idx] = v;
 }
 
-// bf16 form: one 16-byte vector (8 bf16) per (lane, 32-channel group jj, column block nb):
+// bf16: one 16-byte vector (8 bf16) per (lane, 32-channel group jj, column block nb):
 // wp[(((slice*K + k)*CS32 + jj)*2 + nb)*64 + lane][e] = bf16(W(n = slice*32 + nb*16 + (lane&15), k, c = (2 jj + (e>>2))*16 + (lane>>4)*4 + (e&3)))
-__global__ __launch_bounds__(256) void weight_pack_bf16_k(const float* __restrict__ w, bf16x8* __restrict__ wp, int Cd, int K, int Cs, int transposed) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // one bf16x8 per thread
-    const int cs32 = Cs / 32;
-    const int64_t total = (int64_t)(Cd / 32) * K * cs32 * 2 * 64;
-    if (idx >= total) return;
+__device__ __forceinline__ void weight_bf16_vector(const float* __restrict__ w, bf16x8* __restrict__ wp, int64_t idx, int Cd, int K, int Cs, int transposed) {
     const int lane = (int)(idx & 63);
     int64_t t = idx >> 6;
     const int nb = (int)(t & 1); t >>= 1;
+    const int cs32 = Cs / 32;
+    if (idx >= (int64_t)(Cd / 32) * K * cs32 * 2 * 64) return;
     const int jj = (int)(t % cs32); t /= cs32;
     const int k = (int)(t % K);
     const int slice = (int)(t / K);
@@ -927,9 +928,10 @@ __global__ __launch_bounds__(256) void weight_pack_bf16_k(const float* __restric
     wp[idx] = v;
 }
 
-// x3 form (u3d_common.h "bf16x3"): the bf16 form's vectors, three planes per (lane, 32-channel group jj, column block nb):
+// x3 (u3d_common.h "bf16x3"): the bf16 layout's vectors, three planes per (lane, 32-channel group jj, column block nb):
 // wp[((((slice*K + k)*CS32 + jj)*2 + nb)*3 + plane)*64 + lane][e] = plane `plane` of the exact split of the same W element
 __device__ __forceinline__ void weight_x3_vectors(const float* __restrict__ w, bf16x8* __restrict__ wp, int64_t idx, int Cd, int K, int Cs, int transposed) {
+    if (idx >= (int64_t)(Cd / 32) * K * (Cs / 32) * 2 * 64) return;
     const int cs32 = Cs / 32;
     const int lane = (int)(idx & 63);
     int64_t t = idx >> 6;
@@ -950,10 +952,15 @@ __device__ __forceinline__ void weight_x3_vectors(const float* __restrict__ w, b
 #pragma unroll
     for (int pq = 0; pq < 3; ++pq) wp[o + pq * 64] = pl[pq];
 }
-__global__ __launch_bounds__(256) void weight_pack_x3_k(const float* __restrict__ w, bf16x8* __restrict__ wp, int Cd, int K, int Cs, int transposed) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // one (lane, jj, nb) triple of vectors per thread
-    if (idx >= (int64_t)(Cd / 32) * K * (Cs / 32) * 2 * 64) return;
-    weight_x3_vectors(w, wp, idx, Cd, K, Cs, transposed);
+__device__ __forceinline__ void weight_pack_vector(int64_t format, const float* w, void* wp, int64_t idx, int Cd, int K, int Cs, int transposed) {
+    if (format == 2) weight_x3_vectors(w, reinterpret_cast<bf16x8*>(wp), idx, Cd, K, Cs, transposed);
+    else if (format) weight_bf16_vector(w, reinterpret_cast<bf16x8*>(wp), idx, Cd, K, Cs, transposed);
+    else weight_f32_vector(w, reinterpret_cast<float*>(wp), idx, Cd, K, Cs, transposed);
+}
+
+template <int FORMAT>        // one weight: tests and cache misses
+__global__ __launch_bounds__(256) void weight_pack_k(const float* __restrict__ w, void* __restrict__ wp, int Cd, int K, int Cs, int transposed) {
+    weight_pack_vector(FORMAT, w, wp, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, Cd, K, Cs, transposed);
 }
 
 // every convolution weight of the model, both orientations, in ONE launch (the weights change once per optimizer step; 89 single
@@ -967,44 +974,7 @@ __global__ __launch_bounds__(256) void weight_pack_batch_k(const PackDesc* __res
         if (desc[mid].block0 <= (int64_t)blockIdx.x) lo = mid; else hi = mid;
     }
     const PackDesc d = desc[lo];
-    const int64_t idx = ((int64_t)blockIdx.x - d.block0) * 256 + threadIdx.x;
-    const int Cd = (int)d.Cd, K = (int)d.K, Cs = (int)d.Cs;
-    const int lane = (int)(idx & 63);
-    int64_t t = idx >> 6;
-    const int nb = (int)(t & 1); t >>= 1;
-    if (d.bf == 2) {
-        if (idx >= (int64_t)(Cd / 32) * K * (Cs / 32) * 2 * 64) return;
-        weight_x3_vectors(d.src, reinterpret_cast<bf16x8*>(d.dst), idx, Cd, K, Cs, (int)d.transposed);
-    } else if (d.bf) {
-        const int cs32 = Cs / 32;
-        if (idx >= (int64_t)(Cd / 32) * K * cs32 * 2 * 64) return;
-        const int jj = (int)(t % cs32); t /= cs32;
-        const int k = (int)(t % K), slice = (int)(t / K);
-        const int n = slice * 32 + nb * 16 + (lane & 15), q = lane >> 4;
-        bf16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int c = (2 * jj + (e >> 2)) * 16 + q * 4 + (e & 3);
-            v[e] = (__bf16)(d.transposed ? d.src[((int64_t)c * K + k) * Cd + n] : d.src[((int64_t)n * K + k) * Cs + c]);
-        }
-        reinterpret_cast<bf16x8*>(d.dst)[idx] = v;
-    } else {
-        const int cs16 = Cs / 16;
-        if (idx >= (int64_t)(Cd / 32) * K * cs16 * 2 * 64) return;
-        const int j = (int)(t % cs16); t /= cs16;
-        const int k = (int)(t % K), slice = (int)(t / K);
-        const int n = slice * 32 + nb * 16 + (lane & 15), c = j * 16 + (lane >> 4) * 4;
-        float4 v;
-        if (!d.transposed) {
-            v = *reinterpret_cast<const float4*>(d.src + ((int64_t)n * K + k) * Cs + c);
-        } else {
-            v.x = d.src[((int64_t)(c + 0) * K + k) * Cd + n];
-            v.y = d.src[((int64_t)(c + 1) * K + k) * Cd + n];
-            v.z = d.src[((int64_t)(c + 2) * K + k) * Cd + n];
-            v.w = d.src[((int64_t)(c + 3) * K + k) * Cd + n];
-        }
-        reinterpret_cast<float4*>(d.dst)[idx] = v;
-    }
+    weight_pack_vector(d.bf, d.src, d.dst, ((int64_t)blockIdx.x - d.block0) * 256 + threadIdx.x, (int)d.Cd, (int)d.K, (int)d.Cs, (int)d.transposed);
 }
 
 __global__ void weight_transpose_k(const float* __restrict__ w, float* __restrict__ wt, int Cd, int K, int Cs) {
@@ -1127,18 +1097,25 @@ int u3d_spconv_gmm_bf16a(const void* src_bf16, int64_t n_src, const void* w_rows
                            k_groups, addend, dst, ws, nullptr, flops_hint, stream, 3);
 }
 
-int u3d_weight_pack_x3(const float* w, void* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {
-    if (!w || !wp || Cd <= 0 || K <= 0 || Cs <= 0 || Cd % 32 || Cs % 32) return U3D_EINVAL;
-    const int64_t total8 = (int64_t)Cd * K * Cs / 8;
-    hipLaunchKernelGGL(weight_pack_x3_k, dim3((unsigned)ceil_div(total8, 256)), dim3(256), 0, (hipStream_t)stream, w, (bf16x8*)wp, Cd, K, Cs, transposed);
-    return check_launch("weight_pack_x3");
+static int weight_pack_impl(int format, const float* w, void* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {
+    static const char* const label[] = {"weight_pack", "weight_pack_bf16", "weight_pack_x3"};
+    if (!w || !wp || Cd <= 0 || K <= 0 || Cs <= 0 || Cd % 32 || Cs % (format ? 32 : 16)) return U3D_EINVAL;
+    const dim3 grid((unsigned)ceil_div(weight_pack_vectors(format, Cd, K, Cs), 256));
+    auto* kernel = format == 2 ? weight_pack_k<2> : format ? weight_pack_k<1> : weight_pack_k<0>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, w, wp, Cd, K, Cs, transposed);
+    return check_launch(label[format]);
+}
+
+int u3d_weight_pack(const float* w, float* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {
+    return weight_pack_impl(0, w, wp, Cd, K, Cs, transposed, stream);
 }
 
 int u3d_weight_pack_bf16(const float* w, void* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {
-    if (!w || !wp || Cd <= 0 || K <= 0 || Cs <= 0 || Cd % 32 || Cs % 32) return U3D_EINVAL;
-    const int64_t total8 = (int64_t)Cd * K * Cs / 8;
-    hipLaunchKernelGGL(weight_pack_bf16_k, dim3((unsigned)ceil_div(total8, 256)), dim3(256), 0, (hipStream_t)stream, w, (bf16x8*)wp, Cd, K, Cs, transposed);
-    return check_launch("weight_pack_bf16");
+    return weight_pack_impl(1, w, wp, Cd, K, Cs, transposed, stream);
+}
+
+int u3d_weight_pack_x3(const float* w, void* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {
+    return weight_pack_impl(2, w, wp, Cd, K, Cs, transposed, stream);
 }
 
 int u3d_spconv_wgrad_tile_rows(int K, int64_t n_rows_dy, int Cs, int Cd) {
@@ -1204,13 +1181,6 @@ int u3d_weight_pack_batch(const void* desc, int n_desc, int64_t total_blocks, u3
     if (!desc || n_desc <= 0 || total_blocks <= 0 || total_blocks >= 0x7fffffffLL) return U3D_EINVAL;
     hipLaunchKernelGGL(weight_pack_batch_k, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const PackDesc*)desc, n_desc);
     return check_launch("weight_pack_batch");
-}
-
-int u3d_weight_pack(const float* w, float* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {
-    if (!w || !wp || Cd <= 0 || K <= 0 || Cs <= 0 || Cd % 32 || Cs % 16) return U3D_EINVAL;
-    const int64_t total4 = (int64_t)Cd * K * Cs / 4;
-    hipLaunchKernelGGL(weight_pack_k, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, (hipStream_t)stream, w, wp, Cd, K, Cs, transposed);
-    return check_launch("weight_pack");
 }
 
 int u3d_weight_transpose(const float* w, float* wt, int Cd, int K, int Cs, u3d_stream_t stream) {

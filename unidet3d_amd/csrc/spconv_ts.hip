@@ -39,14 +39,12 @@
 
 namespace u3d {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 ts_bf16x8;
-
-__device__ __forceinline__ f32x4 ts_mfma(const f32x4& a, const ts_bf16x8& b, const f32x4& c) {
+__device__ __forceinline__ f32x4 ts_mfma(const f32x4& a, const bf16x8& b, const f32x4& c) {
 #if U3D_TS_ABL & 1
     asm volatile("" :: "v"(a), "v"(b));
     return c;
 #else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(ts_bf16x8, a), b, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), b, c, 0, 0, 0);
 #endif
 }
 
@@ -340,7 +338,7 @@ __global__ __launch_bounds__(256) void spconv_ts_k(TsParams p) {
         // ---- offsets of this pass, software-pipelined: while offset kk is multiplied, the fragments of the next offset with work
         // in the pass (its loc entries were read one offset earlier) are already on their way from the halo image ----
         int step = 0;
-        struct Ops { ts_bf16x8 x[RT][CS32][3]; bool any[RT]; };
+        struct Ops { bf16x8 x[RT][CS32][3]; bool any[RT]; };
         auto read_lc = [&](int kk, int (&lcv)[RT]) {
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) lcv[rt] = *reinterpret_cast<const unsigned short*>(ll + kk * (T * 2) + loc_lane + rt * 128);
@@ -359,8 +357,8 @@ __global__ __launch_bounds__(256) void spconv_ts_k(TsParams p) {
                     for (int u = 0; u < CS32; ++u)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl) {
-                            if (U3D_TS_ABL & 32) o.x[rt][u][pl] = __builtin_bit_cast(ts_bf16x8, f32x4{(float)a0, 1.f, 2.f, (float)pl});
-                            else o.x[rt][u][pl] = *reinterpret_cast<const ts_bf16x8*>(hl + (u * 3 + pl) * PLANE + a0);
+                            if (U3D_TS_ABL & 32) o.x[rt][u][pl] = __builtin_bit_cast(bf16x8, f32x4{(float)a0, 1.f, 2.f, (float)pl});
+                            else o.x[rt][u][pl] = *reinterpret_cast<const bf16x8*>(hl + (u * 3 + pl) * PLANE + a0);
                         }
                 }
             }
@@ -599,17 +597,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             // (the fragment reads are UNCONDITIONAL -- an item without work reads the zero row: a read inside a branch makes the number
             // of outstanding LDS operations unknown at the join, and the compiler then waits for lgkmcnt(0) in front of every item's
             // MFMAs, i.e. for the reads of the NEXT item as well: no overlap at all, measured 9.5 k cycles per tile instead of ~5 k)
-            ts_bf16x8 xa[3], xb[3];
+            bf16x8 xa[3], xb[3];
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) xa[pl] = *reinterpret_cast<const ts_bf16x8*>(hl + pl * PLANE + a0s[0]);
+            for (int pl = 0; pl < 3; ++pl) xa[pl] = *reinterpret_cast<const bf16x8*>(hl + pl * PLANE + a0s[0]);
 #pragma unroll
             for (int it = 0; it < 28; ++it) {
                 const int j = it >> 2, rt = it & 3;
-                ts_bf16x8 (&cur)[3] = (it & 1) ? xb : xa;
-                ts_bf16x8 (&nxt)[3] = (it & 1) ? xa : xb;
+                bf16x8 (&cur)[3] = (it & 1) ? xb : xa;
+                bf16x8 (&nxt)[3] = (it & 1) ? xa : xb;
                 if (it + 1 < 28) {
 #pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) nxt[pl] = *reinterpret_cast<const ts_bf16x8*>(hl + pl * PLANE + a0s[it + 1]);
+                    for (int pl = 0; pl < 3; ++pl) nxt[pl] = *reinterpret_cast<const bf16x8*>(hl + pl * PLANE + a0s[it + 1]);
                 }
                 if ((amask >> it) & 1u) {
                     // the two column blocks' chains alternate: a dependent MFMA waits for its predecessor (one wave per SIMD: nobody else fills the gap)
@@ -751,14 +749,14 @@ __global__ __launch_bounds__(256) void spconv_rsb_k(RsbParams p) {
                 a0s[it] = ts_slot_off(ok ? s0 : H, q);
                 amask |= (__ballot(ok) != 0ull ? 1u : 0u) << it;
             }
-            ts_bf16x8 xa, xb;
-            xa = *reinterpret_cast<const ts_bf16x8*>(hl + a0s[0]);
+            bf16x8 xa, xb;
+            xa = *reinterpret_cast<const bf16x8*>(hl + a0s[0]);
 #pragma unroll
             for (int it = 0; it < 28; ++it) {
                 const int j = it >> 2, rt = it & 3;
-                ts_bf16x8& cur = (it & 1) ? xb : xa;
-                ts_bf16x8& nxt = (it & 1) ? xa : xb;
-                if (it + 1 < 28) nxt = *reinterpret_cast<const ts_bf16x8*>(hl + a0s[it + 1]);      // unconditional: see spconv_rs_k
+                bf16x8& cur = (it & 1) ? xb : xa;
+                bf16x8& nxt = (it & 1) ? xa : xb;
+                if (it + 1 < 28) nxt = *reinterpret_cast<const bf16x8*>(hl + a0s[it + 1]);      // unconditional: see spconv_rs_k
                 if ((amask >> it) & 1u) {
                     acc[rt][0] = ts_mfma(wf[j][0], cur, acc[rt][0]);
                     acc[rt][1] = ts_mfma(wf[j][1], cur, acc[rt][1]);

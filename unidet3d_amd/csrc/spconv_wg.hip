@@ -19,7 +19,6 @@
 
 namespace u3d {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 __device__ __forceinline__ f32x4 wg_mfma(const f32x4& a, const bf16x8& b, const f32x4& c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), b, c, 0, 0, 0);

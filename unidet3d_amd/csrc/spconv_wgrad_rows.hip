@@ -16,10 +16,6 @@
 
 namespace u3d {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8w;
-typedef __attribute__((ext_vector_type(4))) short s16x4w;
-typedef __attribute__((ext_vector_type(8))) short s16x8w;
-
 struct WgRowsParams {
     const void* x;            // bf16 [n_x][Cs]
     const void* dy;           // bf16 [n_dy][Cd]
@@ -115,21 +111,19 @@ __global__ __launch_bounds__(256) void spconv_wgrad_rows_k(WgRowsParams p) {
         for (int i = 0; i < NIX; ++i) put(tx, TX, i * RX + rx, CS, px, vx[i]);
     };
     // fragment of a [32 pairs][16 channels] block of a plane tile: lane (t16, q) <- column t16 over pairs 8q .. 8q+7, two transpose reads
-    auto frag = [&](const __bf16* tile, int C, int blk) -> bf16x8w {
+    auto frag = [&](const __bf16* tile, int C, int blk) -> bf16x8 {
         const __bf16* s0 = tile + (8 * q + (t16 >> 2)) * C + blk * 16 + 4 * (t16 & 3);
-        const s16x4w r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w*)s0);
-        const s16x4w r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w*)(s0 + 4 * C));
-        return __builtin_bit_cast(bf16x8w, s16x8w{r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]});
+        return tr16_pair(s0, s0 + 4 * C);
     };
     auto multiply = [&]() {
-        bf16x8w fb[NX][NP];
+        bf16x8 fb[NX][NP];
 #pragma unroll
         for (int b = 0; b < NX; ++b)
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl) fb[b][pl] = frag(tx + pl * TX, CS, b);
 #pragma unroll
         for (int a = 0; a < NG; ++a) {
-            bf16x8w fa[NP];
+            bf16x8 fa[NP];
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl) fa[pl] = frag(tg + pl * TG, CD, a);
 #pragma unroll
@@ -266,21 +260,19 @@ __global__ __launch_bounds__(256) void spconv_wgrad_rows_coop_k(WgRowsParams p) 
             if (pid < PX) *reinterpret_cast<f32x4*>(tx + pid * 8) = vx[i];
         }
     };
-    auto frag = [&](const __bf16* tile, int C, int blk) -> bf16x8w {
+    auto frag = [&](const __bf16* tile, int C, int blk) -> bf16x8 {
         const __bf16* s0 = tile + (8 * q + (t16 >> 2)) * C + blk * 16 + 4 * (t16 & 3);
-        const s16x4w r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w*)s0);
-        const s16x4w r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w*)(s0 + 4 * C));
-        return __builtin_bit_cast(bf16x8w, s16x8w{r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]});
+        return tr16_pair(s0, s0 + 4 * C);
     };
     auto multiply = [&](int buf) {
         const __bf16* tg = tiles + buf * (TG + TX);
         const __bf16* tx = tg + TG;
-        bf16x8w fb[NXW];
+        bf16x8 fb[NXW];
 #pragma unroll
         for (int b = 0; b < NXW; ++b) fb[b] = frag(tx, CS, wb * NXW + b);
 #pragma unroll
         for (int a = 0; a < NGW; ++a) {
-            const bf16x8w fa = frag(tg, CD, wa * NGW + a);
+            const bf16x8 fa = frag(tg, CD, wa * NGW + a);
 #pragma unroll
             for (int b = 0; b < NXW; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[b], acc[a][b], 0, 0, 0);
         }

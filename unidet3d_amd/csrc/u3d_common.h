@@ -79,8 +79,42 @@ extern int g_fp32_math;
 extern int g_conv_kernel;      // 1: workgroup-tile sparse convolution (spconv_wg.hip), 0: wave tiles (u3d_conv_kernel)
 bool fp32_x3();
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+// ---- vector types and bf16 / MFMA helpers of the device code: ONE definition each, used by every .hip file ----
 using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
-using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+using s16x4 = __attribute__((ext_vector_type(4))) short;
+using s16x8 = __attribute__((ext_vector_type(8))) short;
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+// two fp32 values -> one dword of two bf16 (round to nearest even; low half: lo)
+__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return __builtin_bit_cast(unsigned, bf16x2{(__bf16)lo, (__bf16)hi}); }
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
+
+// LDS transpose read (ds_read_b64_tr_b16) of two [4 rows][16 cols] bf16 blocks: each 16-lane group hands in the 8-byte addresses
+// of its block (p0, p1: this lane's 4 halves) and lane t receives column t over the four rows of either block -- one MFMA operand.
+__device__ __forceinline__ bf16x8 tr16_pair(const __bf16* p0, const __bf16* p1) {
+    const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p0);
+    const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p1);
+    return __builtin_bit_cast(bf16x8, s16x8{r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]});
+}
+
+// erf GELU with ONE exponential per element: erf(z) = 1 - (a1 t + ... + a5 t^5) exp(-z^2), t = 1 / (1 + p z), z = |x| / sqrt 2
+// (Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 -- below fp32 resolution of the products it enters), and exp(-z^2) =
+// exp(-x^2 / 2) is also the Gaussian of the derivative.  libm's erff costs ~3x the VALU instructions, and VALU time in a
+// GEMM epilogue is not hidden (one wave per SIMD): measured +95 us on the [16k x 1024] hidden-gradient GEMM with erff.
+__device__ __forceinline__ void gelu_parts(float x, float& cdf, float& pdf) {
+    const float ax = fabsf(x), e = __expf(-0.5f * x * x);
+    const float t = __frcp_rn(1.f + 0.3275911f * 0.70710678118654752440f * ax);
+    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+    const float tail = 0.5f * poly * e;                     // 0.5 * erfc(|x| / sqrt 2): Phi(-|x|) without cancellation
+    cdf = x >= 0.f ? 1.f - tail : tail;
+    pdf = 0.39894228040143267794f * e;
+}
+__device__ __forceinline__ float gelu_f(float x) { float c, p; gelu_parts(x, c, p); return x * c; }
+__device__ __forceinline__ float gelu_grad_f(float x) { float c, p; gelu_parts(x, c, p); return c + x * p; }
+
 // two fp32 values -> one dword per plane (low half: a, high half: b).  h is x ROUNDED to 8 significant bits (add half an ulp to
 // the bit pattern, clear the low 16 bits: round to nearest, ties away), m is x - h TRUNCATED to 8 bits, l the exact rest:
 // |x - h| <= 2^-8 |x| with either sign, |l| < 2^-7 |x - h|, so the dropped cross terms m.l + l.m are <= 2^-22 of a product in the
@@ -103,9 +137,9 @@ __device__ __forceinline__ void split3_pair(float a, float b, unsigned& h, unsig
     l = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b2), __builtin_bit_cast(unsigned, a2), 0x07060302u);
 }
 // eight fp32 values -> the three bf16x8 planes
-__device__ __forceinline__ void split3_x8(const f32x4& lo, const f32x4& hi, bf16x8_t (&out)[3]) {
+__device__ __forceinline__ void split3_x8(const f32x4& lo, const f32x4& hi, bf16x8 (&out)[3]) {
 #ifdef U3D_SPLIT_ABL       // timing ablation (tools/build_variant.sh <file> -DU3D_SPLIT_ABL): operands without the split arithmetic, WRONG results
-    out[0] = __builtin_bit_cast(bf16x8_t, lo); out[1] = __builtin_bit_cast(bf16x8_t, hi); out[2] = out[0];
+    out[0] = __builtin_bit_cast(bf16x8, lo); out[1] = __builtin_bit_cast(bf16x8, hi); out[2] = out[0];
     return;
 #endif
     unsigned w[3][4];
@@ -117,7 +151,7 @@ __device__ __forceinline__ void split3_x8(const f32x4& lo, const f32x4& hi, bf16
 #pragma unroll
     for (int q = 0; q < 3; ++q) p[q] = u32x4{w[q][0], w[q][1], w[q][2], w[q][3]};
 #pragma unroll
-    for (int q = 0; q < 3; ++q) out[q] = __builtin_bit_cast(bf16x8_t, p[q]);
+    for (int q = 0; q < 3; ++q) out[q] = __builtin_bit_cast(bf16x8, p[q]);
 }
 #endif
 
