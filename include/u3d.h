@@ -358,7 +358,10 @@ int u3d_segment_minmax_xyz(const float* points, int pt_ld, const int64_t* ids, i
  * K13  self-attention core of nn.MultiheadAttention(256, 8, batch_first) per scene
  *     (unidet3d/encoder.py:19-20,36-37): softmax(Q K^T / sqrt(hd)) V over packed variable
  *     length scenes.  qkv [n_total, 3*H*hd] (the in_proj output), cu_seqlens int32 [B+1],
- *     out [n_total, H*hd], lse [H, n_total] (log-sum-exp, saved for backward).  hd == 32.
+ *     out [n_total, H*hd], lse [H, n_total] (log-sum-exp, saved for backward).
+ *     hd is 32 or 64 in all six entry points (any d_model / num_heads pair with that quotient); every other value returns
+ *     U3D_EUNSUPPORTED ("head_dim <n> unsupported") before the first HIP call.  The native fp32 MFMA arm of the two fp32 entry
+ *     points (u3d_fp32_math(0)) runs hd == 32 only and says so: the default three-plane mode runs 64.
  * ===================================================================================== */
 int u3d_attn_varlen_fwd(const float* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total,
                         int H, int hd, float scale, float* out, float* lse, double flops_hint,

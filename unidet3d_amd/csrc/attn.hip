@@ -1,5 +1,6 @@
 // K13 self-attention core on gfx950: varlen (cu_seqlens-packed) flash attention, fp32 in / fp32
-// accumulate on v_mfma_f32_16x16x4_f32, head_dim 32.  Replaces the math path of
+// accumulate on v_mfma_f32_16x16x4_f32, head_dim 32 (this is the native arm of the fp32 path; head_dim 64
+// runs on the plane kernels only, attn_x3_hd64.h).  Replaces the math path of
 // nn.MultiheadAttention(256, 8, batch_first=True) at unidet3d/encoder.py:19-20,36-37 (called per
 // scene in a Python loop by the reference); the n x n score matrix never leaves the CU.
 //
@@ -290,13 +291,22 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(const float* __restrict__ 
     }
 }
 
+// head dims: 32 and 64 in the plane kernels (attn_x3.hip / attn_x3_hd64.h: every mode but ATTN_NATIVE); the native fp32 MFMA kernels above are the
+// A/B arm of the default fp32 path and stay at 32.  Decided before the first HIP call (tests/test_cabi.py runs this without a device).
+static int attn_check_hd(AttnMode mode, int hd) {
+    if (hd == 32 || (hd == 64 && mode != ATTN_NATIVE)) return U3D_OK;
+    if (hd == 64) set_error("attn: head_dim %d unsupported by the native fp32 MFMA kernels (U3D_FP32_MATH=mfma; 32 only) -- the default fp32 math mode bf16x3 (u3d_fp32_math(1)) runs it", hd);
+    else set_error("attn: head_dim %d unsupported (32 or 64)", hd);
+    return U3D_EUNSUPPORTED;
+}
+
 static const char* const ATTN_FWD_LABEL[] = {"attn_fwd", "attn_fwd_x3", "attn_fwd_bf16", "attn_fwd_b16"};        // by AttnMode
 static const char* const ATTN_BWD_LABEL[] = {"attn_bwd", "attn_bwd_x3", "attn_bwd_bf16", "attn_bwd_b16"};
 
 int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
              float* lse, double flops_hint, u3d_stream_t stream) {
     if (!qkv || !cu || !out || !lse || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
+    if (attn_check_hd(mode, hd) != U3D_OK) return U3D_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_ATTN_FWD, s, flops_hint);
     if (max_len <= 0) return U3D_OK;
@@ -304,7 +314,7 @@ int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_l
         const int n_tiles = (max_len + 63) / 64;
         hipLaunchKernelGGL(attn_fwd_k, dim3(attn_grid(H, B, n_tiles)), dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
     } else {
-        attn_fwd_x3_launch(mode, qkv, cu, B, max_len, n_total, H, scale, out, lse, s);
+        attn_fwd_x3_launch(mode, qkv, cu, B, max_len, n_total, H, hd, scale, out, lse, s);
     }
     return check_launch(ATTN_FWD_LABEL[mode]);
 }
@@ -312,20 +322,25 @@ int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_l
 int attn_bwd(AttnMode mode, const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
              int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream) {
     if (!qkv || !out || !dout || !lse || !cu || !dqkv || !delta_ws || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
-    if (hd != 32) { set_error("attn: head_dim %d unsupported (32 only)", hd); return U3D_EUNSUPPORTED; }
+    if (attn_check_hd(mode, hd) != U3D_OK) return U3D_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_ATTN_BWD, s, flops_hint);
     if (max_len <= 0) return U3D_OK;
     const dim3 dgrid((unsigned)ceil_div(n_total * H, 256));
-    if (mode == ATTN_B16) hipLaunchKernelGGL(attn_delta_k<__bf16>, dgrid, dim3(256), 0, s, (const __bf16*)out, (const __bf16*)dout, n_total, H, delta_ws);
-    else hipLaunchKernelGGL(attn_delta_k<float>, dgrid, dim3(256), 0, s, (const float*)out, (const float*)dout, n_total, H, delta_ws);
+    if (mode == ATTN_B16) {
+        if (hd == 64) hipLaunchKernelGGL((attn_delta_k<__bf16, 64>), dgrid, dim3(256), 0, s, (const __bf16*)out, (const __bf16*)dout, n_total, H, delta_ws);
+        else hipLaunchKernelGGL((attn_delta_k<__bf16, 32>), dgrid, dim3(256), 0, s, (const __bf16*)out, (const __bf16*)dout, n_total, H, delta_ws);
+    } else {
+        if (hd == 64) hipLaunchKernelGGL((attn_delta_k<float, 64>), dgrid, dim3(256), 0, s, (const float*)out, (const float*)dout, n_total, H, delta_ws);
+        else hipLaunchKernelGGL((attn_delta_k<float, 32>), dgrid, dim3(256), 0, s, (const float*)out, (const float*)dout, n_total, H, delta_ws);
+    }
     if (mode == ATTN_NATIVE) {
         const int n_tiles = (max_len + 63) / 64;
         const dim3 grid(attn_grid(H, B, n_tiles));
         hipLaunchKernelGGL(attn_bwd_dq_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
         hipLaunchKernelGGL(attn_bwd_dkv_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
     } else {
-        attn_bwd_x3_launch(mode, qkv, dout, lse, cu, B, max_len, n_total, H, scale, dqkv, delta_ws, s);
+        attn_bwd_x3_launch(mode, qkv, dout, lse, cu, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, s);
     }
     return check_launch(ATTN_BWD_LABEL[mode]);
 }

@@ -1,4 +1,4 @@
-// Shared by the attention kernels of attn.hip (native fp32 MFMA) and attn_x3.hip (bf16 planes): the work decode, the delta
+// Shared by the attention kernels of attn.hip (native fp32 MFMA) and attn_x3.hip / attn_x3_hd64.h (bf16 planes): the work decode, the delta
 // kernel of the backward pass, and the host bodies behind the six u3d_attn_varlen_* entry points.
 #pragma once
 #include "u3d_common.h"
@@ -20,8 +20,8 @@ __device__ __forceinline__ AttnWork attn_decode(int H, int B, int n_tiles) {
 }
 static inline unsigned attn_grid(int H, int B, int n_tiles) { return (unsigned)(((H * B + 7) / 8) * 8 * n_tiles); }
 
-// delta[h][i] = sum_d dO[i][h*32+d] * O[i][h*32+d]; T = float, or __bf16 for bf16 tensors (products and sum in fp32)
-template <typename T>
+// delta[h][i] = sum_d dO[i][h*HD+d] * O[i][h*HD+d]; T = float, or __bf16 for bf16 tensors (products and sum in fp32)
+template <typename T, int HD>
 __global__ __launch_bounds__(256) void attn_delta_k(const T* __restrict__ o, const T* __restrict__ dout, int64_t n, int H, float* delta) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n * H) return;
@@ -29,18 +29,18 @@ __global__ __launch_bounds__(256) void attn_delta_k(const T* __restrict__ o, con
     const int h = (int)(idx % H);
     float s = 0.f;
     if constexpr (sizeof(T) == 4) {
-        const float4* a = reinterpret_cast<const float4*>(o + i * H * 32 + h * 32);
-        const float4* b = reinterpret_cast<const float4*>(dout + i * H * 32 + h * 32);
+        const float4* a = reinterpret_cast<const float4*>(o + i * H * HD + h * HD);
+        const float4* b = reinterpret_cast<const float4*>(dout + i * H * HD + h * HD);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < HD / 4; ++j) {
             const float4 x = a[j], y = b[j];
             s += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
         }
     } else {
-        const u32x4* a = reinterpret_cast<const u32x4*>(o + i * H * 32 + h * 32);
-        const u32x4* b = reinterpret_cast<const u32x4*>(dout + i * H * 32 + h * 32);
+        const u32x4* a = reinterpret_cast<const u32x4*>(o + i * H * HD + h * HD);
+        const u32x4* b = reinterpret_cast<const u32x4*>(dout + i * H * HD + h * HD);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < HD / 8; ++j) {
             const u32x4 x = a[j], y = b[j];
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -59,11 +59,11 @@ enum AttnMode {
     ATTN_B16,           // bf16 tensors (qkv / out / dout / dqkv), one plane
 };
 
-// attn_x3.hip: the plane kernels of every mode but ATTN_NATIVE (the backward launcher expects delta_ws filled)
-void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, float scale, void* out,
+// attn_x3.hip: the plane kernels of every mode but ATTN_NATIVE, hd 32 or 64 (the backward launcher expects delta_ws filled)
+void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
                         float* lse, hipStream_t s);
 void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
-                        int64_t n_total, int H, float scale, void* dqkv, const float* delta, hipStream_t s);
+                        int64_t n_total, int H, int hd, float scale, void* dqkv, const float* delta, hipStream_t s);
 
 // attn.hip: the bodies of the u3d_attn_varlen_{fwd,bwd}{,_bf16,_b16} entry points -- validation, timing scope, dispatch, launch check
 int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,

@@ -5,7 +5,7 @@
 // U3D_FP32_MATH=mfma selects the native fp32 MFMA kernels of attn.hip.
 //
 // v_mfma_f32_16x16x32_bf16: lane (i = lane & 15, g = lane >> 4) holds the 8 reduction elements k = 8g .. 8g+7 of row i (A) /
-// column i (B); head_dim = 32 is one instruction's reduction depth.
+// column i (B); head_dim = 32 is one instruction's reduction depth (head_dim 64: attn_x3_hd64.h; the helpers both share: attn_x3.h).
 //   S^T (16 keys x 16 queries) = K_tile . Q^T       A = K rows, natural [key][dim] planes in LDS (one 16-byte read per plane),
 //                                                   B = own Q rows, split once into registers
 //   O (16 queries x 16 dims) += P . V               A = two C fragments (keys {4g..4g+3} of two 16-key tiles), split in registers,
@@ -22,22 +22,16 @@
 #include <mutex>
 #include <stdlib.h>
 
-#include "attn_common.h"
+#include "attn_x3.h"
 
 namespace u3d {
 
-constexpr float X_LOG2E = 1.44269504088896340736f, X_LN2 = 0.69314718055994530942f;
 constexpr int XLD = 32;                  // halves per row of a natural plane: unpadded, the 16-byte chunk index is XORed with (row >> 1) & 3
                                          // (conflict-free ds_read_b128 for the lane -> (row = lane & 15, chunk = lane >> 4) map)
 constexpr int XN = 64 * XLD;             // halves per natural plane
-#define U3D_MFMA_X(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-// c += a . b with both operands in three planes takes h.l, m.m, l.h, h.m, m.h, h.h (smallest terms first);
-// two independent accumulators side by side (dependent MFMAs wait for their predecessor; alternating chains fills the gaps).
-// A bf16 MFMA truncates its 32 products at the exponent of its C operand, always towards zero: plane products 2^-8 .. 2^-16 below
-// a running sum lose their low bits every time -- a coherent bias (tools/bias_probe.py: -1.2e-8 mean error after 8 blocks, zero
-// for fp32 MFMAs) that reductions over thousands of rows downstream do not average out.  So chains that start from zero (S, dP)
-// run smallest terms first, and the running sums O / dQ / dK / dV keep the low-order products in accumulators of their own.
+// c += a . b, plane products smallest terms first (attn_x3.h): two independent accumulators side by side (dependent MFMAs wait for
+// their predecessor; alternating chains fills the gaps)
 template <int NP>
 __device__ __forceinline__ void mfma_x3_2a(const bf16x8 (&a0)[NP], const bf16x8 (&a1)[NP], const bf16x8 (&b)[NP], f32x4& c0, f32x4& c1) {
 #pragma unroll
@@ -47,21 +41,6 @@ __device__ __forceinline__ void mfma_x3_2a(const bf16x8 (&a0)[NP], const bf16x8 
             c0 = U3D_MFMA_X(a0[qa], b[o - qa], c0);
             c1 = U3D_MFMA_X(a1[qa], b[o - qa], c1);
         }
-}
-// running sums: the h.h product goes to (c0, c1), the five low-order plane products to their own accumulators (l0, l1), joined
-// once at the end of the kernel (NP = 1, bf16 operands: the one product goes to (c0, c1))
-template <int NP>
-__device__ __forceinline__ void mfma_x3_2b(const bf16x8 (&a)[NP], const bf16x8 (&b0)[NP], const bf16x8 (&b1)[NP], f32x4& c0, f32x4& c1,
-                                           f32x4& l0, f32x4& l1) {
-#pragma unroll
-    for (int o = NP - 1; o >= 1; --o)
-#pragma unroll
-        for (int qa = 0; qa <= o; ++qa) {
-            l0 = U3D_MFMA_X(a[qa], b0[o - qa], l0);
-            l1 = U3D_MFMA_X(a[qa], b1[o - qa], l1);
-        }
-    c0 = U3D_MFMA_X(a[0], b0[0], c0);
-    c1 = U3D_MFMA_X(a[0], b1[0], c1);
 }
 // one chain pair sharing nothing: s += a . b, d += c . e (S and dP of the backward kernels)
 template <int NP>
@@ -73,19 +52,6 @@ __device__ __forceinline__ void mfma_x3_2c(const bf16x8 (&a)[NP], const bf16x8 (
             s = U3D_MFMA_X(a[qa], b[o - qa], s);
             d = U3D_MFMA_X(c[qa], e[o - qa], d);
         }
-}
-
-// NP planes of a pair / of eight values: NP = 3 the exact split (u3d_common.h), NP = 1 one bf16 value rounded to nearest even
-// (bf16 operands, BASELINE configs[2])
-template <int NP>
-__device__ __forceinline__ void planes_pair(float a, float b, unsigned (&w)[NP]) {
-    if constexpr (NP == 3) split3_pair(a, b, w[0], w[1], w[2]);
-    else w[0] = pack_bf16(a, b);
-}
-template <int NP>
-__device__ __forceinline__ void planes_x8(const f32x4& lo, const f32x4& hi, bf16x8 (&out)[NP]) {
-    if constexpr (NP == 3) split3_x8(lo, hi, out);
-    else out[0] = bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
 }
 
 // Stage 64 rows x 32 floats of `base` (rows >= len are zero, values scaled before the split): thread (p = tid >> 3, c = tid & 7)
@@ -139,11 +105,6 @@ __device__ __forceinline__ void store_x16(StageRegs16 r, __bf16* nat, int tid) {
     *reinterpret_cast<uint2*>(nat + (2 * p) * XLD + off) = r.a;
     *reinterpret_cast<uint2*>(nat + (2 * p + 1) * XLD + off) = r.b;
 }
-__device__ __forceinline__ void row_frag_x16(const __bf16* ptr, bf16x8 (&out)[1]) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (ptr) v = *reinterpret_cast<const u32x4*>(ptr);
-    out[0] = __builtin_bit_cast(bf16x8, v);
-}
 template <bool IO16> struct IoT { typedef float t; typedef StageRegs regs; };
 template <> struct IoT<true> { typedef __bf16 t; typedef StageRegs16 regs; };
 template <bool IO16>
@@ -160,22 +121,6 @@ template <bool IO16>
 __device__ __forceinline__ void put_io(typename IoT<IO16>::t* p, float v) {
     if constexpr (IO16) *p = (__bf16)v;
     else *p = v;
-}
-
-// own row -> B operand planes: 8 consecutive dims of row `ptr` (nullptr: zeros), scaled
-template <int NP>
-__device__ __forceinline__ void row_frag_x3(const float* ptr, float scale, bf16x8 (&out)[NP]) {
-    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
-    if (ptr) { a = *reinterpret_cast<const f32x4*>(ptr); b = *reinterpret_cast<const f32x4*>(ptr + 4); }
-    a *= scale;
-    b *= scale;
-    planes_x8<NP>(a, b, out);
-}
-
-// A operand planes from two C fragments: k = 8g + e <-> row 16 (e >> 2) + 4g + (e & 3) of the 32-row block
-template <int NP>
-__device__ __forceinline__ void pair_frag_x3(const float (&lo)[4], const float (&hi)[4], bf16x8 (&out)[NP]) {
-    planes_x8<NP>(f32x4{lo[0], lo[1], lo[2], lo[3]}, f32x4{hi[0], hi[1], hi[2], hi[3]}, out);
 }
 
 // natural planes: rows 16 kb + i, dims 8g .. 8g+7
@@ -482,10 +427,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3
     }
 }
 
-// launchers, called from attn.hip's attn_fwd / attn_bwd for every mode but ATTN_NATIVE (arguments already validated there)
-void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, float scale, void* out,
+// launchers, called from attn.hip's attn_fwd / attn_bwd for every mode but ATTN_NATIVE (arguments already validated there: hd is 32 or 64)
+void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
                         float* lse, hipStream_t s) {
     const int n_tiles = (max_len + 63) / 64;
+    if (hd == 64) return attn_fwd_x3_hd64_launch(mode, qkv, cu, B, n_tiles, n_total, H, scale, out, lse, s);
     const dim3 grid(attn_grid(H, B, n_tiles));
     if (mode == ATTN_B16) hipLaunchKernelGGL((attn_fwd_x3_k<1, true>), grid, dim3(256), 0, s, (const __bf16*)qkv, cu, H, scale, (__bf16*)out, lse, n_total, B, n_tiles);
     else if (mode == ATTN_BF16_OPS) hipLaunchKernelGGL((attn_fwd_x3_k<1>), grid, dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
@@ -520,7 +466,7 @@ static AttnFork* attn_fork_of_device() {
 }
 
 void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
-                        int64_t n_total, int H, float scale, void* dqkv, const float* delta, hipStream_t s) {
+                        int64_t n_total, int H, int hd, float scale, void* dqkv, const float* delta, hipStream_t s) {
     const int n_tiles = (max_len + 63) / 64;
     const dim3 grid(attn_grid(H, B, n_tiles));
     AttnFork* f = attn_fork_of_device();
@@ -530,7 +476,9 @@ void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const 
         hipStreamWaitEvent(f->side, f->fork, 0);
         sq = f->side;
     }
-    if (mode == ATTN_B16) {
+    if (hd == 64) {
+        attn_bwd_x3_hd64_launch(mode, qkv, dout, lse, cu, B, n_tiles, n_total, H, scale, dqkv, delta, sq, s);
+    } else if (mode == ATTN_B16) {
         hipLaunchKernelGGL((attn_bwd_dq_x3_k<1, true>), grid, dim3(256), 0, sq, (const __bf16*)qkv, (const __bf16*)dout, lse, delta, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
         hipLaunchKernelGGL((attn_bwd_dkv_x3_k<1, true>), grid, dim3(256), 0, s, (const __bf16*)qkv, (const __bf16*)dout, lse, delta, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
     } else if (mode == ATTN_BF16_OPS) {
@@ -547,6 +495,8 @@ void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const 
 }
 
 }  // namespace u3d
+
+#include "attn_x3_hd64.h"          // the head_dim 64 kernels and their launchers
 
 using namespace u3d;
 
