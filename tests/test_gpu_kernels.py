@@ -583,10 +583,9 @@ def test_batchnorm_statistics_from_the_convolution_epilogue(cin, cout, n_points,
             bn.weight.data.copy_(gamma); bn.bias.data.copy_(beta)
             # (the 16-channel case is the network's zero-padded 6-channel input: no input gradient exists for it)
             xd, wd, ad = x.clone().to(_dev()).requires_grad_(cin % 32 == 0), w.clone().to(_dev()).requires_grad_(), add.clone().to(_dev()).requires_grad_()
-            st = {}
-            f = sparse.sparse_conv(xd, wd, rb, 'fwd', ad, st)
-            assert ('partial' in st) == (mode and sparse._plan(cin, cout, 27, n)[1] == 1)
-            y = bn(f, relu=True, stats=st if 'partial' in st else None)
+            f = sparse.sparse_conv(xd, wd, rb, 'fwd', ad, True)
+            assert (sparse.stats_of(f) is not None) == (mode and sparse._plan(cin, cout, 27, n)[1] == 1)
+            y = bn(f, relu=True)
             y.backward(go.to(_dev()))
             res[mode] = dict(f=f.detach(), y=y.detach(), dx=xd.grad, dw=wd.grad, da=ad.grad, dg=bn.weight.grad, db=bn.bias.grad,
                              rm=bn.running_mean.clone(), rv=bn.running_var.clone(), nbt=int(bn.num_batches_tracked))

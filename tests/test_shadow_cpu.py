@@ -1,5 +1,6 @@
 """Host logic of the bf16 shadows (precision.bf16_rows) that needs no GPU: the fragment-order layout the batch-norm
-kernels write (csrc/bn.hip store_shadow; restated by sparse.to_shadow), how a shadow follows its tensor, and the mode switches."""
+kernels write (csrc/bn.hip store_shadow; restated by sparse.to_shadow), how a shadow -- and, by the same rule, the convolution-epilogue statistics (sparse.stats_of) -- follows
+its tensor, and the mode switches."""
 import torch
 
 
@@ -29,6 +30,25 @@ def test_shadow_follows_its_tensor_and_is_dropped_when_the_tensor_changes():
     assert sparse.shadow_of(t + 0) is None and sparse.shadow_of(t.clone()) is None        # a new tensor (e.g. an accumulated gradient) has none
     t.mul_(2.0)                                              # in-place change: the shadow no longer describes the tensor
     assert sparse.shadow_of(t) is None
+
+
+def test_epilogue_statistics_follow_their_tensor_and_are_dropped_when_the_tensor_changes():
+    """The per-tile column sums a convolution attaches to its output (sparse.attach_stats) obey the shadow's rule: the same tensor
+    object at the same version has them, every other tensor -- and the same one after an in-place write -- has none."""
+    from unidet3d_amd import sparse
+    t = torch.randn(70, 32)
+    assert sparse.stats_of(t) is None                        # never had any
+    partial = torch.randn(3, 2, 32)
+    sparse.attach_stats(t, partial, 3)
+    got = sparse.stats_of(t)
+    assert got is not None and got[0] is partial and got[1] == 3
+    u = t
+    assert sparse.stats_of(u)[0] is partial
+    assert sparse.stats_of(t + 0) is None
+    assert sparse.stats_of(t.clone()) is None
+    t.add_(1)                                                # the stale-sum case: the sums no longer describe the rows
+    assert sparse.stats_of(t) is None
+    assert sparse.stats_of(torch.randn(70, 32)) is None
 
 
 def test_bf16_rows_follow_the_operand_mode():

@@ -13,12 +13,17 @@ Every compute step is a call through the C ABI (include/u3d.h); there is no
 PyTorch fallback.  Rows must be in canonical order (ascending
 ((b*X+x)*Y+y)*Z+z) -- which is what ``ops.voxelize`` / ``UniDet3D.collate``
 produce.
+
+What a layer leaves for the next one rides on the feature TENSOR (bf16 shadow, ``_u3d_from_conv``, the batch-norm statistics of a
+convolution's epilogue: ``shadow_of`` / ``stats_of``); ``SparseConvTensor`` carries geometry only.  A norm on a sparse tensor is one
+call, ``SparseBatchNorm.on``; a convolution layer is: find the geometry, ``_ConvBase._conv``, build the output tensor.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes
 import os
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
@@ -297,6 +302,21 @@ def shadow_of(t: torch.Tensor):
     return None
 
 
+# ---- batch-norm statistics from the convolution epilogue (_EPILOGUE_STATS) ---------------------------------------------------
+# The per-tile column sums a convolution launch wrote travel to the norm behind it the way a shadow does: on the output tensor, valid
+# for the same object at the same ``_version`` on the same device.  Any other tensor has none, and the norm makes its own pass.
+def attach_stats(t: torch.Tensor, partial: torch.Tensor, n_tiles: int):
+    t._u3d_stats = (partial, int(n_tiles), t._version)
+
+
+def stats_of(t: torch.Tensor):
+    """(partial float [n_tiles, 2, C], n_tiles) as the producing convolution attached them, or None"""
+    e = getattr(t, '_u3d_stats', None)
+    if e is not None and e[2] == t._version and e[0].device == t.device:
+        return e[:2]
+    return None
+
+
 # ---- all weight packs of a model in one launch ------------------------------------------------------------------------------
 _PACKED: Dict = {}          # (weight data_ptr, transposed, bf16) -> (buffer, weight tensor, version at pack time)
 
@@ -466,22 +486,20 @@ def _packed_weight(weight, transposed, fmt, Cd, K, Cs, device):
     return wp
 
 
-def _gmm(src, weight, transposed, rb, gather, scatter, role, n_dst, addend, flops, bf=0, stats_out=None, src_rows_bf16=None):
+def _gmm(src, weight, transposed, rb, gather, scatter, role, n_dst, addend, flops, bf=0, stats=None, src_rows_bf16=None):
     """weight: the layer's [C_out, K, C_in] tensor; transposed=True runs the input-gradient (dst channels = C_in).
-    ``stats_out`` (a dict, or None): asks the kernel's epilogue for the per-tile column sums of dst that the batch norm behind
-    this convolution needs (``partial`` float [n_tiles, 2, Cd], ``n_tiles``).  ONE rule: it is filled only by a pair-list launch
-    that gathers fp32 rows, under _EPILOGUE_STATS, with a single offset group; every other launch leaves it EMPTY and the norm makes
-    its own pass (offsets split over groups: deep levels of a few thousand rows; bf16 rows; the 'rsb' / 'rs' / 'ts' kernels).
+    ``stats`` (an empty dict of ``sparse_conv``'s, or None): asks the kernel's epilogue for the per-tile column sums of dst that the
+    batch norm behind this convolution needs (``partial`` float [n_tiles, 2, Cd], ``n_tiles``).  ONE rule: it is filled only by a
+    pair-list launch that gathers fp32 rows, under _EPILOGUE_STATS, with a single offset group; every other launch leaves it EMPTY and
+    the norm makes its own pass (offsets split over groups: deep levels of a few thousand rows; bf16 rows; the 'rsb' / 'rs' / 'ts' kernels).
     ``bf``: operand format (precision.conv_format: 0 fp32 MFMAs, 1 bf16 operands, 2 fp32 products from three bf16 planes).
     ``src_rows_bf16``: the bf16 shadow of ``src`` (``shadow_of``) -- the launch then gathers those rows.
     Which kernel runs: ``_conv_route``; its packed weight: ``_packed_weight``."""
     Cs, Cd = src.shape[1], (weight.shape[2] if transposed else weight.shape[0])
     dst = torch.empty(n_dst, Cd, dtype=torch.float32, device=src.device)
-    if stats_out is not None:
-        stats_out.clear()       # filled below by the one launch form that writes statistics; empty tells the norm to make its own pass
     if not n_dst:
         return dst
-    route, fmt, plan = _conv_route(Cs, Cd, n_dst, rb, bf, src_rows_bf16 is not None, stats_out is not None)
+    route, fmt, plan = _conv_route(Cs, Cd, n_dst, rb, bf, src_rows_bf16 is not None, stats is not None)
     if _PROFILE_FLOPS:      # BASELINE.md section 3: N(Cs+Cd)s + 2P*idx + K*Cs*Cd*s  (s = 4 B, idx = 4 B)
         account.add('conv_gmm', flops, 4.0 * (src.shape[0] * Cs + n_dst * Cd) + 8.0 * rb.total_pairs + 4.0 * rb.K * Cs * Cd)
     wp = _packed_weight(weight, transposed, fmt, Cd, rb.K, Cs, src.device)      # (the tensor, held until the launch below is queued)
@@ -494,10 +512,10 @@ def _gmm(src, weight, transposed, rb, gather, scatter, role, n_dst, addend, flop
                    rb.K, rb.cap, Cs, Cd, n_dst, R, G, L.ptr(addend), L.ptr(dst), L.ptr(ws), float(flops), L.stream())
         else:
             partial = None
-            if stats_out is not None and G == 1 and _EPILOGUE_STATS:
+            if stats is not None and G == 1 and _EPILOGUE_STATS:
                 n_tiles = (n_dst + R - 1) // R
                 partial = torch.empty(n_tiles, 2, Cd, dtype=torch.float32, device=src.device)
-                stats_out.update(partial=partial, n_tiles=n_tiles)
+                stats.update(partial=partial, n_tiles=n_tiles)
             L.call(_GMM_ENTRY[fmt][1], L.ptr(src), src.shape[0], L.ptr(wp), L.ptr(gather), L.ptr(scatter), L.ptr(tiles),
                    rb.K, rb.cap, Cs, Cd, n_dst, R, G, L.ptr(addend), L.ptr(dst), L.ptr(ws), L.ptr(partial), float(flops), L.stream())
     elif route == 'ts':
@@ -532,25 +550,30 @@ def set_profile_flops(on: bool):
     account.enable(on)
 
 
+def _roles(rb: Rulebook, mode: str, transposed: bool = False):
+    """(gather rows, scatter rows, role of the scattered side, its row count) of a launch over ``rb``.  mode 'fwd' reads pair_in rows
+    and writes pair_out rows (SubM and strided conv), 'inv' the other way round (SparseInverseConv3d); the input gradient
+    (``transposed``) swaps them once more.  The weight gradient walks the forward's roles."""
+    if (mode == 'fwd') != transposed:
+        return rb.pair_in, rb.pair_out, 'out', rb.n_out
+    return rb.pair_out, rb.pair_in, 'in', rb.n_in
+
+
 class _SparseConvFn(torch.autograd.Function):
-    """mode: 'fwd' (src rows = pair_in, dst rows = pair_out; SubM and strided conv) or
-    'inv' (roles swapped; SparseInverseConv3d)."""
+    """mode: 'fwd' or 'inv' (``_roles``).  ``stats``: ``_gmm``'s, a dict that ``sparse_conv`` owns."""
 
     @staticmethod
-    def forward(ctx, src, weight, rb: Rulebook, mode: str, addend, stats_out=None):
+    def forward(ctx, src, weight, rb: Rulebook, mode: str, addend, stats=None):
         cout, cin = weight.shape[0], weight.shape[-1]
         w = weight.reshape(cout, rb.K, cin)
         src = src.contiguous()
-        if mode == 'fwd':
-            g, s, role, n_dst = rb.pair_in, rb.pair_out, 'out', rb.n_out
-        else:
-            g, s, role, n_dst = rb.pair_out, rb.pair_in, 'in', rb.n_in
+        g, s, role, n_dst = _roles(rb, mode)
         flops = 2.0 * rb.total_pairs * cin * cout if _PROFILE_FLOPS else 0.0
         ctx.bf = P.conv_format()
         ctx.rows = ctx.bf == P.FMT_BF16 and P.bf16_rows() and cin % 32 == 0
         ctx.src_shadow = shadow_of(src) if ctx.rows else None          # bf16 rows of src: gathered here and by the weight gradient
         dst = _gmm(src, w.contiguous(), False, rb, g, s, role, n_dst, None if addend is None else addend.contiguous(), flops, ctx.bf,
-                   stats_out, ctx.src_shadow)
+                   stats, ctx.src_shadow)
         ctx.save_for_backward(src, weight)
         ctx.rb, ctx.mode, ctx.has_addend = rb, mode, addend is not None
         return dst
@@ -567,10 +590,7 @@ class _SparseConvFn(torch.autograd.Function):
         dout_shadow = shadow_of(dout) if ctx.bf == P.FMT_BF16 and P.bf16_rows() and cout % 32 == 0 else None
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(weight)
-            if mode == 'fwd':
-                rx, rg, role, n_dy = rb.pair_in, rb.pair_out, 'out', rb.n_out
-            else:
-                rx, rg, role, n_dy = rb.pair_out, rb.pair_in, 'in', rb.n_in
+            rx, rg, role, n_dy = _roles(rb, mode)
             if _PROFILE_FLOPS:
                 account.add('conv_wgrad', flops, 4.0 * (src.shape[0] * cin + n_dy * cout) + 8.0 * rb.total_pairs + 4.0 * rb.K * cin * cout)
             Tw = L.lib().u3d_spconv_wgrad_tile_rows(rb.K, n_dy, cin, cout)
@@ -600,10 +620,7 @@ class _SparseConvFn(torch.autograd.Function):
             else:
                 launch()
         if ctx.needs_input_grad[0]:
-            if mode == 'fwd':
-                g, s, role, n_dst = rb.pair_out, rb.pair_in, 'in', rb.n_in
-            else:
-                g, s, role, n_dst = rb.pair_in, rb.pair_out, 'out', rb.n_out
+            g, s, role, n_dst = _roles(rb, mode, transposed=True)
             dsrc = _gmm(dout, weight.reshape(cout, rb.K, cin).contiguous(), True, rb, g, s, role, n_dst, None, flops, ctx.bf,
                         None, dout_shadow)
         if side is not None:          # mode 1: joined only now, after the input gradient was queued next to it
@@ -611,8 +628,13 @@ class _SparseConvFn(torch.autograd.Function):
         return dsrc, dw, None, None, (dout if ctx.has_addend else None), None
 
 
-def sparse_conv(src, weight, rb, mode='fwd', addend=None, stats_out=None):
-    dst = _SparseConvFn.apply(src, weight, rb, mode, addend, stats_out)
+def sparse_conv(src, weight, rb, mode='fwd', addend=None, want_stats=False):
+    """``want_stats``: a batch norm in training mode reads the result: what the launch wrote for it (``_gmm``) rides on the returned
+    tensor (``stats_of``)."""
+    st = {} if want_stats else None
+    dst = _SparseConvFn.apply(src, weight, rb, mode, addend, st)
+    if st:
+        attach_stats(dst, st['partial'], st['n_tiles'])
     if P.bf16_rows():
         dst._u3d_from_conv = True      # the batch norm behind this output hands its gradient back with a bf16 shadow (bf16_rows)
     return dst
@@ -635,48 +657,47 @@ def allreduce_bn_sums(sums: torch.Tensor, group=None):
 
 class _BNReLUFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, relu, training, sync, nbt=None, want_skip=False,
-                stats=None, yb=None, dx_shadow=False):
-        """``stats``: dict(partial, n_tiles) from the epilogue of the convolution that produced x (``_gmm``'s ``stats_out``), or None.
+    def forward(ctx, cfg, x, gamma, beta, running_mean, running_var):
+        """``cfg``: everything that is not a tensor autograd tracks, as one object that stays on ctx (built by ``SparseBatchNorm.forward``):
+        eps, momentum, relu, training, sync, want_skip, and
+        ``nbt``: num_batches_tracked where the statistics kernel is to increment it, else None;
+        ``stats``: (partial, n_tiles) from the epilogue of the convolution that produced x (``stats_of``), or None;
         ``yb`` (bf16 [n, C] or None): receives y rounded to bf16 in the same pass (precision.bf16_rows); ``dx_shadow``: the backward
         writes such a copy of dx too and attaches it to the gradient it returns (x came out of a sparse convolution)."""
         x = x.contiguous()
         n, C = x.shape
         dev = x.device
-        ctx.dx_shadow = bool(dx_shadow)
+        relu, yb, nbt = int(cfg.relu), cfg.yb, cfg.nbt
         st = torch.empty(4, C, dtype=torch.float32, device=dev)     # mean, invstd, scale, shift
         y = torch.empty_like(x)
         ws = L.scratch(L.lib().u3d_bn_ws_bytes(C), dev)
-        part, n_tiles = (stats['partial'], stats['n_tiles']) if stats else (None, 0)
-        sums = None
-        sync_on = sync and _dist_on()
-        if training and (n or sync_on):           # a rank without rows still joins the exchange (zero sums, zero count), like nn.SyncBatchNorm
-            sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)   # [sum x, sum x^2, rows]
-            if sync_on:
+        part, n_tiles = cfg.stats or (None, 0)
+        sync_on = cfg.sync and _dist_on()
+        batch = cfg.training and (n or sync_on)   # a rank without rows still joins the exchange (zero sums, zero count), like nn.SyncBatchNorm
+        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev) if batch else None      # [sum x, sum x^2, rows]
+        if batch and not sync_on:                 # one call: stats -> finalize -> apply
+            L.call('u3d_bn_forward', L.ptr(x), n, C, L.ptr(part), n_tiles, L.ptr(gamma), L.ptr(beta), cfg.eps, cfg.momentum,
+                   L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt), relu, L.ptr(y), L.ptr(yb), L.ptr(st), L.ptr(sums), L.ptr(ws), L.stream())
+        else:
+            if batch:
                 if n:
                     L.call('u3d_bn_stats', L.ptr(x), n, C, L.ptr(part), n_tiles, L.ptr(sums), L.ptr(ws), L.stream())
                 else:
                     sums.zero_()
-                allreduce_bn_sums(sums)          # rows ride along: no host read-back on the critical path
-                L.call('u3d_bn_finalize', L.ptr(sums), -1.0, L.ptr(gamma), L.ptr(beta), eps, momentum,
-                       L.ptr(running_mean), L.ptr(running_var), C, L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]),
-                       L.ptr(st[3]), L.ptr(nbt), L.stream())
-                if n:
-                    L.call('u3d_bn_apply', L.ptr(x), L.ptr(st[2]), L.ptr(st[3]), int(relu), n, C, L.ptr(y), L.ptr(yb), L.stream())
-            else:                                # one call: stats -> finalize -> apply
-                L.call('u3d_bn_forward', L.ptr(x), n, C, L.ptr(part), n_tiles, L.ptr(gamma), L.ptr(beta), eps, momentum, L.ptr(running_mean),
-                       L.ptr(running_var), L.ptr(nbt), int(relu), L.ptr(y), L.ptr(yb), L.ptr(st), L.ptr(sums), L.ptr(ws), L.stream())
-        else:
-            st[0] = running_mean
-            st[1] = torch.rsqrt(running_var + eps)
-            st[2] = gamma * st[1]
-            st[3] = beta - running_mean * st[2]
+                allreduce_bn_sums(sums)           # rows ride along: no host read-back on the critical path
+                L.call('u3d_bn_finalize', L.ptr(sums), -1.0, L.ptr(gamma), L.ptr(beta), cfg.eps, cfg.momentum, L.ptr(running_mean),
+                       L.ptr(running_var), C, L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), L.ptr(nbt), L.stream())
+            else:                                 # the running statistics
+                st[0] = running_mean
+                st[1] = torch.rsqrt(running_var + cfg.eps)
+                st[2] = gamma * st[1]
+                st[3] = beta - running_mean * st[2]
             if n:
-                L.call('u3d_bn_apply', L.ptr(x), L.ptr(st[2]), L.ptr(st[3]), int(relu), n, C, L.ptr(y), L.ptr(yb), L.stream())
+                L.call('u3d_bn_apply', L.ptr(x), L.ptr(st[2]), L.ptr(st[3]), relu, n, C, L.ptr(y), L.ptr(yb), L.stream())
         ctx.save_for_backward(x, st, sums)
-        ctx.relu, ctx.training, ctx.sync, ctx.want_skip = relu, training, sync, want_skip
+        ctx.cfg = cfg
         ctx.set_materialize_grads(False)          # an unused skip output sends None, not a zero tensor
-        if want_skip:
+        if cfg.want_skip:
             # second output = x itself, for the identity branch that leaves the block input next to this norm (residual skip,
             # U-Net concat): its gradient then arrives HERE, together with dy, and is added inside the backward kernel
             # instead of by autograd's accumulation kernel
@@ -685,48 +706,47 @@ class _BNReLUFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dskip=None):
+        cfg = ctx.cfg
         x, st, fsums = ctx.saved_tensors
-        if dy is None:                                 # only the identity branch carried a gradient
-            return (dskip,) + (None,) * 14
-        dy = dy.contiguous()
-        dskip = None if dskip is None else dskip.contiguous()
-        n, C = x.shape
-        dev = x.device
-        dx = torch.empty_like(x)
-        dxb = torch.empty(n, C, dtype=torch.bfloat16, device=dev) if ctx.dx_shadow and n else None
-        # dgamma, dbeta (local sums: DDP averages later); separate tensors so that autograd can adopt them as .grad without a copy
-        dgb = [torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)]
-        if not n:
-            if ctx.training and fsums is not None and ctx.sync and _dist_on():     # keep the collective sequence of the other ranks
-                dist.all_reduce(torch.zeros(2 * C, dtype=torch.float64, device=dev), op=dist.ReduceOp.SUM)
-            return dx, dgb[0].zero_(), dgb[1].zero_(), None, None, None, None, None, None, None, None, None, None, None, None
-        ws = L.scratch(L.lib().u3d_bn_ws_bytes(C), dev)
-        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
-        if ctx.training and fsums is not None:
-            if ctx.sync and _dist_on():
-                sums[2 * C:] = fsums[2 * C:]         # global row count of the forward pass
-                L.call('u3d_bn_bwd_stats', L.ptr(x), L.ptr(dy), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]),
-                       int(ctx.relu), n, C, L.ptr(sums), L.ptr(ws), L.stream())
-                dgb[1] = sums[:C].to(torch.float32)
-                dgb[0] = sums[C:2 * C].to(torch.float32)
-                dist.all_reduce(sums[:2 * C], op=dist.ReduceOp.SUM)
-                L.call('u3d_bn_bwd_apply', L.ptr(x), L.ptr(dy), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]),
-                       int(ctx.relu), L.ptr(sums), -1.0, n, C, L.ptr(dx), L.ptr(dxb), None, None, L.ptr(dskip), L.stream())
-            else:                                    # one call: bwd_stats -> bwd_apply (+ dgamma / dbeta)
-                L.call('u3d_bn_backward', L.ptr(x), L.ptr(dy), L.ptr(st), int(ctx.relu), L.ptr(fsums), L.ptr(sums), n, C, L.ptr(dx), L.ptr(dxb),
-                       L.ptr(dgb[0]), L.ptr(dgb[1]), L.ptr(dskip), L.ptr(ws), L.stream())
-        else:                                        # eval: statistics are constants -> dx = scale * dy'
-            L.call('u3d_bn_bwd_stats', L.ptr(x), L.ptr(dy), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]),
-                   int(ctx.relu), n, C, L.ptr(sums), L.ptr(ws), L.stream())
-            dgb[1] = sums[:C].to(torch.float32)
-            dgb[0] = sums[C:2 * C].to(torch.float32)
-            sums.zero_()
-            sums[2 * C] = 1.0
-            L.call('u3d_bn_bwd_apply', L.ptr(x), L.ptr(dy), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]),
-                   int(ctx.relu), L.ptr(sums), -1.0, n, C, L.ptr(dx), L.ptr(dxb), None, None, L.ptr(dskip), L.stream())
-        if dxb is not None:
-            attach_shadow(dx, dxb)
-        return dx, dgb[0], dgb[1], None, None, None, None, None, None, None, None, None, None, None, None
+        dx, dgb = dskip, [None, None]                  # as they stay when only the identity branch carried a gradient
+        if dy is not None:
+            dy = dy.contiguous()
+            dskip = None if dskip is None else dskip.contiguous()
+            n, C = x.shape
+            dev = x.device
+            dx = torch.empty_like(x)
+            dxb = torch.empty(n, C, dtype=torch.bfloat16, device=dev) if cfg.dx_shadow and n else None
+            # dgamma, dbeta (local sums: DDP averages later); separate tensors so that autograd can adopt them as .grad without a copy
+            dgb = [torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)]
+            batch = cfg.training and fsums is not None          # the forward normalised with batch statistics
+            sync_on = batch and cfg.sync and _dist_on()
+            if not n:
+                if sync_on:                              # keep the collective sequence of the other ranks
+                    dist.all_reduce(torch.zeros(2 * C, dtype=torch.float64, device=dev), op=dist.ReduceOp.SUM)
+                dgb[0].zero_()
+                dgb[1].zero_()
+            else:
+                ws = L.scratch(L.lib().u3d_bn_ws_bytes(C), dev)
+                sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+                xdy = (L.ptr(x), L.ptr(dy), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), int(cfg.relu))
+                if batch and not sync_on:                # one call: bwd_stats -> bwd_apply (+ dgamma / dbeta)
+                    L.call('u3d_bn_backward', L.ptr(x), L.ptr(dy), L.ptr(st), int(cfg.relu), L.ptr(fsums), L.ptr(sums), n, C, L.ptr(dx), L.ptr(dxb),
+                           L.ptr(dgb[0]), L.ptr(dgb[1]), L.ptr(dskip), L.ptr(ws), L.stream())
+                else:
+                    if sync_on:
+                        sums[2 * C:] = fsums[2 * C:]     # global row count of the forward pass
+                    L.call('u3d_bn_bwd_stats', *xdy, n, C, L.ptr(sums), L.ptr(ws), L.stream())
+                    dgb[1] = sums[:C].to(torch.float32)
+                    dgb[0] = sums[C:2 * C].to(torch.float32)
+                    if sync_on:
+                        dist.all_reduce(sums[:2 * C], op=dist.ReduceOp.SUM)
+                    else:                                # eval: statistics are constants -> dx = scale * dy'
+                        sums.zero_()
+                        sums[2 * C] = 1.0
+                    L.call('u3d_bn_bwd_apply', *xdy, L.ptr(sums), -1.0, n, C, L.ptr(dx), L.ptr(dxb), None, None, L.ptr(dskip), L.stream())
+                if dxb is not None:
+                    attach_shadow(dx, dxb)
+        return None, dx, dgb[0], dgb[1], None, None
 
 
 class SparseBatchNorm(nn.Module):
@@ -744,24 +764,31 @@ class SparseBatchNorm(nn.Module):
         self.register_buffer('running_var', torch.ones(num_features))
         self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
 
-    def forward(self, x: torch.Tensor, relu: bool = False, skip: bool = False, stats=None, shadow: bool = True):
+    def forward(self, x: torch.Tensor, relu: bool = False, skip: bool = False, shadow: bool = True):
         """``skip=True`` -> (y, x_id): ``x_id`` is x for a second consumer (the identity branch next to this norm); the gradient that
         consumer sends back is added to dx inside this layer's backward kernel.
-        ``stats``: the per-tile column sums the producing convolution's epilogue wrote for exactly this ``x``
-        (``SparseConvTensor.stats_for``): the statistics then cost no pass over x."""
+        In training mode the per-tile column sums the producing convolution's epilogue attached to exactly this ``x`` (``stats_of``)
+        are used where there are any: the statistics then cost no pass over x."""
         # bf16 operands with bf16 rows in HBM (precision.bf16_rows): y (when a ReLU follows -- the input of a sparse convolution -- and
         # the channel count suits the bf16 kernels) and the gradient handed back to a producing convolution get a bf16 shadow
         rows = P.bf16_rows() and x.is_cuda and x.shape[0] > 0 and x.shape[1] % 32 == 0
         yb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if rows and relu and shadow else None
-        dx_shadow = rows and getattr(x, '_u3d_from_conv', False)
         # num_batches_tracked is incremented by the statistics kernel (one launch less per layer)
-        out = _BNReLUFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
-                              self.momentum, relu, self.training, self.sync,
-                              self.num_batches_tracked if self.training and (x.shape[0] or (self.sync and _dist_on())) else None, skip,
-                              stats if self.training else None, yb, dx_shadow)
+        cfg = SimpleNamespace(eps=self.eps, momentum=self.momentum, relu=relu, training=self.training, sync=self.sync, want_skip=skip,
+                              nbt=self.num_batches_tracked if self.training and (x.shape[0] or (self.sync and _dist_on())) else None,
+                              stats=stats_of(x) if self.training else None, yb=yb, dx_shadow=bool(rows and getattr(x, '_u3d_from_conv', False)))
+        out = _BNReLUFn.apply(cfg, x, self.weight, self.bias, self.running_mean, self.running_var)
         if yb is not None:
             attach_shadow(out[0] if skip else out, yb)
         return out
+
+    def on(self, x: 'SparseConvTensor', relu: bool = False, skip: bool = False, *, feeds_conv: bool):
+        """This norm on a sparse tensor: the new tensor, and with ``skip`` the identity tensor (``forward``'s x_id) as well.
+        ``feeds_conv``: a sparse convolution reads the result (with ``relu``, the only reader a bf16 shadow of y is of use to)."""
+        out = self(x.features, relu=relu, skip=skip, shadow=feeds_conv)
+        if skip:
+            return x.replace_feature(out[0]), x.replace_feature(out[1])
+        return x.replace_feature(out)
 
 
 # ----------------------------------------------------------------------------------------
@@ -775,18 +802,9 @@ class SparseConvTensor:
         self.batch_size = int(batch_size)
         self.indice_dict = {} if indice_dict is None else indice_dict
         self._index = index
-        self.stats = None           # set by the convolution that produced ``features`` (training): dict(partial, n_tiles, owner)
 
-    def replace_feature(self, new_features, stats=None):
-        t = SparseConvTensor(new_features, self.indices, self.spatial_shape, self.batch_size,
-                             self.indice_dict, self._index)
-        if stats:
-            t.stats = dict(stats, owner=new_features)
-        return t
-
-    def stats_for(self, features):
-        """The convolution-epilogue statistics, if they were produced for exactly this feature tensor."""
-        return self.stats if self.stats is not None and self.stats.get('owner') is features and 'partial' in self.stats else None
+    def replace_feature(self, new_features):
+        return SparseConvTensor(new_features, self.indices, self.spatial_shape, self.batch_size, self.indice_dict, self._index)
 
     @property
     def index(self) -> OccupancyIndex:
@@ -831,7 +849,7 @@ class SparseSequential(SparseModule):
             elif isinstance(m, SparseBatchNorm):
                 fuse = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
                 feeds_conv = fuse and i + 2 < len(mods) and isinstance(mods[i + 2], _ConvBase)      # only then a bf16 shadow of y is of use
-                x = x.replace_feature(m(x.features, relu=fuse, stats=x.stats_for(x.features), shadow=feeds_conv))
+                x = m.on(x, relu=fuse, feeds_conv=feeds_conv)
                 i += 1 if fuse else 0
             elif isinstance(m, nn.Identity):
                 pass
@@ -872,6 +890,10 @@ class _ConvBase(SparseModule):
         c = self.in_channels
         return self.weight if c % 16 == 0 else F.pad(self.weight, (0, 16 - c % 16))
 
+    def _conv(self, x: 'SparseConvTensor', rb: Rulebook, mode: str, addend=None) -> torch.Tensor:
+        """pad -> sparse_conv -> result features; in training mode with the statistics for a norm behind this layer asked for"""
+        return sparse_conv(_pad16(x.features), self._w16(), rb, mode, addend, self.training)
+
 
 class SubMConv3d(_ConvBase):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None):
@@ -884,8 +906,7 @@ class SubMConv3d(_ConvBase):
             # library picked a 0.6 ms kernel for the level-1 weight gradient, a [64 x 356k] x [356k x 32] product)
             y = dense.linear(x.features, self.weight.view(self.out_channels, self.in_channels))
             return x.replace_feature(y if addend is None else y + addend)
-        st = {} if self.training else None
-        return x.replace_feature(sparse_conv(_pad16(x.features), self._w16(), self.geometry(x), 'fwd', addend, st), st)
+        return x.replace_feature(self._conv(x, self.geometry(x), 'fwd', addend))
 
     def geometry(self, x: SparseConvTensor) -> Rulebook:
         key = self.indice_key if self.indice_key is not None else ('__subm__', id(self))
@@ -904,12 +925,7 @@ class SparseConv3d(_ConvBase):
 
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
         oc, oshape, ix2, rb = self.geometry(x)
-        st = {} if self.training else None
-        f = sparse_conv(_pad16(x.features), self._w16(), rb, 'fwd', None, st)
-        out = SparseConvTensor(f, oc, oshape, x.batch_size, x.indice_dict, ix2)
-        if st:
-            out.stats = dict(st, owner=f)
-        return out
+        return SparseConvTensor(self._conv(x, rb, 'fwd'), oc, oshape, x.batch_size, x.indice_dict, ix2)
 
     def geometry(self, x: SparseConvTensor):
         """Coarser level + rulebook for this conv; cached in ``indice_dict`` (the inverse conv reads the
@@ -931,9 +947,4 @@ class SparseInverseConv3d(_ConvBase):
         if self.indice_key not in x.indice_dict:
             raise L.U3DError(f'SparseInverseConv3d: no rulebook saved under {self.indice_key!r}')
         rb, idx, shape, index = x.indice_dict[self.indice_key]
-        st = {} if self.training else None
-        f = sparse_conv(_pad16(x.features), self._w16(), rb, 'inv', None, st)
-        out = SparseConvTensor(f, idx, shape, x.batch_size, x.indice_dict, index)
-        if st:
-            out.stats = dict(st, owner=f)
-        return out
+        return SparseConvTensor(self._conv(x, rb, 'inv'), idx, shape, x.batch_size, x.indice_dict, index)

@@ -8,7 +8,9 @@ deconv.{0,2}, blocks_tail.*), so OneFormer3D / UniDet3D checkpoints load unchang
 Differences are all below the module surface: convolutions, rulebooks and batch-norm run as
 HIP kernels through include/u3d.h, BN+ReLU is one fused kernel, and the residual add of
 ``ResidualBlock.forward`` (:88-89) is folded into the accumulator init of the block's last
-convolution.
+convolution.  A norm that does not sit in a ``SparseSequential`` of its own (the two of a block, the one the U-Net's skip
+connection leaves next to) runs through ``SparseBatchNorm.on``, which also says that a convolution reads the result; what a
+convolution leaves for the norm behind it travels on the feature tensor (``sparse.stats_of``), not through these classes.
 """
 from __future__ import annotations
 
@@ -55,12 +57,10 @@ class ResidualBlock(SparseModule):
         mods = list(self.conv_branch._modules.values())
         # the block input feeds the first norm AND the skip branch: the norm hands the input back as a second output so that
         # both gradients meet inside its backward kernel (no accumulation kernel)
-        # (statistics of both norms come from the epilogue of the convolution that produced their input, when there was one)
-        y, x_id = mods[0](input.features, relu=True, skip=True, stats=input.stats_for(input.features))
-        skip = self.i_branch(input.replace_feature(x_id)).features
-        x = input.replace_feature(y)
-        x = mods[2](x)
-        x = x.replace_feature(mods[3](x.features, relu=True, stats=x.stats_for(x.features)))
+        # (each norm finds the statistics of its input on that tensor, when a convolution's epilogue wrote them: sparse.stats_of)
+        x, identity = mods[0].on(input, relu=True, skip=True, feeds_conv=True)
+        skip = self.i_branch(identity).features
+        x = mods[3].on(mods[2](x), relu=True, feeds_conv=True)
         return mods[5](x, addend=skip)          # conv + residual in one kernel
 
 
@@ -122,9 +122,8 @@ class SpConvUNet(nn.Module):
         if len(self.num_planes) > 1:
             cm = list(self.conv._modules.values())
             if isinstance(cm[0], SparseBatchNorm) and len(cm) == 3:       # normalize_before: the skip connection leaves next to a norm
-                y, x_id = cm[0](output.features, relu=True, skip=True, stats=output.stats_for(output.features))
-                identity = output.replace_feature(x_id)
-                dec = cm[2](output.replace_feature(y))
+                y, identity = cm[0].on(output, relu=True, skip=True, feeds_conv=True)
+                dec = cm[2](y)
             else:
                 dec = self.conv(output)
             if self.return_blocks:
