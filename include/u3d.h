@@ -349,7 +349,9 @@ int u3d_segment_mean_xyz(const float* points, int pt_ld, const int32_t* list, co
 
 /* out[s] = [min xyz, max xyz] of (xyz - sub[scene]) over the points with ids[p] == s (ids < 0 are skipped):
  * the axis-aligned GT boxes of UniDet3D.get_bboxes_by_masks (unidet3d/unidet3d.py:220-256) for a whole batch in one
- * pass.  Segments without points return [+FLT_MAX-like, -FLT_MAX-like] sentinels.  ws: n_seg*6*4 bytes. */
+ * pass.  A segment without points returns NaN in all six components, whichever chunk of segments holds it (the untouched
+ * ordered keys INT_MAX / INT_MIN decode to the bit patterns 0x7fffffff / 0xffffffff): an absent instance is loud, not a box of
+ * plausible size.  ws: n_seg*6*4 bytes. */
 int u3d_segment_minmax_xyz(const float* points, int pt_ld, const int64_t* ids, int64_t n, int n_seg, const float* sub,
                            int sub_ld, const int64_t* pt_offsets, int B, float* out /*[n_seg,6]*/, void* ws,
                            u3d_stream_t stream);

@@ -107,9 +107,16 @@ class PoolPlan:
         self.vox_offsets = vb.vox_offsets
 
 
+def _need_fp32(t: torch.Tensor, what: str):
+    """the pooling kernel reads rows as float4 through the raw pointer: any other dtype would be reinterpreted, not converted"""
+    if t.dtype != torch.float32:
+        raise L.U3DError(f'superpoint_pool: {what} must be float32, got {t.dtype}')
+
+
 class _PoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, plan: PoolPlan):
+        _need_fp32(feats, 'feats')
         feats = feats.contiguous()
         C = feats.shape[1]
         out = torch.empty(plan.S, C, dtype=torch.float32, device=feats.device)
@@ -121,6 +128,7 @@ class _PoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         plan = ctx.plan
+        _need_fp32(dout, 'the gradient of the pooled tensor')
         dout = dout.contiguous()
         C = dout.shape[1]
         df = torch.empty(plan.n_vox, C, dtype=torch.float32, device=dout.device)
