@@ -1,4 +1,4 @@
-"""head_dim 64 in the varlen flash attention kernels (csrc/attn_x3_hd64.h), forward and backward, in the three data flows of the default
+"""head_dim 64 in the varlen flash attention kernels (csrc/attn_x3.hip at HD = 64), forward and backward, in the three data flows of the default
 and the bf16 configurations: fp32 tensors with three bf16 planes per operand, fp32 tensors with bf16 operands, bf16 tensors.
 
 Kernel tests against float64 softmax attention per scene and its autograd (the reference of tests/test_gpu_model.py
@@ -142,13 +142,14 @@ def test_head_dim_64_bf16_operands_and_bf16_tensors(lens):
     assert float((out.double().cpu() - ref).abs().mean() / ref.abs().mean()) < 1e-2
 
 
+@pytest.mark.parametrize('H, hd', [(8, 32), (4, 64)])
 @pytest.mark.parametrize('mode', ['fp32', 'bf16_operands', 'bf16_tensors'])
-def test_head_dim_64_scenes_do_not_read_each_other(mode):
+def test_scenes_do_not_read_each_other(mode, H, hd):
     """Scene 1's rows of qkv and dout hold 1e30: scene 0's out and dqkv must be bit-equal to a run with scene 1 removed -- no key tile and
-    no transpose read crosses a scene boundary at the wider row."""
+    no transpose read crosses a scene boundary at either row width."""
     import contextlib
     from unidet3d_amd import precision as P
-    H, hd, lens = 4, 64, [64, 65]
+    lens = [64, 65]
     qkv, go = _inputs(tuple(lens), H * hd, 1.0, mode != 'fp32')
     qkv, go = qkv.clone(), go.clone()
     qkv[64:] = 1e30; go[64:] = 1e30
@@ -160,11 +161,12 @@ def test_head_dim_64_scenes_do_not_read_each_other(mode):
     assert torch.equal(out2[:64], out1) and torch.equal(dx2[:64], dx1)
 
 
-def test_head_dim_64_is_deterministic():
+@pytest.mark.parametrize('H, hd', [(8, 32), (4, 64)])
+def test_attention_is_deterministic(H, hd):
     """two forward + backward passes, bit-equal: no floating-point atomics"""
     lens = [513, 300]
-    qkv, go = _inputs(tuple(lens), 256)
-    a, b = _run(qkv, go, lens, 4), _run(qkv, go, lens, 4)
+    qkv, go = _inputs(tuple(lens), H * hd)
+    a, b = _run(qkv, go, lens, H), _run(qkv, go, lens, H)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 

@@ -116,7 +116,7 @@ def main():
 
     def cell(xs, flops):
         m = statistics.median(xs)
-        return f'{m:8.3f} | {q(xs, 0.1):8.3f} | {q(xs, 0.9):8.3f} ms  {flops / m * 1e-9:7.1f} TFLOP/s'
+        return f'{m:8.4f} | {q(xs, 0.1):8.4f} | {q(xs, 0.9):8.4f} ms  {flops / m * 1e-9:7.1f} TFLOP/s'
     ff, fb = 4.0 * B * n * n * D, 10.0 * B * n * n * D
     lines = [f'varlen attention, {B} scenes x {n} queries, D = {D}: {ff * 1e-9:.1f} GFLOP forward, {fb * 1e-9:.1f} GFLOP backward (algorithmic, the same for every head split); '
              f'{torch.cuda.get_device_name(0)}; {args.warmup} warm-up + {args.reps} timed rounds, variants alternating inside a round',

@@ -4,7 +4,8 @@ The .s files come from the build's own command plus --offload-device-only -S (un
 A kernel's text is what lies between its `Begin function` and `End function` markers, without comments, with its own mangled
 name replaced by a placeholder and the function index dropped from the .LBB<n>_ and .Lfunc_end<n> labels; section-switch directives
 (.text / .section: a template kernel lies in a comdat section of its own) are dropped as well.  A kernel of the new build that has no
-namesake in the parent is matched through the `new=old` arguments (substrings of the demangled names): it replaced that kernel.
+namesake in the parent is matched through the `new=old` arguments (substrings of the demangled names; a comma separates two old names
+only where no space follows it, so `k<3, false>` is one substring): it replaced that kernel.
 One line per kernel of the new build: demangled name, same / differs, VGPR / SGPR / LDS / scratch of parent -> new."""
 import glob
 import os
@@ -47,7 +48,7 @@ def main():
             refs = [(old.get((os.path.basename(f), name)), '')]
             if refs[0][0] is None:         # renamed: every kernel it replaced, in any file of the parent
                 refs = [(v, f'   (replaces {old_dn[k]})') for a, b in renames if a in dn[name]
-                        for (_, k), v in old.items() if any(x in old_dn[k] for x in b.split(','))]
+                        for (_, k), v in old.items() if any(x in old_dn[k] for x in re.split(r',(?! )', b))]
             if not refs:
                 print(f'{os.path.basename(f)[:-2]}: {dn[name]} | NEW, nothing to compare | {res}')
                 n_diff += 1

@@ -1,6 +1,6 @@
 // K13 self-attention core on gfx950: varlen (cu_seqlens-packed) flash attention, fp32 in / fp32
 // accumulate on v_mfma_f32_16x16x4_f32, head_dim 32 (this is the native arm of the fp32 path; head_dim 64
-// runs on the plane kernels only, attn_x3_hd64.h).  Replaces the math path of
+// runs on the plane kernels only, attn_x3.hip).  Replaces the math path of
 // nn.MultiheadAttention(256, 8, batch_first=True) at unidet3d/encoder.py:19-20,36-37 (called per
 // scene in a Python loop by the reference); the n x n score matrix never leaves the CU.
 //
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(const float* __restrict__ 
     }
 }
 
-// head dims: 32 and 64 in the plane kernels (attn_x3.hip / attn_x3_hd64.h: every mode but ATTN_NATIVE); the native fp32 MFMA kernels above are the
+// head dims: 32 and 64 in the plane kernels (attn_x3.hip, one template over the head dim: every mode but ATTN_NATIVE); the native fp32 MFMA kernels above are the
 // A/B arm of the default fp32 path and stay at 32.  Decided before the first HIP call (tests/test_cabi.py runs this without a device).
 static int attn_check_hd(AttnMode mode, int hd) {
     if (hd == 32 || (hd == 64 && mode != ATTN_NATIVE)) return U3D_OK;

@@ -1,4 +1,4 @@
-// Shared by the attention kernels of attn.hip (native fp32 MFMA) and attn_x3.hip / attn_x3_hd64.h (bf16 planes): the work decode, the delta
+// Shared by the attention kernels of attn.hip (native fp32 MFMA) and attn_x3.hip (bf16 planes): the work decode, the delta
 // kernel of the backward pass, and the host bodies behind the six u3d_attn_varlen_* entry points.
 #pragma once
 #include "u3d_common.h"

@@ -5,7 +5,7 @@
 // U3D_FP32_MATH=mfma selects the native fp32 MFMA kernels of attn.hip.
 //
 // v_mfma_f32_16x16x32_bf16: lane (i = lane & 15, g = lane >> 4) holds the 8 reduction elements k = 8g .. 8g+7 of row i (A) /
-// column i (B); head_dim = 32 is one instruction's reduction depth (head_dim 64: attn_x3_hd64.h; the helpers both share: attn_x3.h).
+// column i (B).
 //   S^T (16 keys x 16 queries) = K_tile . Q^T       A = K rows, natural [key][dim] planes in LDS (one 16-byte read per plane),
 //                                                   B = own Q rows, split once into registers
 //   O (16 queries x 16 dims) += P . V               A = two C fragments (keys {4g..4g+3} of two 16-key tiles), split in registers,
@@ -14,175 +14,295 @@
 //       block of its lane group (lane t the 8 bytes at key t >> 2, dims 4 (t & 3) ..) and lane t receives dim t over the four keys.
 //       (Rounds 2-3 staged such tensors a second time in a "pair" layout -- two keys per dword, [dim][key-pair slot] -- read with
 //       ds_read_b128; the transpose read makes that copy unnecessary: half the LDS per staged tensor, no second packing and no
-//       dword stores in the staging threads.  Rows 4g + j and 4 (g + 1) + j of a plane differ by 2 in the chunk XOR, so the 32
-//       lanes of a read cover 256 consecutive-bank bytes: conflict-free.)
+//       dword stores in the staging threads.)
 // The backward kernels read their staged tiles in both orientations the same way: rows with ds_read_b128, columns with transpose reads.
-// The kernels are templates over the number of planes: NP = 3 is the fp32 path above, NP = 1 the bf16-operand form of
+// The kernels are templates over the head dim and the number of planes: NP = 3 is the fp32 path above, NP = 1 the bf16-operand form of
 // BASELINE configs[2] (one bf16 value per operand, rounded to nearest even; u3d_attn_varlen_*_bf16 at the end of the file).
+//
+// HD = 32 is one instruction's reduction depth and two 16-column output blocks; what a row of HD = 64 dims changes is counted, not coded:
+//   reduction   S^T = K . Q^T and dP^T = V . dO^T are KK = HD / 32 chained instructions per plane product (dims 32 kk + 8g .. of the
+//               row).  The chain still starts from zero and still runs smallest terms first: all the products of one order of EVERY
+//               reduction block before the next larger order (mfma_x3_2a / _2c).
+//   outputs     O, dQ, dK, dV are CB = HD / 16 blocks of 16 columns; the running sums keep their separate low-order accumulators
+//               (mfma_x3_2b, called per pair of column blocks with the same P / dS operand planes).
+//   staging     a thread holds dims 4c .. 4c+3 (c = tid % (HD / 4)) of the R = HD / 16 rows R p .. R p + R-1 (p = tid / (HD / 4)): 8 (16)
+//               lanes cover a row's 128 (256) bytes.
+//   LDS         the chunk XOR of the unpadded natural planes, xswz<HD> -- the one place where the two widths differ in logic.
+//   registers   DESIGN 4.2 "head_dim 64": no instantiation uses scratch; dK / dV with three planes runs three (HD = 64: two) workgroups
+//               per CU (DKV_WAVES).
 #include <mutex>
 #include <stdlib.h>
 
-#include "attn_x3.h"
+#include "attn_common.h"
 
 namespace u3d {
 
-constexpr int XLD = 32;                  // halves per row of a natural plane: unpadded, the 16-byte chunk index is XORed with (row >> 1) & 3
-                                         // (conflict-free ds_read_b128 for the lane -> (row = lane & 15, chunk = lane >> 4) map)
-constexpr int XN = 64 * XLD;             // halves per natural plane
+constexpr float X_LOG2E = 1.44269504088896340736f, X_LN2 = 0.69314718055994530942f;
+#define U3D_MFMA_X(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-// c += a . b, plane products smallest terms first (attn_x3.h): two independent accumulators side by side (dependent MFMAs wait for
-// their predecessor; alternating chains fills the gaps)
+// c += a . b with both operands in three planes takes h.l, m.m, l.h, h.m, m.h, h.h (smallest terms first).
+// A bf16 MFMA truncates its 32 products at the exponent of its C operand, always towards zero: plane products 2^-8 .. 2^-16 below
+// a running sum lose their low bits every time -- a coherent bias (tools/bias_probe.py: -1.2e-8 mean error after 8 blocks, zero
+// for fp32 MFMAs) that reductions over thousands of rows downstream do not average out.  So chains that start from zero (S, dP)
+// run smallest terms first, and the running sums O / dQ / dK / dV keep the low-order products in accumulators of their own.
+//
+// running sums: the h.h product goes to (c0, c1), the five low-order plane products to their own accumulators (l0, l1), joined
+// once at the end of the kernel (NP = 1, bf16 operands: the one product goes to (c0, c1))
 template <int NP>
-__device__ __forceinline__ void mfma_x3_2a(const bf16x8 (&a0)[NP], const bf16x8 (&a1)[NP], const bf16x8 (&b)[NP], f32x4& c0, f32x4& c1) {
+__device__ __forceinline__ void mfma_x3_2b(const bf16x8 (&a)[NP], const bf16x8 (&b0)[NP], const bf16x8 (&b1)[NP], f32x4& c0, f32x4& c1,
+                                           f32x4& l0, f32x4& l1) {
+#pragma unroll
+    for (int o = NP - 1; o >= 1; --o)
+#pragma unroll
+        for (int qa = 0; qa <= o; ++qa) {
+            l0 = U3D_MFMA_X(a[qa], b0[o - qa], l0);
+            l1 = U3D_MFMA_X(a[qa], b1[o - qa], l1);
+        }
+    c0 = U3D_MFMA_X(a[0], b0[0], c0);
+    c1 = U3D_MFMA_X(a[0], b1[0], c1);
+}
+
+// NP planes of a pair / of eight values: NP = 3 the exact split (u3d_common.h), NP = 1 one bf16 value rounded to nearest even
+// (bf16 operands, BASELINE configs[2])
+template <int NP>
+__device__ __forceinline__ void planes_pair(float a, float b, unsigned (&w)[NP]) {
+    if constexpr (NP == 3) split3_pair(a, b, w[0], w[1], w[2]);
+    else w[0] = pack_bf16(a, b);
+}
+template <int NP>
+__device__ __forceinline__ void planes_x8(const f32x4& lo, const f32x4& hi, bf16x8 (&out)[NP]) {
+    if constexpr (NP == 3) split3_x8(lo, hi, out);
+    else out[0] = bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+}
+
+// own row -> B operand of a bf16 tensor: 8 consecutive dims of row `ptr` (nullptr: zeros), the tensor's own values
+__device__ __forceinline__ void row_frag_x16(const __bf16* ptr, bf16x8 (&out)[1]) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (ptr) v = *reinterpret_cast<const u32x4*>(ptr);
+    out[0] = __builtin_bit_cast(bf16x8, v);
+}
+
+// own row -> B operand planes: 8 consecutive dims of row `ptr` (nullptr: zeros), scaled
+template <int NP>
+__device__ __forceinline__ void row_frag_x3(const float* ptr, float scale, bf16x8 (&out)[NP]) {
+    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
+    if (ptr) { a = *reinterpret_cast<const f32x4*>(ptr); b = *reinterpret_cast<const f32x4*>(ptr + 4); }
+    a *= scale;
+    b *= scale;
+    planes_x8<NP>(a, b, out);
+}
+
+// A operand planes from two C fragments: k = 8g + e <-> row 16 (e >> 2) + 4g + (e & 3) of the 32-row block
+template <int NP>
+__device__ __forceinline__ void pair_frag_x3(const float (&lo)[4], const float (&hi)[4], bf16x8 (&out)[NP]) {
+    planes_x8<NP>(f32x4{lo[0], lo[1], lo[2], lo[3]}, f32x4{hi[0], hi[1], hi[2], hi[3]}, out);
+}
+
+// Natural planes are [64 rows][HD halves], unpadded; the 16-byte chunk index of a row is XORed with xswz<HD>(row), equal for rows r
+// and r + 16.  The bank of byte a is (a / 4) % 64 for both kinds of read.
+// HD = 32: a row is 64 bytes = 4 chunks and the XOR is (row >> 1) & 3.
+//     ds_read_b128, lane -> (row = lane & 15, chunk = lane >> 4): conflict-free.
+//     ds_read_b64_tr_b16: rows 4g + j and 4 (g + 1) + j of a plane differ by 2 in the chunk XOR, so the 32 lanes of a read cover 256
+//               consecutive-bank bytes: conflict-free.
+// HD = 64: a row is 128 bytes = 8 chunks, two rows per 256-byte bank row (row & 1 picks the half), and (row >> 1) & 3 no longer serves
+//     both kinds of read.  With u = (row >> 1) & 7 (bits u2 u1 u0) the XOR is  v(u) = (u1 ^ u2) << 2 | u0 << 1 | u2  (a bijection of u).
+//     ds_read_b128, rows 16 kb + i, logical chunk 4 kk + g: one 16-lane bank group of the instruction holds all sixteen i -- those with
+//               u2 ^ u1 = 0 (i in 0..3, 12..15) with one g, those with u2 ^ u1 = 1 (i in 4..11) with g ^ 1.  Bit 2 of v is u1 ^ u2, so
+//               the first set lands on the four chunks whose bit 2 is that of the logical chunk and the second on the four others, whatever
+//               bit 0 of the logical chunk is; inside a set (v1, v0) = (u0, u2) tells the four u apart.  Eight even rows take the eight
+//               chunks of one half, eight odd rows those of the other: 16 distinct 16-byte slots, conflict-free.
+//     ds_read_b64_tr_b16, dims 16 cb ..: a 32-lane half takes the aligned rows 8n .. 8n+7, 32 bytes (chunks 2 cb, 2 cb + 1) of each.  u2 is
+//               fixed there and (u1, u0) counts the four even (odd) rows, so bits 2..1 of v = (u1 ^ u2, u0) send the four rows to the four
+//               distinct chunk PAIRS of their half (v0 only swaps the two chunks inside a pair): 8 x 32 = 256 distinct bytes,
+//               conflict-free.  (The straight generalisation (row >> 1) & 7 serves the row reads and leaves these reads 2-way.)
+template <int HD>
+__device__ __forceinline__ int xswz(int row) {
+    static_assert(HD == 32 || HD == 64, "head_dim 32 or 64");
+    if constexpr (HD == 32) return (row >> 1) & 3;
+    else return ((((row >> 2) ^ (row >> 3)) & 1) << 2) | (row & 2) | ((row >> 3) & 1);
+}
+template <int HD> constexpr int XN = 64 * HD;          // halves per natural plane
+
+// c += a . b over KK chained 32-deep reduction blocks, two independent accumulators side by side: the plane products smallest terms
+// first (mfma_x3_2b above), every block's products of one order before the next larger order
+template <int NP, int KK>
+__device__ __forceinline__ void mfma_x3_2a(const bf16x8 (&a0)[KK][NP], const bf16x8 (&a1)[KK][NP], const bf16x8 (&b)[KK][NP], f32x4& c0, f32x4& c1) {
 #pragma unroll
     for (int o = NP - 1; o >= 0; --o)
 #pragma unroll
-        for (int qa = 0; qa <= o; ++qa) {
-            c0 = U3D_MFMA_X(a0[qa], b[o - qa], c0);
-            c1 = U3D_MFMA_X(a1[qa], b[o - qa], c1);
-        }
+        for (int kk = 0; kk < KK; ++kk)
+#pragma unroll
+            for (int qa = 0; qa <= o; ++qa) {
+                c0 = U3D_MFMA_X(a0[kk][qa], b[kk][o - qa], c0);
+                c1 = U3D_MFMA_X(a1[kk][qa], b[kk][o - qa], c1);
+            }
 }
 // one chain pair sharing nothing: s += a . b, d += c . e (S and dP of the backward kernels)
-template <int NP>
-__device__ __forceinline__ void mfma_x3_2c(const bf16x8 (&a)[NP], const bf16x8 (&b)[NP], const bf16x8 (&c)[NP], const bf16x8 (&e)[NP], f32x4& s, f32x4& d) {
+template <int NP, int KK>
+__device__ __forceinline__ void mfma_x3_2c(const bf16x8 (&a)[KK][NP], const bf16x8 (&b)[KK][NP], const bf16x8 (&c)[KK][NP], const bf16x8 (&e)[KK][NP], f32x4& s, f32x4& d) {
 #pragma unroll
     for (int o = NP - 1; o >= 0; --o)
 #pragma unroll
-        for (int qa = 0; qa <= o; ++qa) {
-            s = U3D_MFMA_X(a[qa], b[o - qa], s);
-            d = U3D_MFMA_X(c[qa], e[o - qa], d);
-        }
+        for (int kk = 0; kk < KK; ++kk)
+#pragma unroll
+            for (int qa = 0; qa <= o; ++qa) {
+                s = U3D_MFMA_X(a[kk][qa], b[kk][o - qa], s);
+                d = U3D_MFMA_X(c[kk][qa], e[kk][o - qa], d);
+            }
 }
 
-// Stage 64 rows x 32 floats of `base` (rows >= len are zero, values scaled before the split): thread (p = tid >> 3, c = tid & 7)
-// holds dims 4c .. 4c+3 of rows 2p and 2p+1; load_x3 issues the global loads (one tile ahead of their use: the compute phase of
-// the tile before covers their latency), store_x3 splits and writes the natural planes nat[NP][64][XLD] halves.
-struct StageRegs { f32x4 a, b; };
-__device__ __forceinline__ StageRegs load_x3(const float* __restrict__ base, int ld, int row0, int len, int tid) {
-    const int p = tid >> 3, c = tid & 7;
-    const int r0 = row0 + 2 * p;
-    StageRegs r;
-    r.a = f32x4{0.f, 0.f, 0.f, 0.f};
-    r.b = r.a;
-    if (r0 < len) r.a = *reinterpret_cast<const f32x4*>(base + (int64_t)r0 * ld + c * 4);
-    if (r0 + 1 < len) r.b = *reinterpret_cast<const f32x4*>(base + (int64_t)(r0 + 1) * ld + c * 4);
+// Stage 64 rows x HD floats of `base` (rows >= len are zero, values scaled before the split): thread (p = tid / (HD / 4), c = tid % (HD / 4))
+// holds dims 4c .. 4c+3 of the R = HD / 16 rows R p .. R p + R-1; load_x3 issues the global loads (one tile ahead of their use: the
+// compute phase of the tile before covers their latency), store_x3 splits and writes the natural planes nat[NP][64][HD] halves.
+template <int HD> struct StageRegs { f32x4 v[HD / 16]; };
+template <int HD>
+__device__ __forceinline__ StageRegs<HD> load_x3(const float* __restrict__ base, int ld, int row0, int len, int tid) {
+    constexpr int R = HD / 16;
+    const int p = tid / (HD / 4), c = tid % (HD / 4);
+    const int r0 = row0 + R * p;
+    StageRegs<HD> r;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        r.v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (r0 + j < len) r.v[j] = *reinterpret_cast<const f32x4*>(base + (int64_t)(r0 + j) * ld + c * 4);
+    }
     return r;
 }
-template <int NP>
-__device__ __forceinline__ void store_x3(StageRegs r, float scale, __bf16* nat, int tid) {
-    const int p = tid >> 3, c = tid & 7;
-    const f32x4 a = r.a * scale, b = r.b * scale;
-    unsigned wa[2][NP], wb[2][NP];
+template <int HD, int NP>
+__device__ __forceinline__ void store_x3(StageRegs<HD> r, float scale, __bf16* nat, int tid) {
+    constexpr int R = HD / 16;
+    const int p = tid / (HD / 4), c = tid % (HD / 4);
+    unsigned w[R][2][NP];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        planes_pair<NP>(a[2 * j], a[2 * j + 1], wa[j]);
-        planes_pair<NP>(b[2 * j], b[2 * j + 1], wb[j]);
-    }
-    const int off = (((c >> 1) ^ (p & 3)) * 8) + (c & 1) * 4;          // rows 2p and 2p+1 share (row >> 1) & 3 = p & 3
+    for (int j = 0; j < R; ++j) r.v[j] *= scale;
 #pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        *reinterpret_cast<uint2*>(nat + q * XN + (2 * p) * XLD + off) = make_uint2(wa[0][q], wa[1][q]);
-        *reinterpret_cast<uint2*>(nat + q * XN + (2 * p + 1) * XLD + off) = make_uint2(wb[0][q], wb[1][q]);
-    }
+    for (int h = 0; h < 2; ++h)          // the first halves of every row, then the second: the order the kernels were timed with
+#pragma unroll
+        for (int j = 0; j < R; ++j) planes_pair<NP>(r.v[j][2 * h], r.v[j][2 * h + 1], w[j][h]);
+#pragma unroll
+    for (int q = 0; q < NP; ++q)
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const int row = R * p + j;
+            *reinterpret_cast<uint2*>(nat + q * XN<HD> + row * HD + (((c >> 1) ^ xswz<HD>(row)) * 8) + (c & 1) * 4) = make_uint2(w[j][0][q], w[j][1][q]);
+        }
 }
 
 // bf16 tensors in HBM (IO16; one plane, include/u3d.h u3d_attn_varlen_*_b16): the same staging map with 8-byte loads and no arithmetic --
 // the staged values are the tensor's own, so a scale cannot be folded in here (the kernels apply it to the scores / to dK instead)
-struct StageRegs16 { uint2 a, b; };
-__device__ __forceinline__ StageRegs16 load_x16(const __bf16* __restrict__ base, int ld, int row0, int len, int tid) {
-    const int p = tid >> 3, c = tid & 7;
-    const int r0 = row0 + 2 * p;
-    StageRegs16 r;
-    r.a = make_uint2(0u, 0u);
-    r.b = r.a;
-    if (r0 < len) r.a = *reinterpret_cast<const uint2*>(base + (int64_t)r0 * ld + c * 4);
-    if (r0 + 1 < len) r.b = *reinterpret_cast<const uint2*>(base + (int64_t)(r0 + 1) * ld + c * 4);
+template <int HD> struct StageRegs16 { uint2 v[HD / 16]; };
+template <int HD>
+__device__ __forceinline__ StageRegs16<HD> load_x16(const __bf16* __restrict__ base, int ld, int row0, int len, int tid) {
+    constexpr int R = HD / 16;
+    const int p = tid / (HD / 4), c = tid % (HD / 4);
+    const int r0 = row0 + R * p;
+    StageRegs16<HD> r;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        r.v[j] = make_uint2(0u, 0u);
+        if (r0 + j < len) r.v[j] = *reinterpret_cast<const uint2*>(base + (int64_t)(r0 + j) * ld + c * 4);
+    }
     return r;
 }
-__device__ __forceinline__ void store_x16(StageRegs16 r, __bf16* nat, int tid) {
-    const int p = tid >> 3, c = tid & 7;
-    const int off = (((c >> 1) ^ (p & 3)) * 8) + (c & 1) * 4;
-    *reinterpret_cast<uint2*>(nat + (2 * p) * XLD + off) = r.a;
-    *reinterpret_cast<uint2*>(nat + (2 * p + 1) * XLD + off) = r.b;
+template <int HD>
+__device__ __forceinline__ void store_x16(StageRegs16<HD> r, __bf16* nat, int tid) {
+    constexpr int R = HD / 16;
+    const int p = tid / (HD / 4), c = tid % (HD / 4);
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int row = R * p + j;
+        *reinterpret_cast<uint2*>(nat + row * HD + (((c >> 1) ^ xswz<HD>(row)) * 8) + (c & 1) * 4) = r.v[j];
+    }
 }
-template <bool IO16> struct IoT { typedef float t; typedef StageRegs regs; };
-template <> struct IoT<true> { typedef __bf16 t; typedef StageRegs16 regs; };
+template <bool IO16> struct IoT { typedef float t; template <int HD> using regs = StageRegs<HD>; };
+template <> struct IoT<true> { typedef __bf16 t; template <int HD> using regs = StageRegs16<HD>; };
+template <bool IO16> using io_of = typename IoT<IO16>::t;                                        // the tensors' element type
+template <int HD, bool IO16> using io_regs = typename IoT<IO16>::template regs<HD>;            // a thread's share of a staged tile
+template <int HD, bool IO16>
+__device__ __forceinline__ io_regs<HD, IO16> load_io(const io_of<IO16>* __restrict__ base, int ld, int row0, int len, int tid) {
+    if constexpr (IO16) return load_x16<HD>(base, ld, row0, len, tid);
+    else return load_x3<HD>(base, ld, row0, len, tid);
+}
+template <int HD, int NP, bool IO16>
+__device__ __forceinline__ void store_io(io_regs<HD, IO16> r, float scale, __bf16* nat, int tid) {
+    if constexpr (IO16) store_x16<HD>(r, nat, tid);
+    else store_x3<HD, NP>(r, scale, nat, tid);
+}
 template <bool IO16>
-__device__ __forceinline__ typename IoT<IO16>::regs load_io(const typename IoT<IO16>::t* __restrict__ base, int ld, int row0, int len, int tid) {
-    if constexpr (IO16) return load_x16(base, ld, row0, len, tid);
-    else return load_x3(base, ld, row0, len, tid);
-}
-template <int NP, bool IO16>
-__device__ __forceinline__ void store_io(typename IoT<IO16>::regs r, float scale, __bf16* nat, int tid) {
-    if constexpr (IO16) store_x16(r, nat, tid);
-    else store_x3<NP>(r, scale, nat, tid);
-}
-template <bool IO16>
-__device__ __forceinline__ void put_io(typename IoT<IO16>::t* p, float v) {
+__device__ __forceinline__ void put_io(io_of<IO16>* p, float v) {
     if constexpr (IO16) *p = (__bf16)v;
     else *p = v;
 }
 
-// natural planes: rows 16 kb + i, dims 8g .. 8g+7
-template <int NP>
-__device__ __forceinline__ void nat_frag_x3(const __bf16* nat, int kb, int i16, int g, bf16x8 (&out)[NP]) {
+// natural planes: rows 16 kb + i, dims 32 kk + 8g .. 32 kk + 8g+7 of the reduction blocks kk < HD / 32
+template <int HD, int NP>
+__device__ __forceinline__ void nat_frag_x3(const __bf16* nat, int kb, int i16, int g, bf16x8 (&out)[HD / 32][NP]) {
 #pragma unroll
-    for (int q = 0; q < NP; ++q) out[q] = *reinterpret_cast<const bf16x8*>(nat + q * XN + (kb * 16 + i16) * XLD + ((g ^ ((i16 >> 1) & 3)) * 8));
+    for (int kk = 0; kk < HD / 32; ++kk)
+#pragma unroll
+        for (int q = 0; q < NP; ++q)
+            out[kk][q] = *reinterpret_cast<const bf16x8*>(nat + q * XN<HD> + (kb * 16 + i16) * HD + (((4 * kk + g) ^ xswz<HD>(i16)) * 8));      // xswz<HD>(16 kb + i) = xswz<HD>(i)
 }
 
 // natural planes read by COLUMN: dim 16 cb + i16 over rows {4g..4g+3} and {16+4g..16+4g+3} of the 32-row block t (the k order of
 // pair_frag_x3).  ds_read_b64_tr_b16: lane i16 of a 16-lane group passes the address of 4 halves -- row (i16 >> 2) of the group's four,
 // dims 16 cb + 4 (i16 & 3) .. -- and receives dim 16 cb + i16 of the four rows.
-template <int NP>
+template <int HD, int NP>
 __device__ __forceinline__ void tr_col_frag_x3(const __bf16* nat, int t, int g, int i16, int cb, bf16x8 (&out)[NP]) {
     const int row = 32 * t + 4 * g + (i16 >> 2), pc = i16 & 3;
-    const __bf16* s = nat + row * XLD + (((2 * cb + (pc >> 1)) ^ ((row >> 1) & 3)) * 8) + 4 * (pc & 1);      // row + 16 has the same chunk XOR
+    const __bf16* s = nat + row * HD + (((2 * cb + (pc >> 1)) ^ xswz<HD>(row)) * 8) + 4 * (pc & 1);      // row + 16 has the same chunk XOR
 #pragma unroll
-    for (int q = 0; q < NP; ++q) out[q] = tr16_pair(s + q * XN, s + q * XN + 16 * XLD);
+    for (int q = 0; q < NP; ++q) out[q] = tr16_pair(s + q * XN<HD>, s + q * XN<HD> + 16 * HD);
 }
 
-template <int NP, bool IO16 = false>
-__global__ __launch_bounds__(256) void attn_fwd_x3_k(const typename IoT<IO16>::t* __restrict__ qkv, const int32_t* __restrict__ cu, int H, float scale,
-                                                     typename IoT<IO16>::t* __restrict__ out, float* __restrict__ lse, int64_t n_total, int B, int n_tiles) {
+template <int HD, int NP, bool IO16>
+__global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restrict__ qkv, const int32_t* __restrict__ cu, int H, float scale,
+                                                     io_of<IO16>* __restrict__ out, float* __restrict__ lse, int64_t n_total, int B, int n_tiles) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
-    typedef typename IoT<IO16>::t io_t;
-    __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN];
-    __shared__ __attribute__((aligned(16))) __bf16 Vn[NP * XN];
+    typedef io_of<IO16> io_t;
+    constexpr int KK = HD / 32, CB = HD / 16;          // 32-deep reduction blocks of a row | 16-column blocks of an output row
+    __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN<HD>];
+    __shared__ __attribute__((aligned(16))) __bf16 Vn[NP * XN<HD>];
     const AttnWork wk_ = attn_decode(H, B, n_tiles);
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
     const int q0 = wk_.tile * 64;
     if (q0 >= len) return;
-    const int D = H * 32, ld = 3 * D;
+    const int D = H * HD, ld = 3 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
-    const io_t* base = qkv + (int64_t)start * ld + h * 32;
+    const io_t* base = qkv + (int64_t)start * ld + h * HD;
     const int qrow = q0 + wave * 16 + i16;
-    bf16x8 qf[NP];                                // scores in log2 units: q carries scale * log2(e) -- or, IO16, the scores are scaled
-    if constexpr (IO16) row_frag_x16(qrow < len ? base + (int64_t)qrow * ld + g * 8 : nullptr, qf);
-    else row_frag_x3(qrow < len ? base + (int64_t)qrow * ld + g * 8 : nullptr, scale * X_LOG2E, qf);
+    bf16x8 qf[KK][NP];                            // scores in log2 units: q carries scale * log2(e) -- or, IO16, the scores are scaled
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) {
+        if constexpr (IO16) row_frag_x16(qrow < len ? base + (int64_t)qrow * ld + 32 * kk + g * 8 : nullptr, qf[kk]);
+        else row_frag_x3(qrow < len ? base + (int64_t)qrow * ld + 32 * kk + g * 8 : nullptr, scale * X_LOG2E, qf[kk]);
+    }
     const float sc_ = IO16 ? scale * X_LOG2E : 1.f;
     float m = -INFINITY, l = 0.f;
-    f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, ol[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // h.h | low-order products
+    f32x4 o[CB], ol[CB];          // h.h | low-order products
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) o[cb] = ol[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntiles = (len + 63) >> 6;
-    typename IoT<IO16>::regs rk = load_io<IO16>(base + D, ld, 0, len, tid), rv = load_io<IO16>(base + 2 * D, ld, 0, len, tid);
+    io_regs<HD, IO16> rk = load_io<HD, IO16>(base + D, ld, 0, len, tid), rv = load_io<HD, IO16>(base + 2 * D, ld, 0, len, tid);
     for (int kt = 0; kt < ntiles; ++kt) {
         __syncthreads();
-        store_io<NP, IO16>(rk, 1.f, Kn, tid);
-        store_io<NP, IO16>(rv, 1.f, Vn, tid);
+        store_io<HD, NP, IO16>(rk, 1.f, Kn, tid);
+        store_io<HD, NP, IO16>(rv, 1.f, Vn, tid);
         if (kt + 1 < ntiles) {
-            rk = load_io<IO16>(base + D, ld, kt * 64 + 64, len, tid);
-            rv = load_io<IO16>(base + 2 * D, ld, kt * 64 + 64, len, tid);
+            rk = load_io<HD, IO16>(base + D, ld, kt * 64 + 64, len, tid);
+            rv = load_io<HD, IO16>(base + 2 * D, ld, kt * 64 + 64, len, tid);
         }
         __syncthreads();
         float st[4][4];
 #pragma unroll
         for (int kb = 0; kb < 4; kb += 2) {
-            bf16x8 a0[NP], a1[NP];
-            nat_frag_x3(Kn, kb, i16, g, a0);
-            nat_frag_x3(Kn, kb + 1, i16, g, a1);
+            bf16x8 a0[KK][NP], a1[KK][NP];
+            nat_frag_x3<HD, NP>(Kn, kb, i16, g, a0);
+            nat_frag_x3<HD, NP>(Kn, kb + 1, i16, g, a1);
             f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-            mfma_x3_2a(a0, a1, qf, s0, s1);
+            mfma_x3_2a<NP, KK>(a0, a1, qf, s0, s1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if constexpr (IO16) { st[kb][r] = s0[r] * sc_; st[kb + 1][r] = s1[r] * sc_; }
@@ -218,92 +338,102 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const typename IoT<IO16>::t
         ps += __shfl_xor(ps, 32, 64);
         l = l * alpha + ps;
         m = m_new;
+        f32x4 ar;          // alpha of the rows 4g .. 4g+3 whose sums this lane holds; all four fetched before the first is used -- fetched
+                           // row by row beside the scaling, two of the four shuffles no longer overlap (DESIGN 4.2 "head_dim 64")
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float ar = __shfl(alpha, g * 4 + r, 64);
-            o[0][r] *= ar;
-            o[1][r] *= ar;
-            ol[0][r] *= ar;
-            ol[1][r] *= ar;
+        for (int r = 0; r < 4; ++r) ar[r] = __shfl(alpha, g * 4 + r, 64);
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            o[cb] *= ar;
+            ol[cb] *= ar;
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             bf16x8 pa[NP], v0[NP], v1[NP];
             pair_frag_x3(st[2 * t], st[2 * t + 1], pa);
-            tr_col_frag_x3(Vn, t, g, i16, 0, v0);
-            tr_col_frag_x3(Vn, t, g, i16, 1, v1);
-            mfma_x3_2b(pa, v0, v1, o[0], o[1], ol[0], ol[1]);
+#pragma unroll
+            for (int cb = 0; cb < CB; cb += 2) {
+                tr_col_frag_x3<HD, NP>(Vn, t, g, i16, cb, v0);
+                tr_col_frag_x3<HD, NP>(Vn, t, g, i16, cb + 1, v1);
+                mfma_x3_2b(pa, v0, v1, o[cb], o[cb + 1], ol[cb], ol[cb + 1]);
+            }
         }
     }
-    o[0] += ol[0];
-    o[1] += ol[1];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) o[cb] += ol[cb];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const float lr = __shfl(l, g * 4 + r, 64);
         const int row = q0 + wave * 16 + g * 4 + r;
         if (row < len) {
             const float inv = 1.f / lr;
-            io_t* op = out + (int64_t)(start + row) * D + h * 32 + i16;
-            put_io<IO16>(op, o[0][r] * inv);
-            put_io<IO16>(op + 16, o[1][r] * inv);
+            io_t* op = out + (int64_t)(start + row) * D + h * HD + i16;
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) put_io<IO16>(op + 16 * cb, o[cb][r] * inv);
         }
     }
     if (g == 0 && qrow < len) lse[(int64_t)h * n_total + start + qrow] = m * X_LN2 + __logf(l);      // natural-log units
 }
 
 // dQ: one workgroup per 64-query tile, keys streamed.  K is read by rows for S and by columns for dQ += dS . K.
-template <int NP, bool IO16 = false>
-__global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const typename IoT<IO16>::t* __restrict__ qkv, const typename IoT<IO16>::t* __restrict__ dout, const float* __restrict__ lse,
+template <int HD, int NP, bool IO16>
+__global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
                                                         const float* __restrict__ delta, const int32_t* __restrict__ cu, int H, float scale,
-                                                        typename IoT<IO16>::t* __restrict__ dqkv, int64_t n_total, int B, int n_tiles) {
+                                                        io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
-    typedef typename IoT<IO16>::t io_t;
-    __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN];
-    __shared__ __attribute__((aligned(16))) __bf16 Vn[NP * XN];
+    typedef io_of<IO16> io_t;
+    constexpr int KK = HD / 32, CB = HD / 16;          // 32-deep reduction blocks of a row | 16-column blocks of an output row
+    __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN<HD>];
+    __shared__ __attribute__((aligned(16))) __bf16 Vn[NP * XN<HD>];
     const AttnWork wk_ = attn_decode(H, B, n_tiles);
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
     const int q0 = wk_.tile * 64;
     if (q0 >= len) return;
-    const int D = H * 32, ld = 3 * D;
+    const int D = H * HD, ld = 3 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
-    const io_t* base = qkv + (int64_t)start * ld + h * 32;
+    const io_t* base = qkv + (int64_t)start * ld + h * HD;
     const int qrow = q0 + wave * 16 + i16;
     const bool qok = qrow < len;
-    bf16x8 qf[NP], dof[NP];
-    if constexpr (IO16) {
-        row_frag_x16(qok ? base + (int64_t)qrow * ld + g * 8 : nullptr, qf);
-        row_frag_x16(qok ? dout + (int64_t)(start + qrow) * D + h * 32 + g * 8 : nullptr, dof);
-    } else {
-        row_frag_x3(qok ? base + (int64_t)qrow * ld + g * 8 : nullptr, scale * X_LOG2E, qf);
-        row_frag_x3(qok ? dout + (int64_t)(start + qrow) * D + h * 32 + g * 8 : nullptr, 1.f, dof);
+    bf16x8 qf[KK][NP], dof[KK][NP];
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) {
+        if constexpr (IO16) {
+            row_frag_x16(qok ? base + (int64_t)qrow * ld + 32 * kk + g * 8 : nullptr, qf[kk]);
+            row_frag_x16(qok ? dout + (int64_t)(start + qrow) * D + h * HD + 32 * kk + g * 8 : nullptr, dof[kk]);
+        } else {
+            row_frag_x3(qok ? base + (int64_t)qrow * ld + 32 * kk + g * 8 : nullptr, scale * X_LOG2E, qf[kk]);
+            row_frag_x3(qok ? dout + (int64_t)(start + qrow) * D + h * HD + 32 * kk + g * 8 : nullptr, 1.f, dof[kk]);
+        }
     }
     const float sc_ = IO16 ? scale * X_LOG2E : 1.f;
     // log2 units; rows past the end get +inf so that exp2(s - lse) = 0 masks them without a select per element
     const float lse_q = qok ? lse[(int64_t)h * n_total + start + qrow] * X_LOG2E : INFINITY;
     const float del_q = qok ? delta[(int64_t)h * n_total + start + qrow] : 0.f;
-    f32x4 dq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, dql[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    f32x4 dq[CB], dql[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) dq[cb] = dql[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntiles = (len + 63) >> 6;
-    typename IoT<IO16>::regs rk = load_io<IO16>(base + D, ld, 0, len, tid), rv = load_io<IO16>(base + 2 * D, ld, 0, len, tid);
+    io_regs<HD, IO16> rk = load_io<HD, IO16>(base + D, ld, 0, len, tid), rv = load_io<HD, IO16>(base + 2 * D, ld, 0, len, tid);
     for (int kt = 0; kt < ntiles; ++kt) {
         __syncthreads();
-        store_io<NP, IO16>(rk, 1.f, Kn, tid);
-        store_io<NP, IO16>(rv, 1.f, Vn, tid);
+        store_io<HD, NP, IO16>(rk, 1.f, Kn, tid);
+        store_io<HD, NP, IO16>(rv, 1.f, Vn, tid);
         if (kt + 1 < ntiles) {
-            rk = load_io<IO16>(base + D, ld, kt * 64 + 64, len, tid);
-            rv = load_io<IO16>(base + 2 * D, ld, kt * 64 + 64, len, tid);
+            rk = load_io<HD, IO16>(base + D, ld, kt * 64 + 64, len, tid);
+            rv = load_io<HD, IO16>(base + 2 * D, ld, kt * 64 + 64, len, tid);
         }
         __syncthreads();
         const bool last = kt == ntiles - 1 && (len & 63);          // wave-uniform
         float ds[4][4];
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
-            bf16x8 ak[NP], av[NP];
-            nat_frag_x3(Kn, kb, i16, g, ak);
-            nat_frag_x3(Vn, kb, i16, g, av);
+            bf16x8 ak[KK][NP], av[KK][NP];
+            nat_frag_x3<HD, NP>(Kn, kb, i16, g, ak);
+            nat_frag_x3<HD, NP>(Vn, kb, i16, g, av);
             f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, dp4 = s4;
-            mfma_x3_2c<NP>(ak, qf, av, dof, s4, dp4);
+            mfma_x3_2c<NP, KK>(ak, qf, av, dof, s4, dp4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float p = __builtin_amdgcn_exp2f(IO16 ? s4[r] * sc_ - lse_q : s4[r] - lse_q);
@@ -315,34 +445,40 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const typename IoT<IO16>
         for (int t = 0; t < 2; ++t) {
             bf16x8 da[NP], k0[NP], k1[NP];
             pair_frag_x3(ds[2 * t], ds[2 * t + 1], da);
-            tr_col_frag_x3(Kn, t, g, i16, 0, k0);
-            tr_col_frag_x3(Kn, t, g, i16, 1, k1);
-            mfma_x3_2b(da, k0, k1, dq[0], dq[1], dql[0], dql[1]);
+#pragma unroll
+            for (int cb = 0; cb < CB; cb += 2) {
+                tr_col_frag_x3<HD, NP>(Kn, t, g, i16, cb, k0);
+                tr_col_frag_x3<HD, NP>(Kn, t, g, i16, cb + 1, k1);
+                mfma_x3_2b(da, k0, k1, dq[cb], dq[cb + 1], dql[cb], dql[cb + 1]);
+            }
         }
     }
-    dq[0] += dql[0];
-    dq[1] += dql[1];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) dq[cb] += dql[cb];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int row = q0 + wave * 16 + g * 4 + r;
         if (row < len) {
-            io_t* op = dqkv + (int64_t)(start + row) * ld + h * 32 + i16;
-            put_io<IO16>(op, dq[0][r] * scale);
-            put_io<IO16>(op + 16, dq[1][r] * scale);
+            io_t* op = dqkv + (int64_t)(start + row) * ld + h * HD + i16;
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) put_io<IO16>(op + 16 * cb, dq[cb][r] * scale);
         }
     }
 }
 
 // dK, dV: one workgroup per 64-key tile, queries streamed.  Q and dO are read by rows (S, dP) and by columns (dK, dV).
-// (three workgroups per CU: the compiler settles at 178 VGPRs without the bound and 166, no spills, with it)
-template <int NP, bool IO16 = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3 : 1))) void attn_bwd_dkv_x3_k(const typename IoT<IO16>::t* __restrict__ qkv, const typename IoT<IO16>::t* __restrict__ dout, const float* __restrict__ lse,
+// (HD = 32, three planes: three workgroups per CU -- the compiler settles at 178 VGPRs without the bound and 166, no spills, with it.
+// HD = 64: the accumulators and the register-resident K / V planes double; DKV_WAVES asks for what leaves no scratch -- DESIGN 4.2)
+template <int HD, int NP> constexpr int DKV_WAVES = NP == 3 ? (HD == 32 ? 3 : 2) : 1;
+template <int HD, int NP, bool IO16>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<HD, NP>))) void attn_bwd_dkv_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
                                                          const float* __restrict__ delta, const int32_t* __restrict__ cu, int H, float scale,
-                                                         typename IoT<IO16>::t* __restrict__ dqkv, int64_t n_total, int B, int n_tiles) {
+                                                         io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
-    typedef typename IoT<IO16>::t io_t;
-    __shared__ __attribute__((aligned(16))) __bf16 Qn[NP * XN];
-    __shared__ __attribute__((aligned(16))) __bf16 On[NP * XN];
+    typedef io_of<IO16> io_t;
+    constexpr int KK = HD / 32, CB = HD / 16;          // 32-deep reduction blocks of a row | 16-column blocks of an output row
+    __shared__ __attribute__((aligned(16))) __bf16 Qn[NP * XN<HD>];
+    __shared__ __attribute__((aligned(16))) __bf16 On[NP * XN<HD>];
     __shared__ float lse_s[64], del_s[64];
     const AttnWork wk_ = attn_decode(H, B, n_tiles);
     const int b = wk_.b, h = wk_.h;
@@ -350,31 +486,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3
     const int start = cu[b], len = cu[b + 1] - start;
     const int k0 = wk_.tile * 64;
     if (k0 >= len) return;
-    const int D = H * 32, ld = 3 * D;
+    const int D = H * HD, ld = 3 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
-    const io_t* base = qkv + (int64_t)start * ld + h * 32;
-    const io_t* dobase = dout + (int64_t)start * D + h * 32;
+    const io_t* base = qkv + (int64_t)start * ld + h * HD;
+    const io_t* dobase = dout + (int64_t)start * D + h * HD;
     const int krow = k0 + wave * 16 + i16;
-    bf16x8 kf[NP], vf[NP];
-    if constexpr (IO16) {
-        row_frag_x16(krow < len ? base + (int64_t)krow * ld + D + g * 8 : nullptr, kf);
-        row_frag_x16(krow < len ? base + (int64_t)krow * ld + 2 * D + g * 8 : nullptr, vf);
-    } else {
-        row_frag_x3(krow < len ? base + (int64_t)krow * ld + D + g * 8 : nullptr, 1.f, kf);
-        row_frag_x3(krow < len ? base + (int64_t)krow * ld + 2 * D + g * 8 : nullptr, 1.f, vf);
+    bf16x8 kf[KK][NP], vf[KK][NP];
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) {
+        if constexpr (IO16) {
+            row_frag_x16(krow < len ? base + (int64_t)krow * ld + D + 32 * kk + g * 8 : nullptr, kf[kk]);
+            row_frag_x16(krow < len ? base + (int64_t)krow * ld + 2 * D + 32 * kk + g * 8 : nullptr, vf[kk]);
+        } else {
+            row_frag_x3(krow < len ? base + (int64_t)krow * ld + D + 32 * kk + g * 8 : nullptr, 1.f, kf[kk]);
+            row_frag_x3(krow < len ? base + (int64_t)krow * ld + 2 * D + 32 * kk + g * 8 : nullptr, 1.f, vf[kk]);
+        }
     }
     const float sc_ = IO16 ? scale * X_LOG2E : 1.f;
-    f32x4 dk[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, dv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    f32x4 dkl[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, dvl[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};       // low-order plane products
+    f32x4 dk[CB], dv[CB], dkl[CB], dvl[CB];       // dkl, dvl: low-order plane products
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) dk[cb] = dv[cb] = dkl[cb] = dvl[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntiles = (len + 63) >> 6;
-    typename IoT<IO16>::regs rq = load_io<IO16>(base, ld, 0, len, tid), ro = load_io<IO16>(dobase, D, 0, len, tid);
+    io_regs<HD, IO16> rq = load_io<HD, IO16>(base, ld, 0, len, tid), ro = load_io<HD, IO16>(dobase, D, 0, len, tid);
     for (int qt = 0; qt < ntiles; ++qt) {
         __syncthreads();
-        store_io<NP, IO16>(rq, scale * X_LOG2E, Qn, tid);  // log2 units; dK is rescaled by ln 2 at the end (IO16: Q as it is, scores scaled, dK by `scale`)
-        store_io<NP, IO16>(ro, 1.f, On, tid);
+        store_io<HD, NP, IO16>(rq, scale * X_LOG2E, Qn, tid);  // log2 units; dK is rescaled by ln 2 at the end (IO16: Q as it is, scores scaled, dK by `scale`)
+        store_io<HD, NP, IO16>(ro, 1.f, On, tid);
         if (qt + 1 < ntiles) {
-            rq = load_io<IO16>(base, ld, qt * 64 + 64, len, tid);
-            ro = load_io<IO16>(dobase, D, qt * 64 + 64, len, tid);
+            rq = load_io<HD, IO16>(base, ld, qt * 64 + 64, len, tid);
+            ro = load_io<HD, IO16>(dobase, D, qt * 64 + 64, len, tid);
         }
         if (tid < 64) {
             const int q = qt * 64 + tid;
@@ -388,11 +528,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int qb = 2 * t + u;
-                bf16x8 aq[NP], ao[NP];
-                nat_frag_x3(Qn, qb, i16, g, aq);
-                nat_frag_x3(On, qb, i16, g, ao);
+                bf16x8 aq[KK][NP], ao[KK][NP];
+                nat_frag_x3<HD, NP>(Qn, qb, i16, g, aq);
+                nat_frag_x3<HD, NP>(On, qb, i16, g, ao);
                 f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, dp4 = s4;
-                mfma_x3_2c<NP>(aq, kf, ao, vf, s4, dp4);
+                mfma_x3_2c<NP, KK>(aq, kf, ao, vf, s4, dp4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int qq = qb * 16 + g * 4 + r;
@@ -402,40 +542,65 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3
             }
             bf16x8 pa[NP], da[NP], f0[NP], f1[NP];
             pair_frag_x3(p[0], p[1], pa);
-            tr_col_frag_x3(On, t, g, i16, 0, f0);
-            tr_col_frag_x3(On, t, g, i16, 1, f1);
-            mfma_x3_2b(pa, f0, f1, dv[0], dv[1], dvl[0], dvl[1]);
+#pragma unroll
+            for (int cb = 0; cb < CB; cb += 2) {
+                tr_col_frag_x3<HD, NP>(On, t, g, i16, cb, f0);
+                tr_col_frag_x3<HD, NP>(On, t, g, i16, cb + 1, f1);
+                mfma_x3_2b(pa, f0, f1, dv[cb], dv[cb + 1], dvl[cb], dvl[cb + 1]);
+            }
             pair_frag_x3(ds[0], ds[1], da);
-            tr_col_frag_x3(Qn, t, g, i16, 0, f0);
-            tr_col_frag_x3(Qn, t, g, i16, 1, f1);
-            mfma_x3_2b(da, f0, f1, dk[0], dk[1], dkl[0], dkl[1]);
+#pragma unroll
+            for (int cb = 0; cb < CB; cb += 2) {
+                tr_col_frag_x3<HD, NP>(Qn, t, g, i16, cb, f0);
+                tr_col_frag_x3<HD, NP>(Qn, t, g, i16, cb + 1, f1);
+                mfma_x3_2b(da, f0, f1, dk[cb], dk[cb + 1], dkl[cb], dkl[cb + 1]);
+            }
         }
     }
-    dv[0] += dvl[0]; dv[1] += dvl[1];
-    dk[0] += dkl[0]; dk[1] += dkl[1];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) { dv[cb] += dvl[cb]; dk[cb] += dkl[cb]; }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int row = k0 + wave * 16 + g * 4 + r;
         if (row < len) {
-            io_t* op = dqkv + (int64_t)(start + row) * ld + h * 32 + i16;
+            io_t* op = dqkv + (int64_t)(start + row) * ld + h * HD + i16;
             const float ks = IO16 ? scale : X_LN2;
-            put_io<IO16>(op + D, dk[0][r] * ks);
-            put_io<IO16>(op + D + 16, dk[1][r] * ks);
-            put_io<IO16>(op + 2 * D, dv[0][r]);
-            put_io<IO16>(op + 2 * D + 16, dv[1][r]);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) put_io<IO16>(op + D + 16 * cb, dk[cb][r] * ks);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) put_io<IO16>(op + 2 * D + 16 * cb, dv[cb][r]);
         }
     }
+}
+
+// (hd, mode) -> the instantiation (HD, NP, IO16) that runs it; `f` receives it as a tag type
+template <int HD_, int NP_, bool IO16_> struct X3Form {
+    static constexpr int HD = HD_, NP = NP_;
+    static constexpr bool IO16 = IO16_;
+    typedef io_of<IO16_> io_t;
+};
+template <int HD, typename F>
+static void attn_x3_by_mode(AttnMode mode, F&& f) {
+    if (mode == ATTN_B16) f(X3Form<HD, 1, true>());
+    else if (mode == ATTN_BF16_OPS) f(X3Form<HD, 1, false>());
+    else f(X3Form<HD, 3, false>());
+}
+template <typename F>
+static void attn_x3_dispatch(int hd, AttnMode mode, F&& f) {
+    if (hd == 64) attn_x3_by_mode<64>(mode, f);
+    else attn_x3_by_mode<32>(mode, f);
 }
 
 // launchers, called from attn.hip's attn_fwd / attn_bwd for every mode but ATTN_NATIVE (arguments already validated there: hd is 32 or 64)
 void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
                         float* lse, hipStream_t s) {
     const int n_tiles = (max_len + 63) / 64;
-    if (hd == 64) return attn_fwd_x3_hd64_launch(mode, qkv, cu, B, n_tiles, n_total, H, scale, out, lse, s);
     const dim3 grid(attn_grid(H, B, n_tiles));
-    if (mode == ATTN_B16) hipLaunchKernelGGL((attn_fwd_x3_k<1, true>), grid, dim3(256), 0, s, (const __bf16*)qkv, cu, H, scale, (__bf16*)out, lse, n_total, B, n_tiles);
-    else if (mode == ATTN_BF16_OPS) hipLaunchKernelGGL((attn_fwd_x3_k<1>), grid, dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
-    else hipLaunchKernelGGL((attn_fwd_x3_k<3>), grid, dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
+    attn_x3_dispatch(hd, mode, [&](auto form) {
+        typedef decltype(form) F;
+        typedef typename F::io_t T;
+        hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, n_tiles);
+    });
 }
 
 // dQ and dK / dV are independent given delta: with U3D_ATTN_FORK=1 the dQ kernel is forked onto a per-device side stream and joined
@@ -476,18 +641,12 @@ void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const 
         hipStreamWaitEvent(f->side, f->fork, 0);
         sq = f->side;
     }
-    if (hd == 64) {
-        attn_bwd_x3_hd64_launch(mode, qkv, dout, lse, cu, B, n_tiles, n_total, H, scale, dqkv, delta, sq, s);
-    } else if (mode == ATTN_B16) {
-        hipLaunchKernelGGL((attn_bwd_dq_x3_k<1, true>), grid, dim3(256), 0, sq, (const __bf16*)qkv, (const __bf16*)dout, lse, delta, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
-        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<1, true>), grid, dim3(256), 0, s, (const __bf16*)qkv, (const __bf16*)dout, lse, delta, cu, H, scale, (__bf16*)dqkv, n_total, B, n_tiles);
-    } else if (mode == ATTN_BF16_OPS) {
-        hipLaunchKernelGGL((attn_bwd_dq_x3_k<1>), grid, dim3(256), 0, sq, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
-        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<1>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_x3_k<3>), grid, dim3(256), 0, sq, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
-        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<3>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, delta, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
-    }
+    attn_x3_dispatch(hd, mode, [&](auto form) {
+        typedef decltype(form) F;
+        typedef typename F::io_t T;
+        hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
+        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
+    });
     if (f) {
         hipEventRecord(f->join, f->side);
         hipStreamWaitEvent(s, f->join, 0);
@@ -495,8 +654,6 @@ void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const 
 }
 
 }  // namespace u3d
-
-#include "attn_x3_hd64.h"          // the head_dim 64 kernels and their launchers
 
 using namespace u3d;
 
