@@ -390,6 +390,48 @@ int u3d_attn_varlen_bwd_b16(const void* qkv, const void* out, const void* dout, 
                             double flops_hint, u3d_stream_t stream);
 
 /* =====================================================================================
+ * K13d  dropout of the decoder (unidet3d/encoder.py:19-22,38,55-61; csrc/dropout.h).  The mask is a stateless hash:
+ *     keep(seed, offset, a, b, c)  <=>  hash32(seed, offset, a, b, c) >= floor(p 2^32).  Nothing is stored; a backward call
+ *     regenerates the mask from the same (p, seed, offset).  The caller picks `offset` per (training step, site).
+ *     Every entry point: p outside [0, 1) (NaN included) is U3D_EINVAL before the first HIP call.  Added entry points:
+ *     U3D_ABI_VERSION is unchanged.
+ *
+ *     Attention: the six calls above with dropout on the softmax probabilities as in nn.MultiheadAttention --
+ *     O = (P . M) V / (1 - p), lse from the undropped P -- with (a, b, c) = (head, packed query row, packed key row), rows counted in
+ *     the packed [n_total, .] matrix.  p == 0 is the call above (the same kernels).  The native fp32 MFMA arm (u3d_fp32_math(0))
+ *     is not built for p > 0: U3D_EUNSUPPORTED, the message names the mode that runs it.
+ * ===================================================================================== */
+int u3d_attn_varlen_fwd_drop(const float* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
+                             float scale, float* out, float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed,
+                             uint64_t offset);
+int u3d_attn_varlen_bwd_drop(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu_seqlens,
+                             int B, int max_len, int64_t n_total, int H, int hd, float scale, float* dqkv, float* delta_ws,
+                             double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset);
+int u3d_attn_varlen_fwd_drop_bf16(const float* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
+                                  float scale, float* out, float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed,
+                                  uint64_t offset);
+int u3d_attn_varlen_bwd_drop_bf16(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu_seqlens,
+                                  int B, int max_len, int64_t n_total, int H, int hd, float scale, float* dqkv, float* delta_ws,
+                                  double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset);
+int u3d_attn_varlen_fwd_drop_b16(const void* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
+                                 float scale, void* out, float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed,
+                                 uint64_t offset);
+int u3d_attn_varlen_bwd_drop_b16(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu_seqlens,
+                                 int B, int max_len, int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws,
+                                 double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset);
+/* the mask itself, one byte per element (1 = kept): what the attention kernels apply for (p, seed, offset) over H heads of a packed
+ * matrix of n_total rows, and what the elementwise kernels below apply to an [n, C] tensor ((a, b, c) = (0, row, column)) */
+int u3d_dropout_mask_attn(double p, uint64_t seed, uint64_t offset, int H, int64_t n_total, uint8_t* mask /*[H][n_total][n_total]*/,
+                          u3d_stream_t stream);
+int u3d_dropout_mask_rows(double p, uint64_t seed, uint64_t offset, int64_t n, int C, uint8_t* mask /*[n][C]*/, u3d_stream_t stream);
+/* elementwise dropout over [n, C]: y = x . M / (1 - p), formed in double and rounded once; backward is the same map on dy.  fp32
+ * tensors (C % 4 == 0) and bf16 tensors (_b16, C % 8 == 0); 16-byte loads and stores, one launch. */
+int u3d_dropout_fwd(const float* x, float* y, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream);
+int u3d_dropout_bwd(const float* dy, float* dx, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream);
+int u3d_dropout_fwd_b16(const void* x, void* y, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream);
+int u3d_dropout_bwd_b16(const void* dy, void* dx, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream);
+
+/* =====================================================================================
  * K14  dense fp32 GEMMs of the decoder's nn.Linear layers (unidet3d/encoder.py:19-21,55-61,138-140,
  *      153-155,163): forward C = A W^T + bias, input-gradient (the same call on the transposed weight),
  *      weight-gradient C = A^T B with the row reduction split over workgroups (ws, fixed-order sum).

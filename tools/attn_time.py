@@ -13,7 +13,11 @@ Device time between HIP events around one forward / one backward call (the backw
 4096^3 GEMM so that the host runs ahead of the GPU, after warm-up, the variants alternating inside every round; median | p10 | p90 over the rounds.  Per-kernel times come from a kernel trace of this script in a run
 of its own (--no-sdpa --reps 5 under rocprofv3 --kernel-trace --stats).
 
-    python tools/attn_time.py [--reps 30] [--warmup 5] [--out profiles/attn_hd64_time.txt]
+--dropout P adds, in the same run and alternating with the others, the `_drop` kernels (dropout with probability P on the
+softmax probabilities, mask regenerated in the kernels) beside the p = 0 ones, gives torch's per-scene call dropout_p = P -- what a user
+without these kernels would run -- and prints the ratios `_drop` / p = 0 and `_drop` / torch.
+
+    python tools/attn_time.py [--reps 30] [--warmup 5] [--dropout 0.1] [--out profiles/attn_hd64_time.txt]
 """
 import argparse
 import contextlib
@@ -51,6 +55,7 @@ def main():
     ap.add_argument('--queries', type=int, default=3000)
     ap.add_argument('--d', type=int, default=256)
     ap.add_argument('--no-sdpa', action='store_true')
+    ap.add_argument('--dropout', type=float, default=0.0)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -68,14 +73,14 @@ def main():
     flows = [('fp32', torch.float32, contextlib.nullcontext), ('bf16 ops', torch.float32, lambda: P.operands('bf16')),
              ('bf16', torch.bfloat16, contextlib.nullcontext)]
 
-    def lib_variant(flow, dtype, ctx, H):
+    def lib_variant(flow, dtype, ctx, H, p=0.0):
         x = qkv32.clone().to(dtype).requires_grad_()
         go = go32.to(dtype)
 
         def run():
             with ctx():
                 x.grad = None
-                out, ef = _timed(lambda: attention_varlen(x, cu, n, H))
+                out, ef = _timed(lambda: attention_varlen(x, cu, n, H, 0, p, (1234, 5)))
                 _, eb = _timed(lambda: out.backward(go))
             return ef, eb
         return run
@@ -87,7 +92,8 @@ def main():
 
         def run():          # per scene, as a user without a varlen kernel would call it
             q.grad = k.grad = v.grad = None
-            outs, ef = _timed(lambda: [torch.nn.functional.scaled_dot_product_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1]) for b in range(B)])
+            outs, ef = _timed(lambda: [torch.nn.functional.scaled_dot_product_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], dropout_p=args.dropout)
+                                       for b in range(B)])
             _, eb = _timed(lambda: torch.autograd.backward(outs, [go[b:b + 1] for b in range(B)]))
             return ef, eb
         return run
@@ -96,10 +102,15 @@ def main():
     for flow, dtype, ctx in flows:
         for H, hd in splits:
             variants.append((f'library  {flow:<8} H={H} hd={hd}', flow, hd, lib_variant(flow, dtype, ctx, H)))
+    if args.dropout:
+        for flow, dtype, ctx in flows:
+            for H, hd in splits:
+                variants.append((f'library  {flow:<8} H={H} hd={hd} dropout {args.dropout}', flow + ' drop', hd, lib_variant(flow, dtype, ctx, H, args.dropout)))
+    sdpa_tag = f' dropout {args.dropout}' if args.dropout else ''
     if not args.no_sdpa:
         for flow, dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
             for H, hd in splits:
-                variants.append((f'torch sdpa per scene {flow:<4} H={H} hd={hd}', 'sdpa ' + flow, hd, sdpa_variant(dtype, H)))
+                variants.append((f'torch sdpa per scene {flow:<4} H={H} hd={hd}{sdpa_tag}', 'sdpa ' + flow, hd, sdpa_variant(dtype, H)))
     fwd = {v[0]: [] for v in variants}
     bwd = {v[0]: [] for v in variants}
     for it in range(args.warmup + args.reps):
@@ -122,7 +133,7 @@ def main():
              f'{torch.cuda.get_device_name(0)}; {args.warmup} warm-up + {args.reps} timed rounds, variants alternating inside a round',
              'device ms between HIP events around one call (issued behind a queued GEMM: execution, not issue): median | p10 | p90, algorithmic TFLOP/s at the median', '']
     for name, _, _, _ in variants:
-        lines.append(f'{name:<40} fwd {cell(fwd[name], ff)}   bwd {cell(bwd[name], fb)}')
+        lines.append(f'{name:<52} fwd {cell(fwd[name], ff)}   bwd {cell(bwd[name], fb)}')
     lines.append('')
     lines.append('head_dim 64 over head_dim 32 of the same flow (medians; p90 / p10 of each variant above is the noise to read it against)')
     by = {}
@@ -130,6 +141,18 @@ def main():
         by.setdefault(flow, {})[hd] = name
     for flow, d in by.items():
         lines.append(f'{flow:<10} fwd {statistics.median(fwd[d[64]]) / statistics.median(fwd[d[32]]):.3f}   bwd {statistics.median(bwd[d[64]]) / statistics.median(bwd[d[32]]):.3f}')
+    if args.dropout:
+        med = statistics.median
+        lines += ['', f'dropout {args.dropout}: the `_drop` kernels over the p = 0 kernels of the same flow and head dim | over torch sdpa per scene with dropout_p = '
+                      f'{args.dropout} (fp32 and bf16 ops beside torch fp32, bf16 beside torch bf16); medians']
+        for flow, _, _ in flows:
+            for _, hd in splits:
+                d, z = by[flow + ' drop'][hd], by[flow][hd]
+                line = f'{flow:<10} hd={hd}  fwd {med(fwd[d]) / med(fwd[z]):.3f}   bwd {med(bwd[d]) / med(bwd[z]):.3f}'
+                s = by.get('sdpa ' + ('bf16' if flow == 'bf16' else 'fp32'))
+                if s:
+                    line += f'   | over torch  fwd {med(fwd[d]) / med(fwd[s[hd]]):.3f}   bwd {med(bwd[d]) / med(bwd[s[hd]]):.3f}'
+                lines.append(line)
     text = '\n'.join(lines) + '\n'
     print(text)
     if args.out:

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('U3D_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libu3d_hip.so')      # override: A/B runs of kernel builds
 
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
+_u64 = C.c_uint64
 
 # name -> (restype, argtypes)   (mirrors include/u3d.h, checked by tests/test_cabi.py)
 PROTOTYPES = {
@@ -131,6 +132,19 @@ PROTOTYPES = {
     'u3d_attn_varlen_bwd_bf16': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
     'u3d_attn_varlen_fwd_b16': (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
     'u3d_attn_varlen_bwd_b16': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
+    # dropout (csrc/dropout.h): the calls above plus (p, seed, offset); the mask dumps; the elementwise kernels
+    'u3d_attn_varlen_fwd_drop': (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp, _f64, _u64, _u64]),
+    'u3d_attn_varlen_bwd_drop': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp, _f64, _u64, _u64]),
+    'u3d_attn_varlen_fwd_drop_bf16': (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp, _f64, _u64, _u64]),
+    'u3d_attn_varlen_bwd_drop_bf16': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp, _f64, _u64, _u64]),
+    'u3d_attn_varlen_fwd_drop_b16': (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp, _f64, _u64, _u64]),
+    'u3d_attn_varlen_bwd_drop_b16': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp, _f64, _u64, _u64]),
+    'u3d_dropout_mask_attn': (_i32, [_f64, _u64, _u64, _i32, _i64, _vp, _vp]),
+    'u3d_dropout_mask_rows': (_i32, [_f64, _u64, _u64, _i64, _i32, _vp, _vp]),
+    'u3d_dropout_fwd': (_i32, [_vp, _vp, _i64, _i32, _f64, _u64, _u64, _vp]),
+    'u3d_dropout_bwd': (_i32, [_vp, _vp, _i64, _i32, _f64, _u64, _u64, _vp]),
+    'u3d_dropout_fwd_b16': (_i32, [_vp, _vp, _i64, _i32, _f64, _u64, _u64, _vp]),
+    'u3d_dropout_bwd_b16': (_i32, [_vp, _vp, _i64, _i32, _f64, _u64, _u64, _vp]),
     'u3d_aug_points': (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, C.POINTER(_f32), C.POINTER(_f32), _f32, _vp, _vp, _vp]),
     'u3d_aug_extent_f32': (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
     'u3d_aug_extent_f64': (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),

@@ -300,13 +300,26 @@ static int attn_check_hd(AttnMode mode, int hd) {
     return U3D_EUNSUPPORTED;
 }
 
+// dropout (csrc/dropout.h) is built into the plane kernels only; like the head dim, decided before the first HIP call
+static int attn_check_drop(AttnMode mode, const DropArgs* dr) {
+    if (!dr || mode != ATTN_NATIVE) return U3D_OK;
+    set_error("attn: dropout unsupported by the native fp32 MFMA kernels (U3D_FP32_MATH=mfma) -- the default fp32 math mode bf16x3 (u3d_fp32_math(1)) runs it");
+    return U3D_EUNSUPPORTED;
+}
+static bool drop_p_ok(double p) {
+    if (p >= 0.0 && p < 1.0) return true;          // false for NaN
+    set_error("attn: dropout probability %g outside [0, 1)", p);
+    return false;
+}
+
 static const char* const ATTN_FWD_LABEL[] = {"attn_fwd", "attn_fwd_x3", "attn_fwd_bf16", "attn_fwd_b16"};        // by AttnMode
 static const char* const ATTN_BWD_LABEL[] = {"attn_bwd", "attn_bwd_x3", "attn_bwd_bf16", "attn_bwd_b16"};
 
 int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
-             float* lse, double flops_hint, u3d_stream_t stream) {
+             float* lse, double flops_hint, u3d_stream_t stream, const DropArgs* dr) {
     if (!qkv || !cu || !out || !lse || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
     if (attn_check_hd(mode, hd) != U3D_OK) return U3D_EUNSUPPORTED;
+    if (attn_check_drop(mode, dr) != U3D_OK) return U3D_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_ATTN_FWD, s, flops_hint);
     if (max_len <= 0) return U3D_OK;
@@ -314,15 +327,16 @@ int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_l
         const int n_tiles = (max_len + 63) / 64;
         hipLaunchKernelGGL(attn_fwd_k, dim3(attn_grid(H, B, n_tiles)), dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
     } else {
-        attn_fwd_x3_launch(mode, qkv, cu, B, max_len, n_total, H, hd, scale, out, lse, s);
+        attn_fwd_x3_launch(mode, qkv, cu, B, max_len, n_total, H, hd, scale, out, lse, s, dr);
     }
     return check_launch(ATTN_FWD_LABEL[mode]);
 }
 
 int attn_bwd(AttnMode mode, const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
-             int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream) {
+             int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream, const DropArgs* dr) {
     if (!qkv || !out || !dout || !lse || !cu || !dqkv || !delta_ws || B <= 0 || H <= 0 || n_total <= 0) return U3D_EINVAL;
     if (attn_check_hd(mode, hd) != U3D_OK) return U3D_EUNSUPPORTED;
+    if (attn_check_drop(mode, dr) != U3D_OK) return U3D_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_ATTN_BWD, s, flops_hint);
     if (max_len <= 0) return U3D_OK;
@@ -340,9 +354,26 @@ int attn_bwd(AttnMode mode, const void* qkv, const void* out, const void* dout, 
         hipLaunchKernelGGL(attn_bwd_dq_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
         hipLaunchKernelGGL(attn_bwd_dkv_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
     } else {
-        attn_bwd_x3_launch(mode, qkv, dout, lse, cu, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, s);
+        attn_bwd_x3_launch(mode, qkv, dout, lse, cu, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, s, dr);
     }
     return check_launch(ATTN_BWD_LABEL[mode]);
+}
+
+int attn_fwd_drop(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
+                  float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset) {
+    if (!drop_p_ok(p)) return U3D_EINVAL;
+    if (p == 0.0) return attn_fwd(mode, qkv, cu, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream);
+    const DropArgs dr = drop_args(p, seed, offset);
+    return attn_fwd(mode, qkv, cu, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream, &dr);
+}
+
+int attn_bwd_drop(AttnMode mode, const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
+                  int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream, double p,
+                  uint64_t seed, uint64_t offset) {
+    if (!drop_p_ok(p)) return U3D_EINVAL;
+    if (p == 0.0) return attn_bwd(mode, qkv, out, dout, lse, cu, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream);
+    const DropArgs dr = drop_args(p, seed, offset);
+    return attn_bwd(mode, qkv, out, dout, lse, cu, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream, &dr);
 }
 
 }  // namespace u3d
@@ -361,6 +392,18 @@ int u3d_attn_varlen_bwd(const float* qkv, const float* out, const float* dout, c
                         int B, int max_len, int64_t n_total, int H, int hd, float scale, float* dqkv, float* delta_ws,
                         double flops_hint, u3d_stream_t stream) {
     return attn_bwd(fp32_x3() ? ATTN_X3 : ATTN_NATIVE, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream);
+}
+
+int u3d_attn_varlen_fwd_drop(const float* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
+                             float scale, float* out, float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset) {
+    return attn_fwd_drop(fp32_x3() ? ATTN_X3 : ATTN_NATIVE, qkv, cu_seqlens, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream, p, seed, offset);
+}
+
+int u3d_attn_varlen_bwd_drop(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu_seqlens,
+                             int B, int max_len, int64_t n_total, int H, int hd, float scale, float* dqkv, float* delta_ws,
+                             double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset) {
+    return attn_bwd_drop(fp32_x3() ? ATTN_X3 : ATTN_NATIVE, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream,
+                         p, seed, offset);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Shared by the attention kernels of attn.hip (native fp32 MFMA) and attn_x3.hip (bf16 planes): the work decode, the delta
-// kernel of the backward pass, and the host bodies behind the six u3d_attn_varlen_* entry points.
+// kernel of the backward pass, and the host bodies behind the u3d_attn_varlen_* entry points (with and without dropout).
 #pragma once
+#include "dropout.h"
 #include "u3d_common.h"
 
 namespace u3d {
@@ -59,16 +60,24 @@ enum AttnMode {
     ATTN_B16,           // bf16 tensors (qkv / out / dout / dqkv), one plane
 };
 
-// attn_x3.hip: the plane kernels of every mode but ATTN_NATIVE, hd 32 or 64 (the backward launcher expects delta_ws filled)
+// attn_x3.hip: the plane kernels of every mode but ATTN_NATIVE, hd 32 or 64 (the backward launcher expects delta_ws filled);
+// `dr` non-null: the DROP = true instantiations with that key (csrc/dropout.h)
 void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
-                        float* lse, hipStream_t s);
+                        float* lse, hipStream_t s, const DropArgs* dr = nullptr);
 void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
-                        int64_t n_total, int H, int hd, float scale, void* dqkv, const float* delta, hipStream_t s);
+                        int64_t n_total, int H, int hd, float scale, void* dqkv, const float* delta, hipStream_t s, const DropArgs* dr = nullptr);
 
 // attn.hip: the bodies of the u3d_attn_varlen_{fwd,bwd}{,_bf16,_b16} entry points -- validation, timing scope, dispatch, launch check
 int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
-             float* lse, double flops_hint, u3d_stream_t stream);
+             float* lse, double flops_hint, u3d_stream_t stream, const DropArgs* dr = nullptr);
 int attn_bwd(AttnMode mode, const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
-             int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream);
+             int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream, const DropArgs* dr = nullptr);
+// the bodies of the u3d_attn_varlen_{fwd,bwd}_drop{,_bf16,_b16} entry points: p outside [0, 1) is U3D_EINVAL, ATTN_NATIVE with p > 0
+// U3D_EUNSUPPORTED, both before the first HIP call; p == 0 is the call without dropout
+int attn_fwd_drop(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
+                  float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset);
+int attn_bwd_drop(AttnMode mode, const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
+                  int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws, double flops_hint, u3d_stream_t stream, double p,
+                  uint64_t seed, uint64_t offset);
 
 }  // namespace u3d

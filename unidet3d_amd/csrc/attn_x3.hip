@@ -255,10 +255,22 @@ __device__ __forceinline__ void tr_col_frag_x3(const __bf16* nat, int t, int g, 
     for (int q = 0; q < NP; ++q) out[q] = tr16_pair(s + q * XN<HD>, s + q * XN<HD> + 16 * HD);
 }
 
-template <int HD, int NP, bool IO16>
+// DROP: dropout on the probabilities, the mask regenerated per element by csrc/dropout.h from (head, packed query row, packed
+// key row) -- l, m and lse come from the undropped probabilities, O = (P . M) V / (1 - p) with the factor folded into the final scaling.
+// The switch is the kernel's trailing argument pack: <HD, NP, IO16> is the kernel without dropout, argument list and all; <HD, NP, IO16,
+// DropArgs> takes the key and has DROP = true.
+struct DropNone {};
+__device__ __forceinline__ DropNone drop_of() { return DropNone{}; }
+__device__ __forceinline__ DropArgs drop_of(DropArgs a) { return a; }
+template <typename... DR> constexpr bool DROP_ON = sizeof...(DR) == 1;
+
+template <int HD, int NP, bool IO16, typename... DR>
 __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restrict__ qkv, const int32_t* __restrict__ cu, int H, float scale,
-                                                     io_of<IO16>* __restrict__ out, float* __restrict__ lse, int64_t n_total, int B, int n_tiles) {
+                                                     io_of<IO16>* __restrict__ out, float* __restrict__ lse, int64_t n_total, int B, int n_tiles,
+                                                     DR... dr_) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
+    constexpr bool DROP = DROP_ON<DR...>;
+    const auto dr = drop_of(dr_...);
     typedef io_of<IO16> io_t;
     constexpr int KK = HD / 32, CB = HD / 16;          // 32-deep reduction blocks of a row | 16-column blocks of an output row
     __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN<HD>];
@@ -280,6 +292,8 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restri
         else row_frag_x3(qrow < len ? base + (int64_t)qrow * ld + 32 * kk + g * 8 : nullptr, scale * X_LOG2E, qf[kk]);
     }
     const float sc_ = IO16 ? scale * X_LOG2E : 1.f;
+    DropRow drw = {0u, 0u};                       // this lane's query row of the mask; a lane's keys are c = start + 64 kt + 16 kb + 4g + r
+    if constexpr (DROP) drw = drop_row(drop_key(dr.seed, dr.offset, (uint32_t)h), (uint32_t)(start + qrow));
     float m = -INFINITY, l = 0.f;
     f32x4 o[CB], ol[CB];          // h.h | low-order products
 #pragma unroll
@@ -338,6 +352,14 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restri
         ps += __shfl_xor(ps, 32, 64);
         l = l * alpha + ps;
         m = m_new;
+        if constexpr (DROP) {                     // after the row sum, before the planes of P are formed
+            const DropRow rt = {drw.x + (uint32_t)(start + kt * 64 + g * 4), drw.y};
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (drop_hash32(rt, (uint32_t)(kb * 16 + r)) < dr.thr) st[kb][r] = 0.f;
+        }
         f32x4 ar;          // alpha of the rows 4g .. 4g+3 whose sums this lane holds; all four fetched before the first is used -- fetched
                            // row by row beside the scaling, two of the four shuffles no longer overlap (DESIGN 4.2 "head_dim 64")
 #pragma unroll
@@ -366,7 +388,8 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restri
         const float lr = __shfl(l, g * 4 + r, 64);
         const int row = q0 + wave * 16 + g * 4 + r;
         if (row < len) {
-            const float inv = 1.f / lr;
+            float inv = 1.f / lr;
+            if constexpr (DROP) inv *= dr.rinv;
             io_t* op = out + (int64_t)(start + row) * D + h * HD + i16;
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) put_io<IO16>(op + 16 * cb, o[cb][r] * inv);
@@ -376,11 +399,14 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restri
 }
 
 // dQ: one workgroup per 64-query tile, keys streamed.  K is read by rows for S and by columns for dQ += dS . K.
-template <int HD, int NP, bool IO16>
+// DROP: dS = P . (M . dP' / (1 - p) - delta); the lane's query and keys are those of the forward kernel
+template <int HD, int NP, bool IO16, typename... DR>
 __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
                                                         const float* __restrict__ delta, const int32_t* __restrict__ cu, int H, float scale,
-                                                        io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles) {
+                                                        io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles, DR... dr_) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
+    constexpr bool DROP = DROP_ON<DR...>;
+    const auto dr = drop_of(dr_...);
     typedef io_of<IO16> io_t;
     constexpr int KK = HD / 32, CB = HD / 16;          // 32-deep reduction blocks of a row | 16-column blocks of an output row
     __shared__ __attribute__((aligned(16))) __bf16 Kn[NP * XN<HD>];
@@ -411,6 +437,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __res
     // log2 units; rows past the end get +inf so that exp2(s - lse) = 0 masks them without a select per element
     const float lse_q = qok ? lse[(int64_t)h * n_total + start + qrow] * X_LOG2E : INFINITY;
     const float del_q = qok ? delta[(int64_t)h * n_total + start + qrow] : 0.f;
+    DropRow drw = {0u, 0u};
+    if constexpr (DROP) drw = drop_row(drop_key(dr.seed, dr.offset, (uint32_t)h), (uint32_t)(start + qrow));
     f32x4 dq[CB], dql[CB];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) dq[cb] = dql[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -438,7 +466,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __res
             for (int r = 0; r < 4; ++r) {
                 float p = __builtin_amdgcn_exp2f(IO16 ? s4[r] * sc_ - lse_q : s4[r] - lse_q);
                 if (last && kt * 64 + kb * 16 + g * 4 + r >= len) p = 0.f;        // zero-padded keys of the last tile
-                ds[kb][r] = p * (dp4[r] - del_q);
+                if constexpr (DROP) {
+                    const bool keep = drop_hash32(DropRow{drw.x + (uint32_t)(start + kt * 64 + g * 4), drw.y}, (uint32_t)(kb * 16 + r)) >= dr.thr;
+                    ds[kb][r] = p * ((keep ? dp4[r] * dr.rinv : 0.f) - del_q);
+                } else {
+                    ds[kb][r] = p * (dp4[r] - del_q);
+                }
             }
         }
 #pragma unroll
@@ -468,13 +501,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __res
 
 // dK, dV: one workgroup per 64-key tile, queries streamed.  Q and dO are read by rows (S, dP) and by columns (dK, dV).
 // (HD = 32, three planes: three workgroups per CU -- the compiler settles at 178 VGPRs without the bound and 166, no spills, with it.
-// HD = 64: the accumulators and the register-resident K / V planes double; DKV_WAVES asks for what leaves no scratch -- DESIGN 4.2)
-template <int HD, int NP> constexpr int DKV_WAVES = NP == 3 ? (HD == 32 ? 3 : 2) : 1;
-template <int HD, int NP, bool IO16>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<HD, NP>))) void attn_bwd_dkv_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
+// HD = 64: the accumulators and the register-resident K / V planes double; DKV_WAVES asks for what leaves no scratch -- DESIGN 4.2.
+// DROP: the keep mask and the hash temporaries take HD = 32 with three planes from 154 to over 168 registers -- two workgroups per CU there, no scratch)
+template <int HD, int NP, bool DROP> constexpr int DKV_WAVES = NP == 3 ? (HD == 32 && !DROP ? 3 : 2) : 1;
+// DROP: dV += (P . M)^T dO / (1 - p) (the factor at the end), dS = P . (M . dP' / (1 - p) - delta).  Here a lane holds ONE key (c = start +
+// krow) and four consecutive queries (b = start + 64 qt + 16 qb + 4g + r): the row stage of the hash runs per element.
+template <int HD, int NP, bool IO16, typename... DR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<HD, NP, DROP_ON<DR...>>))) void attn_bwd_dkv_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
                                                          const float* __restrict__ delta, const int32_t* __restrict__ cu, int H, float scale,
-                                                         io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles) {
+                                                         io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles, DR... dr_) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
+    constexpr bool DROP = DROP_ON<DR...>;
+    const auto dr = drop_of(dr_...);
     typedef io_of<IO16> io_t;
     constexpr int KK = HD / 32, CB = HD / 16;          // 32-deep reduction blocks of a row | 16-column blocks of an output row
     __shared__ __attribute__((aligned(16))) __bf16 Qn[NP * XN<HD>];
@@ -503,6 +541,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<H
         }
     }
     const float sc_ = IO16 ? scale * X_LOG2E : 1.f;
+    DropKey dkey = {0u, 0u};
+    if constexpr (DROP) dkey = drop_key(dr.seed, dr.offset, (uint32_t)h);
     f32x4 dk[CB], dv[CB], dkl[CB], dvl[CB];       // dkl, dvl: low-order plane products
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) dk[cb] = dv[cb] = dkl[cb] = dvl[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -522,6 +562,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<H
             del_s[tid] = q < len ? delta[(int64_t)h * n_total + start + q] : 0.f;
         }
         __syncthreads();
+        unsigned km = 0u;          // DROP: bit 4 qb + r = keep (query 16 qb + 4g + r of this tile, this lane's key), made here in one register:
+                                   // hashed where the probabilities are formed, the sixteen hashes' temporaries stay live across the MFMA chains
+        if constexpr (DROP) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int qq = (e >> 2) * 16 + g * 4 + (e & 3);
+                if (drop_hash32(drop_row(dkey, (uint32_t)(start + qt * 64 + qq)), (uint32_t)(start + krow)) >= dr.thr) km |= 1u << e;
+            }
+        }
         #pragma unroll
         for (int t = 0; t < 2; ++t) {
             float p[2][4], ds[2][4];          // 32 queries at a time: S / dP of two 16-query blocks, then their dV / dK products
@@ -537,7 +586,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<H
                 for (int r = 0; r < 4; ++r) {
                     const int qq = qb * 16 + g * 4 + r;
                     p[u][r] = __builtin_amdgcn_exp2f(IO16 ? s4[r] * sc_ - lse_s[qq] : s4[r] - lse_s[qq]);
-                    ds[u][r] = p[u][r] * (dp4[r] - del_s[qq]);
+                    if constexpr (DROP) {
+                        const bool keep = (km >> (4 * qb + r)) & 1u;
+                        ds[u][r] = p[u][r] * ((keep ? dp4[r] * dr.rinv : 0.f) - del_s[qq]);
+                        if (!keep) p[u][r] = 0.f;
+                    } else {
+                        ds[u][r] = p[u][r] * (dp4[r] - del_s[qq]);
+                    }
                 }
             }
             bf16x8 pa[NP], da[NP], f0[NP], f1[NP];
@@ -568,7 +623,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<H
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) put_io<IO16>(op + D + 16 * cb, dk[cb][r] * ks);
 #pragma unroll
-            for (int cb = 0; cb < CB; ++cb) put_io<IO16>(op + 2 * D + 16 * cb, dv[cb][r]);
+            for (int cb = 0; cb < CB; ++cb) {
+                if constexpr (DROP) put_io<IO16>(op + 2 * D + 16 * cb, dv[cb][r] * dr.rinv);
+                else put_io<IO16>(op + 2 * D + 16 * cb, dv[cb][r]);
+            }
         }
     }
 }
@@ -593,13 +651,14 @@ static void attn_x3_dispatch(int hd, AttnMode mode, F&& f) {
 
 // launchers, called from attn.hip's attn_fwd / attn_bwd for every mode but ATTN_NATIVE (arguments already validated there: hd is 32 or 64)
 void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
-                        float* lse, hipStream_t s) {
+                        float* lse, hipStream_t s, const DropArgs* dr) {
     const int n_tiles = (max_len + 63) / 64;
     const dim3 grid(attn_grid(H, B, n_tiles));
     attn_x3_dispatch(hd, mode, [&](auto form) {
         typedef decltype(form) F;
         typedef typename F::io_t T;
-        hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, n_tiles);
+        if (dr) hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16, DropArgs>), grid, dim3(256), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, n_tiles, *dr);
+        else hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, n_tiles);
     });
 }
 
@@ -631,7 +690,7 @@ static AttnFork* attn_fork_of_device() {
 }
 
 void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
-                        int64_t n_total, int H, int hd, float scale, void* dqkv, const float* delta, hipStream_t s) {
+                        int64_t n_total, int H, int hd, float scale, void* dqkv, const float* delta, hipStream_t s, const DropArgs* dr) {
     const int n_tiles = (max_len + 63) / 64;
     const dim3 grid(attn_grid(H, B, n_tiles));
     AttnFork* f = attn_fork_of_device();
@@ -644,8 +703,13 @@ void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const 
     attn_x3_dispatch(hd, mode, [&](auto form) {
         typedef decltype(form) F;
         typedef typename F::io_t T;
-        hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
-        hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
+        if (dr) {
+            hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16, DropArgs>), grid, dim3(256), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles, *dr);
+            hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16, DropArgs>), grid, dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles, *dr);
+        } else {
+            hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
+            hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
+        }
     });
     if (f) {
         hipEventRecord(f->join, f->side);
@@ -684,6 +748,29 @@ int u3d_attn_varlen_bwd_b16(const void* qkv, const void* out, const void* dout, 
                             int B, int max_len, int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws,
                             double flops_hint, u3d_stream_t stream) {
     return attn_bwd(ATTN_B16, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream);
+}
+
+// dropout forms of the four entry points above (include/u3d.h "dropout"): the same arguments plus (p, seed, offset)
+int u3d_attn_varlen_fwd_drop_bf16(const float* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
+                                  float scale, float* out, float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset) {
+    return attn_fwd_drop(ATTN_BF16_OPS, qkv, cu_seqlens, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream, p, seed, offset);
+}
+
+int u3d_attn_varlen_bwd_drop_bf16(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu_seqlens,
+                                  int B, int max_len, int64_t n_total, int H, int hd, float scale, float* dqkv, float* delta_ws,
+                                  double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset) {
+    return attn_bwd_drop(ATTN_BF16_OPS, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream, p, seed, offset);
+}
+
+int u3d_attn_varlen_fwd_drop_b16(const void* qkv, const int32_t* cu_seqlens, int B, int max_len, int64_t n_total, int H, int hd,
+                                 float scale, void* out, float* lse, double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset) {
+    return attn_fwd_drop(ATTN_B16, qkv, cu_seqlens, B, max_len, n_total, H, hd, scale, out, lse, flops_hint, stream, p, seed, offset);
+}
+
+int u3d_attn_varlen_bwd_drop_b16(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu_seqlens,
+                                 int B, int max_len, int64_t n_total, int H, int hd, float scale, void* dqkv, float* delta_ws,
+                                 double flops_hint, u3d_stream_t stream, double p, uint64_t seed, uint64_t offset) {
+    return attn_bwd_drop(ATTN_B16, qkv, out, dout, lse, cu_seqlens, B, max_len, n_total, H, hd, scale, dqkv, delta_ws, flops_hint, stream, p, seed, offset);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "dropout.h"
 #include "u3d_common.h"
 
 namespace u3d {
@@ -165,6 +166,92 @@ int exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, void* ws, hip
     return scan_impl(LoadI32{in}, n, out, ws, s);
 }
 
+// ---- dropout (csrc/dropout.h) -------------------------------------------------------------------------------------
+// mask dump: out[a][b][c] = keep(seed, offset, a, b, c), one byte per element -- the device function with trivial indexing
+__global__ __launch_bounds__(256) void dropout_mask_k(uint64_t seed, uint64_t offset, uint32_t thr, int A, int64_t nb, int64_t nc, uint8_t* __restrict__ out) {
+    const int64_t total = (int64_t)A * nb * nc;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t c = i % nc, ab = i / nc;
+        out[i] = drop_keep(seed, offset, (uint32_t)(ab / nb), (uint32_t)(ab % nb), (uint32_t)c, thr) ? 1 : 0;
+    }
+}
+
+// double -> fp32 rounded to ODD (truncate towards zero, set the last bit when inexact): rounding the result to bf16 afterwards (nearest
+// even, 16 bits shorter) gives the bf16 value nearest to the double -- ONE rounding, where double -> fp32 -> bf16 to nearest twice can
+// land on the other neighbour of a tie the first rounding made.  Finite values in fp32's normal range.
+__device__ __forceinline__ float f32_round_to_odd(double d) {
+    float f = (float)d;
+    if ((double)f != d) {
+        unsigned u = __builtin_bit_cast(unsigned, f);
+        if (fabs((double)f) > fabs(d)) u -= 1u;          // the magnitude one ulp down (sign-magnitude; f != 0 here)
+        f = __builtin_bit_cast(float, u | 1u);
+    }
+    return f;
+}
+
+// y = x . M / (1 - p) over [n, C], (a, b, c) = (0, row, column); the same kernel maps dy to dx.  One 16-byte vector per thread and trip:
+// four fp32 or eight bf16 values of one row.  The product is formed in double and rounded once to the tensor's type.
+template <bool B16>
+__global__ __launch_bounds__(256) void dropout_k(const u32x4* __restrict__ x, u32x4* __restrict__ y, int64_t nvec, int vec_per_row, DropKey key, uint32_t thr,
+                                                 double rinv) {
+    constexpr int W = B16 ? 8 : 4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / vec_per_row;
+        const uint32_t c0 = (uint32_t)(i - row * vec_per_row) * W;
+        const DropRow r = drop_row(key, (uint32_t)row);
+        const u32x4 v = x[i];
+        u32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (B16) {
+                const float lo = bf16_bits_to_f32((unsigned short)v[j]), hi = __builtin_bit_cast(float, v[j] & 0xffff0000u);
+                const float a = drop_hash32(r, c0 + 2 * j) >= thr ? f32_round_to_odd((double)lo * rinv) : 0.f;
+                const float b = drop_hash32(r, c0 + 2 * j + 1) >= thr ? f32_round_to_odd((double)hi * rinv) : 0.f;
+                o[j] = pack_bf16(a, b);
+            } else {
+                const unsigned w = v[j];          // (a copy: bit_cast of the vector element itself reads element 0 for every j)
+                const float a = drop_hash32(r, c0 + j) >= thr ? (float)((double)__builtin_bit_cast(float, w) * rinv) : 0.f;
+                o[j] = __builtin_bit_cast(unsigned, a);
+            }
+        }
+        y[i] = o;
+    }
+}
+
+static bool dropout_p_ok(const char* what, double p) {
+    if (p >= 0.0 && p < 1.0) return true;          // false for NaN
+    set_error("%s: dropout probability %g outside [0, 1)", what, p);
+    return false;
+}
+
+static int dropout_mask(const char* what, double p, uint64_t seed, uint64_t offset, int A, int64_t nb, int64_t nc, uint8_t* mask, u3d_stream_t stream) {
+    if (!dropout_p_ok(what, p)) return U3D_EINVAL;
+    if (!mask || A < 0 || nb < 0 || nc < 0 || nb > 0xffffffffll || nc > 0xffffffffll) return U3D_EINVAL;
+    const int64_t total = (int64_t)A * nb * nc;
+    if (!total) return U3D_OK;
+    const int64_t g = ceil_div(total, 256);
+    hipLaunchKernelGGL(dropout_mask_k, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(256), 0, (hipStream_t)stream, seed, offset, drop_args(p, seed, offset).thr, A,
+                       nb, nc, mask);
+    return check_launch(what);
+}
+
+template <bool B16>
+static int dropout_rows(const char* what, const void* x, void* y, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream) {
+    constexpr int W = B16 ? 8 : 4;
+    if (!dropout_p_ok(what, p)) return U3D_EINVAL;
+    if (!x || !y || n < 0 || n > 0xffffffffll || C <= 0) return U3D_EINVAL;
+    if (C % W) {
+        set_error("%s: C = %d must be a multiple of %d (16-byte vectors)", what, C, W);
+        return U3D_EINVAL;
+    }
+    if (!n) return U3D_OK;
+    const int64_t nvec = n * (C / W), g = ceil_div(nvec, 256);
+    const DropArgs a = drop_args(p, seed, offset);
+    hipLaunchKernelGGL(dropout_k<B16>, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, (hipStream_t)stream, (const u32x4*)x, (u32x4*)y, nvec, C / W,
+                       drop_key(seed, offset, 0u), a.thr, 1.0 / (1.0 - p));
+    return check_launch(what);
+}
+
 }  // namespace u3d
 
 extern "C" {
@@ -219,6 +306,25 @@ int64_t u3d_index_rank_ws_bytes(int64_t n_words) { return u3d::scan_ws_bytes(n_w
 int u3d_index_rank(const uint64_t* bitmap, int64_t n_words, int32_t* word_rank, void* ws, u3d_stream_t stream) {
     if (!bitmap || !word_rank || n_words <= 0) return U3D_EINVAL;
     return u3d::exclusive_scan_popc64(bitmap, n_words, word_rank, ws, (hipStream_t)stream);
+}
+
+int u3d_dropout_mask_attn(double p, uint64_t seed, uint64_t offset, int H, int64_t n_total, uint8_t* mask, u3d_stream_t stream) {
+    return u3d::dropout_mask("dropout_mask_attn", p, seed, offset, H, n_total, n_total, mask, stream);
+}
+int u3d_dropout_mask_rows(double p, uint64_t seed, uint64_t offset, int64_t n, int C, uint8_t* mask, u3d_stream_t stream) {
+    return u3d::dropout_mask("dropout_mask_rows", p, seed, offset, 1, n, C, mask, stream);
+}
+int u3d_dropout_fwd(const float* x, float* y, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream) {
+    return u3d::dropout_rows<false>("dropout_fwd", x, y, n, C, p, seed, offset, stream);
+}
+int u3d_dropout_bwd(const float* dy, float* dx, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream) {
+    return u3d::dropout_rows<false>("dropout_bwd", dy, dx, n, C, p, seed, offset, stream);
+}
+int u3d_dropout_fwd_b16(const void* x, void* y, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream) {
+    return u3d::dropout_rows<true>("dropout_fwd_b16", x, y, n, C, p, seed, offset, stream);
+}
+int u3d_dropout_bwd_b16(const void* dy, void* dx, int64_t n, int C, double p, uint64_t seed, uint64_t offset, u3d_stream_t stream) {
+    return u3d::dropout_rows<true>("dropout_bwd_b16", dy, dx, n, C, p, seed, offset, stream);
 }
 
 }  // extern "C"

@@ -255,6 +255,17 @@ class _Flow32:
                    M, d_in, hid, d_out, 1.0 if _PROFILE_FLOPS else 0.0, L.stream())
         return h, a, z
 
+    def relu_nt(self, x, w, bias, planes=None):
+        """relu(x W^T + b) as one call (u3d_linear_act): the first half of ``ffn`` when something runs between the two GEMMs"""
+        M, K = x.shape
+        N = w.shape[0]
+        a = torch.empty(M, N, dtype=torch.float32, device=x.device)
+        if M:
+            if not self.bf:
+                _use_planes(w, planes)
+            L.call('u3d_linear_act', L.ptr(x), L.ptr(w), L.ptr(bias), ACT_RELU | self.flag, None, L.ptr(a), M, N, K, _book(M, N, K), L.stream())
+        return a
+
     def ln_linear(self, x, gamma, beta, eps, w, bias):
         """(nq, None, stats, y) = (LayerNorm(x), no bf16 copy, row statistics, nq W^T + b): include/u3d.h u3d_ln_linear"""
         M, C = x.shape
@@ -403,13 +414,54 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias=None, out_bf16: bool = Fa
 FUSE_GELU = os.environ.get('U3D_FUSE_GELU', '0') == '1'
 
 
+def _dropout_pass(name, t, p, key):
+    """one launch of the elementwise dropout kernel over a 2-D tensor (fp32, or bf16 for the ``_b16`` names): t . M / (1 - p)"""
+    out = torch.empty_like(t)
+    if t.numel():
+        L.call(name, L.ptr(t), L.ptr(out), t.shape[0], t.shape[1], float(p), int(key[0]), int(key[1]), L.stream())
+    return out
+
+
+def _dropout_name(t, direction):
+    return f'u3d_dropout_{direction}' + ('_b16' if t.dtype == torch.bfloat16 else '')
+
+
+class _DropoutFn(torch.autograd.Function):
+    """y = x . M / (1 - p) with M = the mask of ``key`` over (row, column) (csrc/dropout.h); nothing is saved but the key -- backward
+    regenerates the mask.  The tensor keeps its type: fp32, or bf16 under dense16.FLOW (the attention output)."""
+
+    @staticmethod
+    def forward(ctx, x, p, key):
+        x = x.contiguous()
+        ctx.p, ctx.key = p, key
+        return _dropout_pass(_dropout_name(x, 'fwd'), x, p, key)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        return _dropout_pass(_dropout_name(dy, 'bwd'), dy, ctx.p, ctx.key), None, None
+
+
+def dropout(x: torch.Tensor, p: float, key) -> torch.Tensor:
+    """Dropout of a 2-D tensor [n, C] (fp32: C % 4 == 0; bf16: C % 8 == 0) with probability ``p`` and the mask of ``key = (seed,
+    offset)``: the same key gives the same mask (``ops.dropout_mask_rows`` dumps it).  One launch each way."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise L.U3DError('dropout: a 2-D fp32 or bf16 tensor is expected')
+    return _DropoutFn.apply(x, float(p), (int(key[0]), int(key[1])))
+
+
 class _MLPFn(torch.autograd.Function):
     """z = act(x W1^T + b1) W2^T + b2.  Fused (ReLU always, GELU under FUSE_GELU): bias and activation live in the first GEMM's
     epilogue (``flow.ffn``), the activation's derivative in the epilogue of the GEMM that produces the hidden gradient -- no
-    elementwise kernels.  Under dense16.FLOW the hidden tensors (and their gradients) exist in bf16 only; z is fp32."""
+    elementwise kernels.  Under dense16.FLOW the hidden tensors (and their gradients) exist in bf16 only; z is fp32.
+    ``drop = (p, key)``: dropout on the hidden activation (the reference's FFN, unidet3d/encoder.py:55-61).  The dropped tensor is what
+    the second Linear reads and what is saved for its weight gradient; the hidden gradient is masked and scaled before the activation's
+    derivative, which reads the saved activation ``a`` (ReLU: the undropped one -- a dropped element's gradient is already zero -- so
+    the fused epilogue still applies) or pre-activation ``h`` (GELU).  The two GEMMs then run as calls of their own with the dropout
+    pass between them."""
 
     @staticmethod
-    def forward(ctx, flow, x, w1, b1, w2, b2, act):
+    def forward(ctx, flow, x, w1, b1, w2, b2, act, drop=None):
         x = x.contiguous()
         xa = flow.operand(x)
         w1c, w2c = w1.contiguous(), w2.contiguous()
@@ -418,7 +470,19 @@ class _MLPFn(torch.autograd.Function):
         ctx.wtp1, ctx.wtp2 = _planes_of(ctx.wt1), _planes_of(ctx.wt2)
         p1, p2 = _planes_of(w1c), _planes_of(w2c)
         ctx.fused = act != ACT_GELU or (FUSE_GELU and not flow.act16)
-        if ctx.fused:
+        ctx.drop = drop
+        if drop is not None:                            # GEMM (+bias, activation) -> dropout pass -> plain GEMM
+            if act == ACT_GELU:
+                ctx.fused = False
+                h = flow.nt(xa, w1c, b1, out_bf16=True, planes=p1)
+                a = _gelu_pass(flow.gelu[0], h)
+                a = _dropout_pass(_dropout_name(a, 'fwd'), a, *drop)          # the undropped activation is not needed again
+            else:
+                h = None
+                a = flow.relu_nt(xa, w1c, b1, p1)
+                a = _dropout_pass(_dropout_name(a, 'fwd'), a, *drop)
+            z = flow.nt(a, w2c, b2, planes=p2)
+        elif ctx.fused:
             h, a, z = flow.ffn(xa, w1c, b1, w2c, b2, act, p1, p2)
         else:                                           # plain GEMM (+bias) -> GELU pass -> plain GEMM
             h = flow.nt(xa, w1c, b1, out_bf16=True, planes=p1)
@@ -437,7 +501,17 @@ class _MLPFn(torch.autograd.Function):
         dza = flow.operand(dz)
         need = ctx.needs_input_grad[1:]
         dw2, db2 = _weight_grad_overlapped(flow, dza, a, ctx.bias[1] and need[4], w2, ctx.bias_refs[1]) if need[3] else (None, None)
-        if ctx.fused:
+        if ctx.drop is not None:
+            # da = dz W2, masked and scaled, then the activation's derivative.  ReLU's derivative is a 0 / 1 factor that commutes with
+            # the mask exactly, and [a_dropped > 0] equals relu'(pre) wherever the mask keeps the element: the fused epilogue on the
+            # saved (dropped) activation, then the mask.
+            if ctx.act == ACT_GELU:
+                da = _input_grad(flow, dza, w2, ctx.wt2, ctx.wtp2, out_bf16=True)
+                dh = _gelu_pass(flow.gelu[1], _dropout_pass(_dropout_name(da, 'bwd'), da, *ctx.drop), h)
+            else:
+                da = _input_grad(flow, dza, w2, ctx.wt2, ctx.wtp2, EPI_RELU_MASK, a, out_bf16=True)
+                dh = _dropout_pass(_dropout_name(da, 'bwd'), da, *ctx.drop)
+        elif ctx.fused:
             epi, aux = (EPI_GELU_MASK, h) if ctx.act == ACT_GELU else (EPI_RELU_MASK, a)
             dh = _input_grad(flow, dza, w2, ctx.wt2, ctx.wtp2, epi, aux, out_bf16=True)
         else:
@@ -448,12 +522,15 @@ class _MLPFn(torch.autograd.Function):
             db2 = dz.float().sum(0)
         if db1 is None and ctx.bias[0] and need[2]:
             db1 = dh.float().sum(0)
-        return None, dx, dw1, db1, dw2, db2, None
+        return None, dx, dw1, db1, dw2, db2, None, None
 
 
-def mlp(x, w1, b1, w2, b2, act: str) -> torch.Tensor:
-    """Linear -> ReLU / GELU -> Linear on 2-D x (d_in, hidden % 16 == 0)."""
-    return _MLPFn.apply(_flow(x, x.shape[1], w1.shape[0]), x, w1, b1, w2, b2, {'relu': ACT_RELU, 'gelu': ACT_GELU}[act])
+def mlp(x, w1, b1, w2, b2, act: str, drop=None) -> torch.Tensor:
+    """Linear -> ReLU / GELU -> Linear on 2-D x (d_in, hidden % 16 == 0).  ``drop = (p, (seed, offset))``: dropout on the hidden
+    activation, between the activation and the second Linear."""
+    if drop is not None:
+        drop = (float(drop[0]), (int(drop[1][0]), int(drop[1][1])))
+    return _MLPFn.apply(_flow(x, x.shape[1], w1.shape[0]), x, w1, b1, w2, b2, {'relu': ACT_RELU, 'gelu': ACT_GELU}[act], drop)
 
 
 def _aliases(y, n_out):

@@ -99,6 +99,11 @@ def _ffn(x, w1, b1, w2, b2, act, p1, p2):
     return None, a, gemm_nt(a, w2, b2)
 
 
+def _relu_nt(x, w, bias, planes=None):
+    """relu(x W^T + b) in bf16: the first half of ``_ffn``"""
+    return gemm_nt(x, w, bias, EPI_RELU, out_bf16=True)
+
+
 def _ln_linear(x, gamma, beta, eps, w, bias):
     """(nq, nq16, stats, y) = (LayerNorm(x), its bf16 copy, row statistics, nq W^T + b) with the Linear streaming nq16"""
     nq, nq16, stats = D._layer_norm_fwd(FLOW, x, None, gamma, beta, eps, None)
@@ -115,6 +120,7 @@ class FLOW:
     tn = staticmethod(_tn)
     tn_q = staticmethod(_tn_q)
     ffn = staticmethod(_ffn)
+    relu_nt = staticmethod(_relu_nt)
     ln_linear = staticmethod(_ln_linear)
     attach = staticmethod(attach_b16)
 

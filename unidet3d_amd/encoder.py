@@ -26,7 +26,7 @@ from torch import nn
 from . import _lib as L
 from . import precision as P
 from . import account
-from .dense import LayerNorm, linear, ln_linear, mlp
+from .dense import LayerNorm, dropout, linear, ln_linear, mlp
 from .ops import cat_views
 from .registry import MODELS
 
@@ -35,8 +35,11 @@ _LN_ALIASES = os.environ.get('U3D_LN_ALIASES', '1') != '0'
 
 
 class _AttnFn(torch.autograd.Function):
+    """``p`` > 0: dropout on the softmax probabilities with the mask of ``(seed, offset)`` (the u3d_attn_varlen_*_drop entry points; the
+    backward call regenerates the mask from the same three values); ``p`` == 0: the entry points without dropout."""
+
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_len, H, sum_sq):
+    def forward(ctx, qkv, cu_seqlens, max_len, H, sum_sq, p=0.0, seed=0, offset=0):
         qkv = qkv.contiguous()
         n, d3 = qkv.shape
         d = d3 // 3
@@ -51,9 +54,10 @@ class _AttnFn(torch.autograd.Function):
             account.add('attn_fwd', flops, qkv.element_size() * n * 4 * d + 4.0 * n * H)
         ctx.sum_sq = sum_sq
         ctx.sfx = '_b16' if b16 else ('_bf16' if P.bf16() else '')
+        ctx.drop = (float(p), int(seed), int(offset)) if p else ()
         if n:
-            L.call('u3d_attn_varlen_fwd' + ctx.sfx, L.ptr(qkv), L.ptr(cu_seqlens), B, max_len, n, H, hd, 1.0 / math.sqrt(hd),
-                   L.ptr(out), L.ptr(lse), flops, L.stream())
+            L.call('u3d_attn_varlen_fwd' + ('_drop' if p else '') + ctx.sfx, L.ptr(qkv), L.ptr(cu_seqlens), B, max_len, n, H, hd,
+                   1.0 / math.sqrt(hd), L.ptr(out), L.ptr(lse), flops, L.stream(), *ctx.drop)
         ctx.save_for_backward(qkv, out, lse, cu_seqlens)
         ctx.max_len, ctx.H = max_len, H
         return out
@@ -72,15 +76,20 @@ class _AttnFn(torch.autograd.Function):
         if flops:
             account.add('attn_bwd', flops, qkv.element_size() * n * 8 * (d3 // 3) + 4.0 * n * 2 * H)
         if n:
-            L.call('u3d_attn_varlen_bwd' + ctx.sfx, L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(cu), cu.numel() - 1,
-                   ctx.max_len, n, H, hd, 1.0 / math.sqrt(hd), L.ptr(dqkv), L.ptr(delta), flops, L.stream())
-        return dqkv, None, None, None, None
+            L.call('u3d_attn_varlen_bwd' + ('_drop' if ctx.drop else '') + ctx.sfx, L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(cu),
+                   cu.numel() - 1, ctx.max_len, n, H, hd, 1.0 / math.sqrt(hd), L.ptr(dqkv), L.ptr(delta), flops, L.stream(), *ctx.drop)
+        return dqkv, None, None, None, None, None, None, None
 
 
-def attention_varlen(qkv, cu_seqlens, max_len, num_heads, sum_sq=0):
+def attention_varlen(qkv, cu_seqlens, max_len, num_heads, sum_sq=0, p=0.0, key=(0, 0)):
     """softmax(Q K^T / sqrt(hd)) V per scene and head; qkv [n, 3*d] packed, cu_seqlens int32 [B+1];
-    ``sum_sq`` = sum of n_i^2 (host value, only used for the bench's flops accounting)."""
-    return _AttnFn.apply(qkv, cu_seqlens, max_len, num_heads, sum_sq)
+    ``sum_sq`` = sum of n_i^2 (host value, only used for the bench's flops accounting).  ``p`` > 0: dropout with probability ``p`` on the
+    softmax probabilities, as nn.MultiheadAttention applies it, with the mask of ``key = (seed, offset)`` (``ops.dropout_mask_attn``)."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'dropout probability {p} outside [0, 1)')
+    if not p:
+        return _AttnFn.apply(qkv, cu_seqlens, max_len, num_heads, sum_sq)
+    return _AttnFn.apply(qkv, cu_seqlens, max_len, num_heads, sum_sq, float(p), int(key[0]), int(key[1]))
 
 
 class _MHA(nn.Module):
@@ -95,25 +104,27 @@ class _MHA(nn.Module):
         nn.init.xavier_uniform_(self.in_proj_weight)
         nn.init.zeros_(self.out_proj.bias)
 
-    def forward(self, x, cu_seqlens, max_len, sum_sq=0):
+    def forward(self, x, cu_seqlens, max_len, sum_sq=0, p=0.0, key=(0, 0)):
         qkv = linear(x, self.in_proj_weight, self.in_proj_bias, out_bf16=True)     # a bf16 tensor under precision.bf16_act(), fp32 otherwise
-        o = attention_varlen(qkv, cu_seqlens, max_len, self.num_heads, sum_sq)
+        o = attention_varlen(qkv, cu_seqlens, max_len, self.num_heads, sum_sq, p, key)
         return linear(o, self.out_proj.weight, self.out_proj.bias)
 
 
 class SelfAttentionLayer(nn.Module):          # encoder.py:8-41
     def __init__(self, d_model, num_heads, dropout):
         super().__init__()
-        if dropout != 0.0:
-            raise NotImplementedError('the reference configs use dropout=0.0; dropout is not built')
         self.attn = _MHA(d_model, num_heads)
         self.norm = LayerNorm(d_model)
 
-    def forward(self, x, cu_seqlens, max_len, sum_sq=0, res=None, n_out=1):
+    def forward(self, x, cu_seqlens, max_len, sum_sq=0, res=None, n_out=1, drop=None):
         """LayerNorm(attn(x) + res), the add inside the LayerNorm kernel.  ``res``: the residual (default x) -- the encoder hands the
         attention and the residual their own alias of the previous LayerNorm's result; ``n_out``: how many aliases of THIS result to
-        return (one per consumer: their gradients are summed in the LayerNorm's backward kernel, dense.layer_norm)."""
-        return self.norm(self.attn(x, cu_seqlens, max_len, sum_sq), x if res is None else res, n_out)
+        return (one per consumer: their gradients are summed in the LayerNorm's backward kernel, dense.layer_norm).
+        ``drop = (p, key of the probabilities, key of the output)``: LayerNorm(dropout(attn_p(x)) + res), encoder.py:19-22,38."""
+        if drop is None:
+            return self.norm(self.attn(x, cu_seqlens, max_len, sum_sq), x if res is None else res, n_out)
+        p, k_prob, k_out = drop
+        return self.norm(dropout(self.attn(x, cu_seqlens, max_len, sum_sq, p, k_prob), p, k_out), x if res is None else res, n_out)
 
 
 class FFN(nn.Module):                         # encoder.py:43-80
@@ -124,9 +135,15 @@ class FFN(nn.Module):                         # encoder.py:43-80
         self.norm = LayerNorm(d_model)
         self.act = 'relu' if activation_fn == 'relu' else 'gelu'
 
-    def forward(self, x, res=None, n_out=1):
+    def forward(self, x, res=None, n_out=1, drop=None):
         # bias + activation in the first GEMM's epilogue, residual add inside the LayerNorm kernel (``res`` / ``n_out``: SelfAttentionLayer)
-        return self.norm(mlp(x, self.net[0].weight, self.net[0].bias, self.net[3].weight, self.net[3].bias, self.act), x if res is None else res, n_out)
+        # ``drop = (p, key of the hidden activation, key of the output)``: the two nn.Dropout of ``net`` (encoder.py:55-61), which hold no
+        # state and are never called -- the hidden one runs inside ``mlp``, the second on its result
+        w1, b1, w2, b2 = self.net[0].weight, self.net[0].bias, self.net[3].weight, self.net[3].bias
+        if drop is None:
+            return self.norm(mlp(x, w1, b1, w2, b2, self.act), x if res is None else res, n_out)
+        p, k_hid, k_out = drop
+        return self.norm(dropout(mlp(x, w1, b1, w2, b2, self.act, drop=(p, k_hid)), p, k_out), x if res is None else res, n_out)
 
 
 class PredBBox(nn.Module):                    # encoder.py:82-111
@@ -225,6 +242,13 @@ class UniDet3DEncoder(nn.Module):
     def __init__(self, num_layers, datasets_classes, in_channels, d_model, num_heads, hidden_dim, dropout,
                  activation_fn, datasets, angles, **kwargs):
         super().__init__()
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f'dropout probability {dropout} outside [0, 1)')
+        # Dropout state: plain attributes, not buffers -- the state_dict keys stay the reference's.  The mask of a site is
+        # a hash of (seed, offset): the seed is per model, the offset counts (training step, layer, site).
+        self.dropout_p = float(dropout)
+        self.dropout_seed = None            # taken from torch.initial_seed() by the first training-mode forward unless set_dropout_state set it
+        self.dropout_step = 0               # training-mode forwards so far (host counter: no device read, no wait)
         self.num_layers = num_layers
         self.datasets = datasets
         self.angles = angles
@@ -238,6 +262,35 @@ class UniDet3DEncoder(nn.Module):
         self.datasets_cls_idxs = [[unique_cls.index(c) for c in dc] + [-1] for dc in datasets_classes]
         self.out_bboxes = PredBBox(d_model, 8)
         self._cidx_cache = {}
+
+    DROP_PROB, DROP_ATTN_OUT, DROP_FFN_HIDDEN, DROP_FFN_OUT = 0, 1, 2, 3         # ``which`` of dropout_key: the four sites of a layer
+
+    def set_dropout_state(self, seed: int, step: int = 0):
+        """Seed and step counter of the dropout masks, for a reproducible run or resume: the forward passes that follow draw the masks a
+        run with the same seed drew from step ``step`` on.  (Not part of ``state_dict``.)"""
+        seed, step = int(seed), int(step)
+        if not 0 <= seed < 1 << 64 or step < 0:
+            raise ValueError('dropout seed must fit 64 bits, step must not be negative')
+        self.dropout_seed, self.dropout_step = seed, step
+
+    def dropout_key(self, step: int, layer: int, which: int):
+        """``(seed, offset)`` of one dropout site: ``offset = step 4 num_layers + 4 layer + which``, ``which`` 0 the attention
+        probabilities, 1 the attention output, 2 the FFN hidden activation, 3 the FFN output.  ``ops.dropout_mask_attn`` (site 0) and
+        ``ops.dropout_mask_rows`` (sites 1-3) give the mask that training step ``step`` applies there."""
+        if not (step >= 0 and 0 <= layer < self.num_layers and 0 <= which < 4):
+            raise ValueError(f'dropout_key: step {step}, layer {layer} or site {which} out of range')
+        if self.dropout_seed is None:
+            self.dropout_seed = int(torch.initial_seed()) & ((1 << 64) - 1)
+        return self.dropout_seed, int(step) * 4 * self.num_layers + 4 * int(layer) + int(which)
+
+    def _drop_keys(self):
+        """per layer ((p, key 0, key 1), (p, key 2, key 3)) of this training-mode forward -- and the step counter moves on -- or None"""
+        if not (self.training and self.dropout_p > 0.0):
+            return None
+        step, p = self.dropout_step, self.dropout_p
+        self.dropout_step += 1
+        return [((p, self.dropout_key(step, i, 0), self.dropout_key(step, i, 1)), (p, self.dropout_key(step, i, 2), self.dropout_key(step, i, 3)))
+                for i in range(self.num_layers)]
 
     def _cidx(self, idx, device):
         key = (idx, str(device))
@@ -305,16 +358,18 @@ class UniDet3DEncoder(nn.Module):
         # as one alias per consumer: the gradients then reach the LayerNorm's backward kernel separately and are summed there as they are
         # read -- 16 of autograd's 18 elementwise gradient sums per step (cfg2: 52 MB each) are gone.
         x_in = r_in = feats
+        keys = self._drop_keys()                 # None in eval mode and at dropout = 0: exactly the calls without dropout
         for i in range(self.num_layers):
+            da, df = keys[i] if keys is not None else (None, None)
             if not _LN_ALIASES:                  # U3D_LN_ALIASES=0: one tensor per result, autograd sums (A/B runs)
-                feats = self.ffn_layers[i](self.self_attn_layers[i](feats, cu, max_len, sum_sq))
+                feats = self.ffn_layers[i](self.self_attn_layers[i](feats, cu, max_len, sum_sq, drop=da), drop=df)
                 layer_feats.append(feats)
                 continue
-            a_in, a_res = self.self_attn_layers[i](x_in, cu, max_len, sum_sq, res=r_in, n_out=2)
+            a_in, a_res = self.self_attn_layers[i](x_in, cu, max_len, sum_sq, res=r_in, n_out=2, drop=da)
             if i + 1 < self.num_layers:
-                x_in, r_in, feats = self.ffn_layers[i](a_in, res=a_res, n_out=3)
+                x_in, r_in, feats = self.ffn_layers[i](a_in, res=a_res, n_out=3, drop=df)
             else:
-                feats = self.ffn_layers[i](a_in, res=a_res)
+                feats = self.ffn_layers[i](a_in, res=a_res, drop=df)
             layer_feats.append(feats)
         # The reference applies the shared prediction head after the input projection and after every layer (encoder.py:221-239).
         # The head is row-wise (LayerNorm, Linear, ReLU), so its num_layers + 1 applications on [n, d] are ONE application on the

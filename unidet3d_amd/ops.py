@@ -443,6 +443,22 @@ def cat_views(ts):
     return torch.cat(ts)
 
 
+def dropout_mask_attn(p: float, seed: int, offset: int, H: int, n_total: int, device='cuda') -> torch.Tensor:
+    """uint8 [H, n_total, n_total], 1 = kept: the mask the attention kernels apply to the softmax probabilities of a packed matrix of
+    ``n_total`` rows for the key ``(seed, offset)`` (``UniDet3DEncoder.dropout_key``); rows and columns are PACKED row indices, so
+    scene b's block is ``[:, cu[b]:cu[b+1], cu[b]:cu[b+1]]``.  The kernels never store it -- this is the same device function, dumped."""
+    mask = torch.empty(int(H), int(n_total), int(n_total), dtype=torch.uint8, device=device)
+    L.call('u3d_dropout_mask_attn', float(p), int(seed), int(offset), int(H), int(n_total), L.ptr(mask), L.stream())
+    return mask
+
+
+def dropout_mask_rows(p: float, seed: int, offset: int, n: int, C: int, device='cuda') -> torch.Tensor:
+    """uint8 [n, C], 1 = kept: the mask ``dense.dropout`` applies to an [n, C] tensor for the key ``(seed, offset)``"""
+    mask = torch.empty(int(n), int(C), dtype=torch.uint8, device=device)
+    L.call('u3d_dropout_mask_rows', float(p), int(seed), int(offset), int(n), int(C), L.ptr(mask), L.stream())
+    return mask
+
+
 def offset_ids(ids, biases, keep_negative: bool = False) -> torch.Tensor:
     """``torch.cat([ids[i] + biases[i] for i])`` for per-scene int64 id tensors (superpoint / instance ids made batch-global) in a handful
     of multi-tensor launches whatever the number of scenes.  ``keep_negative``: ids < 0 ("no instance") stay as they are:
