@@ -209,10 +209,16 @@ int u3d_weight_pack_batch(const void* desc, int n_desc, int64_t total_blocks, u3
 /* Launch plan for a shape: tile_rows (rows per wave-tile = the tile height to pass to u3d_tile_starts) and
  * k_groups (kernel offsets are split into that many groups when the level has too few rows to fill the chip;
  * the groups' partial sums go through ws = k_groups*n_dst*Cd*4 bytes and a fixed-order reduce).
- * Returns U3D_EUNSUPPORTED for channel counts that are not instantiated. */
+ * Channel contract of the sparse convolutions (forward, input gradient, weight gradient): Cs in {16} u {32, 64, ..., 512},
+ * Cd in {32, 64, ..., 512}; U3D_EUNSUPPORTED for anything else, before any HIP call.  The widths of the 32-channel five-level U-Net
+ * (Cs / 16 in {1, 2, 4, 6, 8, 10, 12, 16}) run fully unrolled kernels, every other width a run-time loop over 32 / 64 / 128-channel
+ * chunks of the source row; the weight gradient has 17 whole-block (Cs, Cd) kernels and a channel-blocked walk for the rest. */
 int u3d_spconv_plan(int Cs, int Cd, int K, int64_t n_dst, int* tile_rows, int* k_groups);
 /* the plan u3d_spconv_gmm_bf16a wants (its light items prefer 32-row tiles and fewer offset groups at the small levels) */
 int u3d_spconv_plan_bf16a(int Cs, int Cd, int K, int64_t n_dst, int* tile_rows, int* k_groups);
+/* 1 where u3d_spconv_gmm_bf16a has a kernel for the source width (those of the 32-channel five-level U-Net: Cs in {32, 64, 96, 128, 160,
+ * 192, 256}), else 0: the caller then gathers the fp32 rows with bf16 operands (u3d_spconv_gmm_bf16) -- same operands, same results. */
+int u3d_spconv_gmm_bf16a_supported(int Cs, int Cd);
 /* ---- tile-stationary SubMConv3d(k=3) (csrc/spconv_ts.hip; unidet3d/spconv_unet.py:43-56): accumulators of a row tile in registers
  * for all 27 offsets and all C_out columns, every source row of a tile fetched once.
  * u3d_subm_halo builds, per tile of tile_rows consecutive rows (64 / 128 / 256) of a level, from the same occupancy index the

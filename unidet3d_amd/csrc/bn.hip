@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const float* __restrict__ 
     }
 }
 
-static bool bn_ok(int64_t n, int C) { return n > 0 && C >= 4 && C <= 256 && C % 4 == 0; }
+static bool bn_ok(int64_t n, int C) { return n > 0 && C >= 4 && C <= 512 && C % 4 == 0; }      // bn_reduce_k: C / 4 <= 256 lanes per row
 static bool shadow_ok(const void* sh, int C) { return !sh || C % 32 == 0; }
 static unsigned ew_grid(int64_t n4) {
     int64_t g = ceil_div(n4, 256);

@@ -80,7 +80,9 @@ struct GmmItem {
 // PR = 0: fp32 MFMAs; 1: bf16 operands (above); 2: fp32 products from three exact bf16 planes per operand (u3d_common.h "bf16x3"):
 // same operand shapes as PR = 1, the gathered rows are split where PR = 1 rounds them, the weights come pre-split from
 // u3d_weight_pack_x3 (three 1 KB blocks per (32-channel group, column block)), and a fragment pair takes six MFMAs.
-template <int CS16, int R, int JB_, int PR = 0>
+// CHUNKED: the wave walks its items once per CHUNK of CS16 16-channel groups of a wider row (c16_0 = first group of the chunk,
+// cs16_tot = groups of the whole row; rows keep their true stride p.Cs): the source-channel loop of the wide layers (spconv_gmm_k).
+template <int CS16, int R, int JB_, int PR = 0, bool CHUNKED = false>
 struct GmmWave {
     static constexpr bool BF = PR == 1, X3 = PR == 2;
     static constexpr int NCH = R / 32;            // 16-pair chunks per item
@@ -104,6 +106,7 @@ struct GmmWave {
     int lr, lp16, lane16, lw, lw4, q16;           // per-lane constants
     int cg[1], cs_[1];                            // byte offsets of this lane's first entries in an item's index window (see load_idx)
     int wr_off, rd_off[JB];                       // float offsets into `stage` of this lane's write / fragment reads
+    int c16_0, cs16_tot;                          // CHUNKED only
 
     GmmItem it0, it1;                             // item being computed / item whose first unit is fetched next
     // Pair indices per lane, loaded straight into the lanes that use them (round 3; rounds 1-2 loaded one coalesced window and
@@ -171,11 +174,21 @@ struct GmmWave {
 #pragma unroll
         for (int c = 0; c < NCH; ++c) s_[c] = bload32(rs_s, vs + c * 64, soff_k);
     }
+    // byte offset of unit u's row piece inside a source row / of its first packed-weight block (BLK bytes per group of G16 16-channel groups)
+    __device__ __forceinline__ int src_off(int u) const {
+        if constexpr (CHUNKED) return c16_0 * 64 + u * (JB * 64);
+        else return u * (JB * 64);
+    }
+    template <int G16, int BLK>
+    __device__ __forceinline__ int w_off(int k, int u) const {
+        if constexpr (CHUNKED) return ((slice * K + k) * (cs16_tot / G16) + (c16_0 + u * JB) / G16) * BLK;
+        else return ((slice * K + k) * (CS16 / G16) + u * (JB / G16)) * BLK;
+    }
     __device__ __forceinline__ void issue(Buf& buf, const int (&g)[NI], int k, int u) const {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) buf.a[i] = bload128(rs_src, (int)__umul24(g[i], cs4) + lp16, u * (JB * 64));
+        for (int i = 0; i < NI; ++i) buf.a[i] = bload128(rs_src, (int)__umul24(g[i], cs4) + lp16, src_off(u));
         if constexpr (X3) {      // 32-channel groups: (jl, nb, plane) blocks of 1 KB (8 bf16 per lane)
-            const int wso = ((slice * K + k) * (CS16 / 2) + u * (JB / 2)) * 6144;
+            const int wso = w_off<2, 6144>(k, u);
 #pragma unroll
             for (int j = 0; j < JB / 2; ++j)
 #pragma unroll
@@ -183,7 +196,7 @@ struct GmmWave {
 #pragma unroll
                     for (int q = 0; q < 3; ++q) buf.b[j * 2 + nb][q] = bload128(rs_w, lane16 + (nb * 3 + q) * 1024, wso + j * 6144);
         } else if constexpr (BF) {      // 32-channel groups: (jl, nb) blocks of 1 KB (8 bf16 per lane)
-            const int wso = ((slice * K + k) * (CS16 / 2) + u * (JB / 2)) * 2048;
+            const int wso = w_off<2, 2048>(k, u);
 #pragma unroll
             for (int j = 0; j < JB / 2; ++j) {
                 buf.b[j][0] = bload128(rs_w, lane16, wso + j * 2048);
@@ -193,7 +206,7 @@ struct GmmWave {
 #pragma unroll
             for (int j = 0; j < JB; ++j) { asm volatile("" : "+v"(buf.b[j][0]), "+v"(buf.b[j][1])); }
         } else {
-            const int wso = ((slice * K + k) * CS16 + u * JB) * 2048;       // bytes: (j, nb) blocks of 1 KB
+            const int wso = w_off<1, 2048>(k, u);       // bytes: (j, nb) blocks of 1 KB
 #pragma unroll
             for (int j = 0; j < JB; ++j) {
                 buf.b[j][0] = bload128(rs_w, lane16, wso + j * 2048);
@@ -412,7 +425,10 @@ constexpr int gmm_jb(int cs16, int r) { return (cs16 % 4 == 0 && r == 32) ? 4 : 
 constexpr int gmm_acc_rows(int r) { return GMM_SWZ ? r : r + 1; }
 constexpr int gmm_wave_lds(int cs16, int r) { return gmm_acc_rows(r) * GMM_ALD + 16 * gmm_jb(cs16, r) * 16; }
 
-template <int CS16, int R, int PR = 0>
+// CHUNKED (wide layers: Cs / 16 outside the instantiated set, up to 512 channels): CS16 is the width of a CHUNK and the wave program runs
+// over a RUN-TIME number of chunks of the source row -- three chunk widths (32, 64, 128 channels) serve every multiple of 32 instead
+// of one fully unrolled body per width.
+template <int CS16, int R, int PR = 0, bool CHUNKED = false>
 __global__ __launch_bounds__(256) void spconv_gmm_k(GmmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -439,7 +455,7 @@ __global__ __launch_bounds__(256) void spconv_gmm_k(GmmParams p) {
     }
 
     static_assert(PR == 0 || CS16 % 2 == 0, "bf16 operands pair 16-channel groups");
-    GmmWave<CS16, R, gmm_jb(CS16, R), PR> w;
+    GmmWave<CS16, R, gmm_jb(CS16, R), PR, CHUNKED> w;
     w.init(p, acc, acc + gmm_acc_rows(R) * GMM_ALD, lane, slice, row0);
     const int k_lo = g * p.kper;
     w.k_hi = min(p.K, k_lo + p.kper);
@@ -449,7 +465,12 @@ __global__ __launch_bounds__(256) void spconv_gmm_k(GmmParams p) {
         w.ts_s = p.ts[lane * tsld + sub];
         w.ts_e = p.ts[lane * tsld + sub + 1];
     }
-    w.run(k_lo);
+    if constexpr (CHUNKED) {          // the accumulator tile stays in LDS between the chunks: every walk adds its source channels' products
+        w.cs16_tot = p.Cs >> 4;
+        for (int c = 0; c < w.cs16_tot; c += CS16) { w.c16_0 = c; w.run(k_lo); }
+    } else {
+        w.run(k_lo);
+    }
 
     float* out = p.out + (p.G > 1 ? (int64_t)g * p.n_dst * p.Cd : 0);
     // dst rows leave the LDS tile here; the batch norm that follows (every convolution of the U-Net feeds one) needs sum x and
@@ -530,6 +551,25 @@ static int launch_gmm(const GmmParams& p, hipStream_t s) {
     const int64_t waves = p.n_sub * p.n_slices * p.G;
     hipLaunchKernelGGL((spconv_gmm_k<CS16, R, PR>), dim3((unsigned)ceil_div(waves, 4)), dim3(256), lds, s, p);
     return check_launch("spconv_gmm");
+}
+
+// source-channel chunks of a wide layer: the widest of 128 / 64 / 32 channels that divides Cs
+static int gmm_chunk16(int cs16) { return cs16 % 8 == 0 ? 8 : (cs16 % 4 == 0 ? 4 : 2); }
+// the widths spconv_gmm_k is instantiated for (every layer of the 32-channel five-level U-Net); all other contract widths take the chunk loop
+static bool gmm_fixed_width(int cs16) { return cs16 == 1 || cs16 == 2 || cs16 == 4 || cs16 == 6 || cs16 == 8 || cs16 == 10 || cs16 == 12 || cs16 == 16; }
+
+template <int CH16, int PR>
+static int launch_gmm_chunk(const GmmParams& p, int R, hipStream_t s) {
+    const size_t lds = (size_t)4 * gmm_wave_lds(CH16, R) * sizeof(float);
+    const unsigned grid = (unsigned)ceil_div(p.n_sub * p.n_slices * p.G, 4);
+    if (R == 64) hipLaunchKernelGGL((spconv_gmm_k<CH16, 64, PR, true>), dim3(grid), dim3(256), lds, s, p);
+    else hipLaunchKernelGGL((spconv_gmm_k<CH16, 32, PR, true>), dim3(grid), dim3(256), lds, s, p);
+    return check_launch("spconv_gmm_chunk");
+}
+template <int PR>
+static int launch_gmm_wide(const GmmParams& p, int R, hipStream_t s) {
+    const int ch = gmm_chunk16(p.Cs / 16);
+    return ch == 8 ? launch_gmm_chunk<8, PR>(p, R, s) : (ch == 4 ? launch_gmm_chunk<4, PR>(p, R, s) : launch_gmm_chunk<2, PR>(p, R, s));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -995,10 +1035,11 @@ using namespace u3d;
 extern "C" {
 
 static int spconv_plan_impl(int Cs, int Cd, int K, int64_t n_dst, int* tile_rows, int* k_groups, bool rows_kernel) {
-    if (Cs % 16 || Cd % 32 || Cs <= 0 || Cd <= 0 || Cd > 256 || Cs > 256 || K <= 0 || K > 32 || n_dst <= 0 || !tile_rows || !k_groups)
+    // the contract: Cs in {16} u {32, 64, ..., 512}, Cd in {32, 64, ..., 512}
+    if (Cs % 16 || Cd % 32 || Cs <= 0 || Cd <= 0 || Cd > 512 || Cs > 512 || K <= 0 || K > 32 || n_dst <= 0 || !tile_rows || !k_groups)
         return U3D_EUNSUPPORTED;
     const int cs16 = Cs / 16;
-    if (!(cs16 == 1 || cs16 == 2 || cs16 == 4 || cs16 == 6 || cs16 == 8 || cs16 == 10 || cs16 == 12 || cs16 == 16)) return U3D_EUNSUPPORTED;
+    if (cs16 != 1 && cs16 % 2) return U3D_EUNSUPPORTED;
     plan_gmm(Cs, Cd, K, n_dst, tile_rows, k_groups, rows_kernel);
     return U3D_OK;
 }
@@ -1007,6 +1048,9 @@ int u3d_spconv_plan(int Cs, int Cd, int K, int64_t n_dst, int* tile_rows, int* k
 }
 int u3d_spconv_plan_bf16a(int Cs, int Cd, int K, int64_t n_dst, int* tile_rows, int* k_groups) {
     return spconv_plan_impl(Cs, Cd, K, n_dst, tile_rows, k_groups, true);
+}
+int u3d_spconv_gmm_bf16a_supported(int Cs, int Cd) {
+    return Cs > 0 && Cs % 32 == 0 && Cd > 0 && gmm_wg_supported(Cs / 16, 32, 3) && gmm_wg_supported(Cs / 16, 64, 3) ? 1 : 0;
 }
 
 static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows, const int32_t* gather, const int32_t* scatter,
@@ -1048,6 +1092,8 @@ static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows,
     const int ck = u3d_conv_kernel(-1);
     if (pr == 3 || (pr && (ck == 2 || (ck == 1 && pr == 2 && G == 1)) && !bn_partial && gmm_wg_supported(cs16, R, pr))) {
         rc = launch_gmm_wg(p, cs16, R, pr, s);
+    } else if (!gmm_fixed_width(cs16)) {
+        rc = pr == 1 ? launch_gmm_wide<1>(p, R, s) : (pr == 2 ? launch_gmm_wide<2>(p, R, s) : launch_gmm_wide<0>(p, R, s));
     } else if (pr == 1) {
         U3D_GMM_CASE_BF(2) U3D_GMM_CASE_BF(4) U3D_GMM_CASE_BF(6) U3D_GMM_CASE_BF(8) U3D_GMM_CASE_BF(10) U3D_GMM_CASE_BF(12) U3D_GMM_CASE_BF(16)
     } else if (pr == 2) {
@@ -1138,6 +1184,7 @@ static int spconv_wgrad_impl(const float* x, int64_t n_rows_x, const float* dy, 
         set_error("spconv_wgrad: %lld / %lld rows exceed the kernel's 32-bit addressing", (long long)n_rows_x, (long long)n_rows_dy);
         return U3D_EUNSUPPORTED;
     }
+    if (!wgrad_blk_supported(Cs, Cd)) { set_error("spconv_wgrad: no kernel for Cs=%d Cd=%d", Cs, Cd); return U3D_EUNSUPPORTED; }
     if (tile_rows != plan_wgrad_rows(K, n_rows_dy, Cs, Cd)) {
         set_error("spconv_wgrad: tile_rows %d does not match the plan", tile_rows);
         return U3D_EINVAL;
@@ -1161,8 +1208,12 @@ static int spconv_wgrad_impl(const float* x, int64_t n_rows_x, const float* dy, 
     U3D_WG_CASE(2, 4) U3D_WG_CASE(4, 6) U3D_WG_CASE(6, 8) U3D_WG_CASE(8, 10)
     U3D_WG_CASE(6, 4) U3D_WG_CASE(8, 6) U3D_WG_CASE(10, 8)
 #undef U3D_WG_CASE
-    set_error("spconv_wgrad: no instantiation for Cs=%d Cd=%d", Cs, Cd);
-    return U3D_EUNSUPPORTED;
+    // every other pair of the contract: the channel-blocked walk (spconv_wgrad_blk.hip), fp32 MFMAs for both fp32 flows -- the
+    // x3-from-160x160 rule above was measured on the whole-block walk and is not re-measured for these shapes
+    WgBlkParams b;
+    b.x = x; b.dy = dy; b.rows_x = rows_x; b.rows_dy = rows_dy; b.ts = tile_starts; b.partial = (float*)ws; b.K = K; b.cap = cap;
+    b.n_tiles = p.n_tiles; b.Cs = Cs; b.Cd = Cd; b.n_rows_x = n_rows_x; b.n_rows_dy = n_rows_dy;
+    return launch_wgrad_blk(b, bf, dW, s);
 }
 
 int u3d_spconv_wgrad(const float* x, int64_t n_rows_x, const float* dy, const int32_t* rows_x, const int32_t* rows_dy,

@@ -45,4 +45,22 @@ constexpr int GMM_ALD = 32;
 int launch_gmm_wg(const GmmParams& p, int cs16, int R, int pr, hipStream_t s);
 bool gmm_wg_supported(int cs16, int R, int pr);
 
+// channel-blocked weight gradient (spconv_wgrad_blk.hip): every (Cs, Cd) pair of the C ABI contract that spconv_wgrad_k (spconv.hip) has
+// no instantiation for.  Same pair lists, tile_starts and workspace size as that kernel; partial = [K][n_tiles][Cd][Cs] floats.
+struct WgBlkParams {
+    const float* x;
+    const float* dy;
+    const int32_t* rows_x;
+    const int32_t* rows_dy;
+    const int32_t* ts;        // tile_starts [K][n_tiles+1] over the dy-side rows
+    float* partial;
+    int K;
+    int64_t cap;
+    int n_tiles;
+    int Cs, Cd;
+    int64_t n_rows_x, n_rows_dy;
+};
+bool wgrad_blk_supported(int Cs, int Cd);       // Cs in {16} u {32, 64, ..., 512}, Cd in {32, 64, ..., 512}
+int launch_wgrad_blk(const WgBlkParams& p, bool bf16, float* dW, hipStream_t s);
+
 }  // namespace u3d

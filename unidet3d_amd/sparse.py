@@ -471,7 +471,9 @@ def _conv_route(Cs, Cd, n_dst, rb, bf, has_rows, want_stats):
             return 'ts', bf, ts
     if Cs % 32:
         bf = P.FMT_FP32
-    rows = has_rows and bf == P.FMT_BF16       # gather the bf16 shadow: same packed weights, u3d_spconv_gmm_bf16a and its own plan
+    # gather the bf16 shadow: same packed weights, u3d_spconv_gmm_bf16a and its own plan -- where that kernel has the width; elsewhere the
+    # fp32 rows are gathered and rounded as the operands are formed (same values, same results)
+    rows = has_rows and bf == P.FMT_BF16 and bool(L.lib().u3d_spconv_gmm_bf16a_supported(Cs, Cd))
     return 'pairs', bf, _plan(Cs, Cd, rb.K, n_dst, rows) + (rows,)
 
 

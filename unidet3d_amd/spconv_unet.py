@@ -20,6 +20,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from ._lib import U3DError
 from .registry import MODELS
 from .sparse import (SparseBatchNorm, SparseConv3d, SparseConvTensor, SparseInverseConv3d, SparseModule,
                      SparseSequential, SubMConv3d)
@@ -64,13 +65,29 @@ class ResidualBlock(SparseModule):
         return mods[5](x, addend=skip)          # conv + residual in one kernel
 
 
+POOL_WIDTHS = (32, 64, 128, 256)       # channel counts the superpoint pooling that reads the U-Net's output is built for (ops.superpoint_pool)
+
+
+def check_num_planes(num_planes):
+    """The channel contract of the sparse kernels, stated once for a whole U-Net: every plane a multiple of 32 up to 512, a plane above
+    the deepest level at most 256 (its tail block reads the 2c-channel concatenation), and the first plane a pooling width."""
+    planes = [int(c) for c in num_planes]
+    ok = bool(planes) and all(c > 0 and c % 32 == 0 and c <= 512 for c in planes) and all(2 * c <= 512 for c in planes[:-1])
+    if not ok or planes[0] not in POOL_WIDTHS:
+        raise U3DError(f'SpConvUNet: num_planes={planes} is outside what the gfx950 kernels are built for: every entry must be a multiple '
+                       f'of 32 (at most 512; at most 256 above the deepest level, whose tail blocks read 2c channels), and num_planes[0] '
+                       f'must be one of {list(POOL_WIDTHS)}, the widths of the superpoint pooling behind the backbone')
+
+
 @MODELS.register_module()
 class SpConvUNet(nn.Module):
     def __init__(self, num_planes, use_sync_bn=True, block_reps=2, block=ResidualBlock, indice_key_id=1,
-                 normalize_before=True, return_blocks=False):
+                 normalize_before=True, return_blocks=False, *, _inner=False):
         super().__init__()
         self.return_blocks = return_blocks
         self.num_planes = list(num_planes)
+        if not _inner:                     # the outermost U-Net checks the whole list (an inner level's first plane is not pooled)
+            check_num_planes(self.num_planes)
         # The reference's recursion passes its norm_fn partial in the ``use_sync_bn`` slot
         # (spconv_unet.py:166-168), which is truthy: every inner level is SyncBatchNorm even when
         # the top level asked for BatchNorm1d.  Reproduced: inner levels always sync.
@@ -94,7 +111,7 @@ class SpConvUNet(nn.Module):
             else:
                 self.conv = SparseSequential(down, norm_fn(c1), nn.ReLU())
             self.u = SpConvUNet(self.num_planes[1:], True, block_reps, block, indice_key_id=indice_key_id + 1,
-                                normalize_before=normalize_before, return_blocks=return_blocks)
+                                normalize_before=normalize_before, return_blocks=return_blocks, _inner=True)
             if normalize_before:
                 self.deconv = SparseSequential(norm_fn(c1), nn.ReLU(), up)
             else:
