@@ -36,7 +36,7 @@ typedef void* u3d_stream_t; /* hipStream_t */
 /* Bumped with every change of an entry point's argument list; unidet3d_amd/_lib.py refuses a library whose version differs from
  * the one it was written against (a stale .so would misread shifted arguments instead of failing).  Entry points that are only
  * ADDED (R15) leave it alone: no existing argument list moves, and _lib.py refuses a library that lacks a declared symbol. */
-#define U3D_ABI_VERSION 116
+#define U3D_ABI_VERSION 117
 int u3d_version(void);
 const char* u3d_last_error(void);
 /* How the fp32 matrix kernels (decoder GEMMs, attention, sparse convolutions without U3D_BF16_OPERANDS) multiply:
@@ -443,7 +443,7 @@ int u3d_dropout_bwd_b16(const void* dy, void* dx, int64_t n, int C, double p, ui
  *      weight-gradient C = A^T B with the row reduction split over workgroups (ws, fixed-order sum).
  * ===================================================================================== */
 int u3d_gemm_nt(const float* A /*[M,K]*/, const float* W /*[N,K]*/, const float* bias /*[N] or NULL*/, float* C /*[M,N]*/,
-                int64_t M, int N, int K /* % 16 == 0 */, double flops_hint, u3d_stream_t stream);
+                int64_t M, int N, int K /* % 16 == 0 */, const void* w_planes, double flops_hint, u3d_stream_t stream);
 /* OR-ed into `act` of u3d_linear_act / u3d_linear_dact / u3d_ffn_fwd: the MFMA operands are rounded to bf16 (round to nearest
  * even) on their way into LDS -- data stays fp32 in HBM, accumulation and epilogues stay fp32 (BASELINE configs[2]; the
  * reference trains with `--amp`, tools/train.py:86-99).  K must then be a multiple of 32. */
@@ -451,26 +451,26 @@ int u3d_gemm_nt(const float* A /*[M,K]*/, const float* W /*[N,K]*/, const float*
 /* Linear + activation in the GEMM epilogue (no separate elementwise kernel): Y = act(X W^T + bias), act: 0 none, 1 ReLU,
  * 2 GELU (erf form, unidet3d/encoder.py:58-59 `nn.GELU()`).  For GELU `pre` [M,N] receives X W^T + bias (kept for backward). */
 int u3d_linear_act(const float* X /*[M,K]*/, const float* W /*[N,K]*/, const float* bias, int act, float* pre, float* Y /*[M,N]*/,
-                   int64_t M, int N, int K, double flops_hint, u3d_stream_t stream);
+                   int64_t M, int N, int K, const void* w_planes, double flops_hint, u3d_stream_t stream);
 /* input gradient THROUGH the activation: dX = (dY Wt^T) * act'(aux), Wt [N,K] = the next layer's weight transposed;
  * aux [M,N] = the ReLU output (act 1) or the GELU pre-activation (act 2). */
 int u3d_linear_dact(const float* dY /*[M,K]*/, const float* Wt /*[N,K]*/, const float* aux, int act, float* dX /*[M,N]*/,
-                    int64_t M, int N, int K, double flops_hint, u3d_stream_t stream);
+                    int64_t M, int N, int K, const void* w_planes, double flops_hint, u3d_stream_t stream);
 /* C = A W^T + addend: a second gradient contribution folded into the GEMM that produces the first (flags: 0 or U3D_BF16_OPERANDS) */
 int u3d_gemm_nt_add(const float* A /*[M,K]*/, const float* W /*[N,K]*/, const float* addend /*[M,N]*/, int flags, float* C, int64_t M,
-                    int N, int K, double flops_hint, u3d_stream_t stream);
+                    int N, int K, const void* w_planes, double flops_hint, u3d_stream_t stream);
 /* SURVEY.md 8(b) `ln_linear`: NQ = LayerNorm(X (+ RES)) (u3d_layer_norm_fwd: SUM receives X + RES, STATS the row statistics), then
  * Y = act(NQ W^T + bias) (u3d_linear_act) -- the head of the decoder (unidet3d/encoder.py:187-196: out_norm -> out_bboxes / outs_cls).
  * Two launches: the decoder is post-norm and NQ has further consumers, so the normalised rows are written in any case. */
 int u3d_ln_linear(const float* X, const float* RES, const float* gamma, const float* beta, float eps, float* SUM, float* NQ, float* STATS,
                   const float* W /*[N,C]*/, const float* bias, int act, float* PRE, float* Y /*[M,N]*/, int64_t M, int C, int N,
-                  double flops_hint, u3d_stream_t stream);
+                  const void* w_planes, double flops_hint, u3d_stream_t stream);
 /* SURVEY.md 8(b) `ffn`: Z = act(X W1^T + b1) W2^T + b2 in two launches -- the FFN block (encoder.py:55-61, act 2), input_proj
  * (:138-140, act 1) and the class head (:153-155, act 1).  A [M,hid] receives the activation, H [M,hid] the GELU
  * pre-activation (NULL for ReLU); both are what the backward pass needs (u3d_linear_dact, u3d_gemm_tn). */
 int u3d_ffn_fwd(const float* X, const float* W1 /*[hid,d_in]*/, const float* b1, const float* W2 /*[d_out,hid]*/, const float* b2,
-                int act, float* H, float* A, float* Z /*[M,d_out]*/, int64_t M, int d_in, int hid, int d_out, double flops_hint,
-                u3d_stream_t stream);
+                int act, float* H, float* A, float* Z /*[M,d_out]*/, int64_t M, int d_in, int hid, int d_out,
+                const void* w1_planes, const void* w2_planes, double flops_hint, u3d_stream_t stream);
 /* stand-alone erf-GELU passes (the unfused alternative to act = 2 above; n % 4 == 0): a = gelu(h); dh = da * gelu'(h) */
 int u3d_gelu_fwd(const float* h, float* a, int64_t n, u3d_stream_t stream);
 int u3d_gelu_bwd(const float* da, const float* h, float* dh, int64_t n, u3d_stream_t stream);
@@ -489,13 +489,12 @@ int u3d_transpose_batch(const void* desc, int n_desc, int64_t total_blocks, u3d_
 /* Pre-split W operands for the three-plane ("bf16x3") NT products.  u3d_weight_planes_batch: desc int64 [n_desc][4] = {src ptr (fp32,
  * n8 * 8 values), dst ptr (bf16 [3][n8 * 8]: the three exact planes of every value, 8-element groups split exactly as the GEMM
  * kernels split them in flight), n8, first block}; a matrix takes ceil(n8 / 256) blocks; one launch for every weight (and transposed
- * copy) of a training step.  u3d_gemm_w_planes(w, p, w2, p2): the NEXT NT entry point called on this host thread (u3d_gemm_nt,
- * u3d_linear_act, u3d_linear_dact, u3d_gemm_nt_add, u3d_ln_linear; u3d_ffn_fwd takes p for W1 and p2 for W2) reads its W operand from
- * these planes ([3][N][K] bf16, same N, K as its fp32 W, which must still be passed) when it runs the three-plane kernel AND its W
- * argument is the pointer w (w2) the planes were registered for -- planes of another matrix are ignored; consumed (cleared) by
- * that call whatever kernel it picks; NULL = none.  Results are bit-identical with and without. */
+ * copy) of a training step.  The `w_planes` argument of the NT entry points above (u3d_gemm_nt, u3d_linear_act, u3d_linear_dact,
+ * u3d_gemm_nt_add, u3d_ln_linear; u3d_ffn_fwd takes one for W1 and one for W2) is such a matrix's planes ([3][N][K] bf16, same N, K
+ * as the fp32 W of that call, which must still be passed) or NULL: the call reads its W operand from them when it runs the
+ * three-plane kernel and ignores them otherwise (bf16 operands, the native fp32 math mode, K % 32 != 0).  Results are bit-identical
+ * with and without. */
 int u3d_weight_planes_batch(const void* desc, int n_desc, int64_t total_blocks, u3d_stream_t stream);
-int u3d_gemm_w_planes(const void* w, const void* planes, const void* w2, const void* planes2);
 
 /* ---- K14b: the same Linear layers with bf16 ACTIVATIONS in HBM (csrc/gemm_b16.hip; BASELINE configs[2] -- the reference's `--amp`
  * autocasts the Linear / MultiheadAttention activations, tools/train.py:86-99 around unidet3d/encoder.py:19-21,55-61,138-163).

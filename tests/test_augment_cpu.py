@@ -125,7 +125,7 @@ def test_abi_version_and_symbols():
     import re, os
     from unidet3d_amd import _lib
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'u3d.h')).read()
-    assert int(re.search(r'#define\s+U3D_ABI_VERSION\s+(\d+)', hdr).group(1)) == _lib.ABI_VERSION == 116
+    assert int(re.search(r'#define\s+U3D_ABI_VERSION\s+(\d+)', hdr).group(1)) == _lib.ABI_VERSION == 117
     l = _lib.lib()
     for name in ('u3d_aug_points', 'u3d_aug_extent_f32', 'u3d_aug_extent_f64', 'u3d_aug_noise_blur', 'u3d_aug_elastic', 'u3d_relabel_ids',
                  'u3d_aug_remap_ids', 'u3d_aug_sp_masks'):

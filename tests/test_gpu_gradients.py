@@ -304,9 +304,11 @@ def test_side_stream_weight_gradients_with_shared_weights_and_hooks():
 def test_presplit_weight_planes_and_batched_transposes_change_no_bit():
     """dense.transposed_weights(): every Linear weight's [K, N] copy (one u3d_transpose_batch launch) and, for the three-plane fp32
     products, the three bf16 planes of every weight and transposed copy (one u3d_weight_planes_batch launch; the NT kernels then load
-    their W operand pre-split, u3d_gemm_w_planes) -- against the same step with neither (per-launch transposes, in-kernel splits):
-    loss and every gradient identical to the bit, in both fp32 math modes."""
+    their W operand pre-split, the `w_planes` argument) -- against the same step with neither (per-launch transposes, in-kernel splits):
+    loss and every gradient identical to the bit, in both fp32 math modes.  Not vacuous: with the planes on, plane pointers do reach
+    the NT entry points (both weights of u3d_ffn_fwd among them); with them off, none does."""
     import unidet3d_amd  # noqa: F401
+    from unidet3d_amd import _lib as L
     from unidet3d_amd import dense
     from unidet3d_amd import precision as P
     from unidet3d_amd.config import build_model
@@ -316,9 +318,21 @@ def test_presplit_weight_planes_and_batched_transposes_change_no_bit():
     cfg['decoder']['num_layers'] = 2
     inputs, samples0 = make_batch_inputs([make_scene(90, n_points=9000), make_scene(91, n_points=7000)], DEV)
 
+    n_planes_args = {'u3d_gemm_nt': 1, 'u3d_linear_act': 1, 'u3d_linear_dact': 1, 'u3d_gemm_nt_add': 1, 'u3d_ln_linear': 1, 'u3d_ffn_fwd': 2}
+    handed = {}                                         # entry point -> most plane pointers one call of it was handed
+    real_call = L.call
+
+    def spy(name, *args):
+        n = n_planes_args.get(name)
+        if n:                                           # w_planes: last before flops_hint and stream
+            handed[name] = max(handed.get(name, 0), sum(a is not None for a in args[-2 - n:-2]))
+        return real_call(name, *args)
+
     def run(planes, batch):
         was = dense._W_PLANES
         dense._W_PLANES = planes
+        handed.clear()
+        L.call = spy
         model = fill_state_dict(build_model(cfg), tag0=3000, scale=0.06).to(DEV).train()
         ctx_cls = dense.transposed_weights
         if not batch:                                   # no context: every backward transposes for itself, no planes
@@ -332,8 +346,14 @@ def test_presplit_weight_planes_and_batched_transposes_change_no_bit():
             loss.backward()
             torch.cuda.synchronize()
         finally:
+            L.call = real_call
             dense.transposed_weights = ctx_cls
             dense._W_PLANES = was
+        assert handed, 'no NT entry point was called'
+        if planes and math == 'bf16x3':                 # the three-plane math mode is the one that makes planes
+            assert handed.get('u3d_ffn_fwd') == 2 and sum(handed.values()) > 2, handed
+        elif not planes:
+            assert not any(handed.values()), handed
         return loss.detach().clone(), {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
 
     for math in ('bf16x3', 'mfma'):

@@ -304,3 +304,21 @@ def test_an_object_is_stale_after_any_header_changes(tmp_path, monkeypatch):
         os.utime(paths[n], (old, old))
     assert not B._stale(str(paths['a.hip']), str(paths['a.o']))
     assert B._stale(str(paths['a.hip']), str(here / 'missing.o'))
+
+
+def test_weight_planes_are_an_argument_of_the_nt_entry_points():
+    """The pre-split W planes reach an NT launch as its own `w_planes` argument (placed last before flops_hint; u3d_ffn_fwd takes
+    two): no hand-over entry point is left in the header or in the ctypes table, and both agree on the six argument lists."""
+    import re
+    from unidet3d_amd import _lib
+    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'u3d.h')).read(), flags=re.S)
+    assert 'u3d_gemm_w_planes' not in _lib.PROTOTYPES and 'u3d_gemm_w_planes' not in hdr
+    for name, n_planes in (('u3d_gemm_nt', 1), ('u3d_linear_act', 1), ('u3d_linear_dact', 1), ('u3d_gemm_nt_add', 1), ('u3d_ln_linear', 1),
+                           ('u3d_ffn_fwd', 2)):
+        params = [p.strip() for p in re.search(r'\b' + name + r'\s*\((.*?)\)\s*;', hdr, flags=re.S).group(1).split(',')]
+        args = _lib.PROTOTYPES[name][1]
+        assert len(params) == len(args), name
+        tail = params[-2 - n_planes:]
+        assert all(re.fullmatch(r'const void\* w\d?_planes', p) for p in tail[:n_planes]), (name, tail)
+        assert tail[n_planes:] == ['double flops_hint', 'u3d_stream_t stream'], (name, tail)
+        assert args[-2 - n_planes:] == [_lib.C.c_void_p] * n_planes + [_lib.C.c_double, _lib.C.c_void_p], name

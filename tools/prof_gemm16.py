@@ -1,5 +1,8 @@
-"""Per-shape timing of the decoder GEMMs under bf16 operands: fp32 tensors rounded in flight (gemm.hip, the round-5 data flow) against
-bf16 tensors in HBM (gemm_b16.hip, include/u3d.h K14b).   python tools/prof_gemm16.py [M ...]      env U3D_NT16_TILE=1|2|3"""
+"""Per-shape timing of the decoder GEMMs under bf16 operands: the fp32-tensor entry points (U3D_BF16_OPERANDS / u3d_gemm_tn_bf16:
+gemm_b16.hip's gemm_nt_b16_k on the cost model's tile, gemm.hip's gemm_tn_bf16_k under the 384-workgroup split plan) against the
+bf16-activation entry points (include/u3d.h K14b: gemm_b16.hip's kernels on the largest tile that fills the CUs / under the
+256-512-workgroup plan).  Products of a few microseconds are launch-bound here: tools/prof_nt_bf16.py times the kernels themselves.
+python tools/prof_gemm16.py [M ...]      env U3D_NT16_TILE=1|2|3"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,8 +40,8 @@ for M in [int(a) for a in sys.argv[1:]] or [24600]:
         w16 = w.bfloat16(); t_torch = bench(lambda: torch.nn.functional.linear(a16, w16))
         t_tn_old = bench(lambda: L.call('u3d_gemm_tn_bf16', L.ptr(dy), L.ptr(a), L.ptr(dw), L.ptr(db), M, N, K, L.ptr(ws), 0.0, L.stream()))
         t_tn = [bench(lambda: D16.gemm_tn(p, q, True)) for p, q in ((dy, a), (dy16, a), (dy, a16), (dy16, a16))]
-        print(f'M={M:6d} N={N:5d} K={K:5d} ({fl / 1e9:5.1f} GF) us | nt: fp32-tensor kernel {us(t_old)} | b16 kernel A/C = f/f {us(t_ff)} h/f {us(t_hf)} f/h {us(t_fh)} '
-              f'h/h {us(t_hh)} ({fl / t_hh / 1e12:5.0f} TF/s) torch bf16 {us(t_torch)} | tn: old {us(t_tn_old)} | b16 f/f {us(t_tn[0])} h/f {us(t_tn[1])} f/h {us(t_tn[2])} h/h {us(t_tn[3])} '
+        print(f'M={M:6d} N={N:5d} K={K:5d} ({fl / 1e9:5.1f} GF) us | nt: fp32 tensors, cost-model tile {us(t_old)} | b16 kernel, fill-the-CUs tile, A/C = f/f {us(t_ff)} h/f {us(t_hf)} f/h {us(t_fh)} '
+              f'h/h {us(t_hh)} ({fl / t_hh / 1e12:5.0f} TF/s) torch bf16 {us(t_torch)} | tn: fp32 tensors, 384-wg plan {us(t_tn_old)} | b16 kernel, 256/512-wg plan, f/f {us(t_tn[0])} h/f {us(t_tn[1])} f/h {us(t_tn[2])} h/h {us(t_tn[3])} '
               f'({fl / t_tn[3] / 1e12:5.0f} TF/s)', flush=True)
     n = M * 1024
     h = torch.randn(M, 1024, device=dev); hb = h.bfloat16(); o = torch.empty_like(h); ob = torch.empty_like(hb)

@@ -12,7 +12,7 @@ wgs = -(-M // tile[0]) * -(-N // tile[1])
 a = torch.randn(M, K, device=dev); w = torch.randn(N, K, device=dev); b = torch.randn(N, device=dev); y = torch.empty(M, N, device=dev)
 tr = torch.zeros(wgs * 12, dtype=torch.int64, device=dev)
 for _ in range(3):
-    L.call('u3d_linear_act', L.ptr(a), L.ptr(w), L.ptr(b), 0, L.ptr(tr), L.ptr(y), M, N, K, 0.0, L.stream())
+    L.call('u3d_linear_act', L.ptr(a), L.ptr(w), L.ptr(b), 0, L.ptr(tr), L.ptr(y), M, N, K, None, 0.0, L.stream())
 torch.cuda.synchronize()
 t = tr.cpu().numpy().reshape(wgs, 12)
 t0 = t[:, 0].min()

@@ -107,12 +107,12 @@ PROTOTYPES = {
     'u3d_box_decode7_bwd': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     'u3d_criterion_ws_bytes': (_i64, [_i32, _i32, _i64, _i64, _i64]),
     'u3d_criterion_ws_bytes_gt': (_i64, [_i32, _i32, _i64, _i64, _i64, _i32]),
-    'u3d_gemm_nt': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _vp]),
-    'u3d_linear_act': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _f64, _vp]),
-    'u3d_linear_dact': (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _f64, _vp]),
-    'u3d_gemm_nt_add': (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _f64, _vp]),
-    'u3d_ln_linear': (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _f64, _vp]),
-    'u3d_ffn_fwd': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f64, _vp]),
+    'u3d_gemm_nt': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _f64, _vp]),
+    'u3d_linear_act': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _f64, _vp]),
+    'u3d_linear_dact': (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _f64, _vp]),
+    'u3d_gemm_nt_add': (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _f64, _vp]),
+    'u3d_ln_linear': (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _f64, _vp]),
+    'u3d_ffn_fwd': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _f64, _vp]),
     'u3d_gelu_fwd': (_i32, [_vp, _vp, _i64, _vp]),
     'u3d_gelu_bwd': (_i32, [_vp, _vp, _vp, _i64, _vp]),
     'u3d_gemm_nt_b16': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _f64, _vp]),
@@ -126,7 +126,6 @@ PROTOTYPES = {
     'u3d_transpose': (_i32, [_vp, _vp, _i32, _i32, _vp]),
     'u3d_transpose_batch': (_i32, [_vp, _i32, _i64, _vp]),
     'u3d_weight_planes_batch': (_i32, [_vp, _i32, _i64, _vp]),
-    'u3d_gemm_w_planes': (_i32, [_vp, _vp, _vp, _vp]),
     'u3d_attn_varlen_fwd': (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
     'u3d_attn_varlen_bwd': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
     'u3d_attn_varlen_fwd_bf16': (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _vp]),
@@ -175,7 +174,7 @@ PROTOTYPES = {
     'u3d_eval_sweep_ws_bytes': (_i64, [_i64, _i64, _i32]),
 }
 
-ABI_VERSION = 116         # include/u3d.h U3D_ABI_VERSION this table was written against
+ABI_VERSION = 117         # include/u3d.h U3D_ABI_VERSION this table was written against
 
 K_CONV_FWD, K_CONV_WGRAD, K_BN, K_POOL, K_ATTN_FWD, K_ATTN_BWD, K_RULEBOOK, K_VOXELIZE, K_GEMM = range(9)
 

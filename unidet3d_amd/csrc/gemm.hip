@@ -11,14 +11,19 @@
 //                                                                split over workgroups, partials summed in a fixed order)
 // K-dim permutation as in the sparse conv kernels: lane (i, h) of the 32x32x2 MFMA feeds step s with
 // k = 8h + s, so its 8 A (or B) values of a 16-deep K-step are two contiguous float4 in LDS.
-#include "u3d_common.h"
+// Kernels here: gemm_nt_k / gemm_tn_k (native fp32 MFMAs), gemm_nt_x3_k / gemm_tn_x3_k (three bf16 planes, the default fp32 math),
+// gemm_tn_bf16_k (fp32 tensors, bf16 operands: the weight gradients of the fallback flow -- bf16 operands without bf16 activations,
+// reduction depths that are no multiple of 32; its NT products run gemm_b16.hip's gemm_nt_b16_k on this file's tile choice, through
+// launch_nt_b16_f32: same bits, tests/test_gpu_gemm_one_kernel.py), the fixed-order split reduce that gemm_b16.hip launches too (launch_tn_reduce), GELU
+// passes, transposes, the W-plane split.  gemm_common.h holds what this file shares with gemm_b16.hip: tile constants, nt_epilogue,
+// cvt8, the host-side tile table / split clamp / offset guards / grids.  A pre-split W operand arrives as the `w_planes` argument of
+// the NT entry points.
+#include "gemm_common.h"
 
 namespace u3d {
 
 #define U3D_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
-constexpr int GT = 128;        // macro tile (both dims)
-constexpr int GK = 16;         // K-step
 constexpr int GLD = GK + 4;    // padded LDS row of the NT tiles
 
 // TN = 128 or 64 output columns per workgroup: the decoder's GEMMs are tall and skinny (M ~ 16k, N = 256..1024), and
@@ -38,44 +43,8 @@ constexpr int GLD = GK + 4;    // padded LDS row of the NT tiles
 //   5  C = acc + aux                                    a second gradient contribution added in place of a separate add kernel
 // The erf GELU (gelu_f, gelu_grad_f) is u3d_common.h's.
 
-// Shared epilogue of the NT kernels.  D layout of 32x32 MFMAs (dtype independent): col = lane & 31,
-// row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
-template <int TN, int EPI, int TM = GT>
-__device__ __forceinline__ void nt_epilogue(const f32x16 (&acc)[TM / 64][TN / 64], float* __restrict__ C, const float* __restrict__ bias,
-                                            const float* __restrict__ aux, float* __restrict__ pre, int64_t m0, int n0, int rows_a, int N,
-                                            int wr, int wc, int i32, int kh) {
-    constexpr int NB = TN / 64, TA = TM / 64;
-    const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(C + m0 * N, (int64_t)rows_a * N * 4);
-    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc((EPI == 2 ? (const float*)pre : aux) + (EPI >= 2 ? m0 * N : 0), (int64_t)rows_a * N * 4);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int n = n0 + wc * (TN / 2) + b * 32 + i32;
-        const float bv = (bias && n < N) ? bias[n] : 0.f;
-        const int vc = n < N ? (4 * kh * N + n) * 4 : 0x7fffffff;        // columns past N: dropped by the bounds check
-#pragma unroll
-        for (int a = 0; a < TA; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wr * (TM / 2) + a * 32 + (r & 3) + 8 * (r >> 2);
-                float v = acc[a][b][r] + bv;
-                if constexpr (EPI == 1) v = fmaxf(v, 0.f);
-                if constexpr (EPI == 2) {
-                    float h = v;
-                    asm volatile("" : "+v"(h));
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h), rs_x, vc, row * N * 4, 0);
-                    v = gelu_f(v);
-                }
-                if constexpr (EPI == 3 || EPI == 4 || EPI == 5) {       // rows / columns outside the tile read as 0 through the descriptor
-                    const float x = __builtin_bit_cast(float, bload32(rs_x, vc, row * N * 4));
-                    v = EPI == 3 ? (x > 0.f ? v : 0.f) : (EPI == 4 ? v * gelu_grad_f(x) : v + x);
-                }
-                asm volatile("" : "+v"(v));          // see gemm_tn_k: keeps the store builtin from mis-selecting the vector element
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_c, vc, row * N * 4, 0);
-            }
-    }
-}
-
 // TM x TN macro tile (TM = 128 or 64 rows: wave (wr, wc) owns TM/2 x TN/2), K-step GK
+// (frame, accumulator zeroing below repeat other kernels' text on purpose: shared helpers change the instruction stream, gemm_common.h)
 template <int TN, int EPI, int TM = GT>
 __global__ __launch_bounds__(256) void gemm_nt_k(const float* __restrict__ A, const float* __restrict__ W, const float* __restrict__ bias,
                                                  float* __restrict__ C, int64_t M, int N, int K, const float* __restrict__ aux,
@@ -153,90 +122,6 @@ __global__ __launch_bounds__(256) void gemm_nt_k(const float* __restrict__ A, co
     nt_epilogue<TN, EPI, TM>(acc, C, bias, aux, pre, m0, n0, rows_a, N, wr, wc, i32, kh);
 }
 
-// bf16-operand form of gemm_nt_k (BASELINE configs[2]; the reference's `--amp` Linear layers): A and W are fp32 in HBM, rounded
-// to bf16 (RNE) while they are staged into LDS, multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulation; same tiling,
-// descriptors and epilogues.  A K-step is 32 deep (two MFMAs per tile pair); lane (i, h) holds k = 8h .. 8h+7 of each 16-deep
-// half, one 16-byte LDS read.  80-byte LDS rows keep the 16-byte reads of 32 consecutive rows conflict-free.
-constexpr int GKH = 32;        // K-step of the bf16 kernel
-constexpr int GLH = GKH + 8;   // padded LDS row (halves)
-
-template <int TN, int EPI, int TM = GT>
-__global__ __launch_bounds__(256) void gemm_nt_bf16_k(const float* __restrict__ A, const float* __restrict__ W, const float* __restrict__ bias,
-                                                      float* __restrict__ C, int64_t M, int N, int K, const float* __restrict__ aux,
-                                                      float* __restrict__ pre) {
-    constexpr int NB = TN / 64, TA = TM / 64;
-    __shared__ __attribute__((aligned(16))) __bf16 As[2][TM * GLH];
-    __shared__ __attribute__((aligned(16))) __bf16 Bs[2][TN * GLH];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1, i32 = lane & 31, kh = lane >> 5;
-    // 1-D grid, XCD-aware: workgroup b runs on XCD b % 8 (own 4 MB L2); XCD x takes a contiguous chunk of tile ids with the
-    // column tiles of one row tile next to each other, so the A row tile (GT x K, read by every column tile: PMC showed 196 MB
-    // fetched per launch for 76 MB of operands with the 2-D grid) comes from HBM once and from that XCD's L2 afterwards
-    const int nt_ = (N + TN - 1) / TN;
-    const int64_t wid_ = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int64_t m0 = (wid_ / nt_) * TM;
-    const int n0 = (int)(wid_ % nt_) * TN;
-    const int rows_a = (int)min((int64_t)TM, M - m0), rows_b = min(TN, N - n0);
-    const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(A + m0 * K, (int64_t)rows_a * K * 4);
-    const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(W + (int64_t)n0 * K, (int64_t)rows_b * K * 4);
-    // staging map: thread -> (row = tid>>2 (+64), 8 floats at column 8 * (tid&3))
-    const int srow = tid >> 2, sc8 = tid & 3;
-    const int vo = (srow * K + sc8 * 8) * 4, vstep = 64 * K * 4;
-    f32x4 ra[TA][2], rb[NB][2];
-    auto gload = [&](int kt) {
-#pragma unroll
-        for (int j = 0; j < TA; ++j) {
-            ra[j][0] = bload128(rs_a, vo + j * vstep, kt * (GKH * 4));
-            ra[j][1] = bload128(rs_a, vo + j * vstep + 16, kt * (GKH * 4));
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            rb[j][0] = bload128(rs_b, vo + j * vstep, kt * (GKH * 4));
-            rb[j][1] = bload128(rs_b, vo + j * vstep + 16, kt * (GKH * 4));
-        }
-    };
-    auto cvt8 = [](const f32x4& lo, const f32x4& hi) {
-        return bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < TA; ++j) *reinterpret_cast<bf16x8*>(&As[buf][(srow + 64 * j) * GLH + sc8 * 8]) = cvt8(ra[j][0], ra[j][1]);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) *reinterpret_cast<bf16x8*>(&Bs[buf][(srow + 64 * j) * GLH + sc8 * 8]) = cvt8(rb[j][0], rb[j][1]);
-    };
-    f32x16 acc[TA][NB];
-#pragma unroll
-    for (int a = 0; a < TA; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    const int nk = K / GKH;
-    gload(0);
-    lstore(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) gload(kt + 1);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            bf16x8 af[TA], bf[NB];
-#pragma unroll
-            for (int t = 0; t < TA; ++t) af[t] = *reinterpret_cast<const bf16x8*>(&As[buf][(wr * (TM / 2) + t * 32 + i32) * GLH + h * 16 + kh * 8]);
-#pragma unroll
-            for (int t = 0; t < NB; ++t) bf[t] = *reinterpret_cast<const bf16x8*>(&Bs[buf][(wc * (TN / 2) + t * 32 + i32) * GLH + h * 16 + kh * 8]);
-#pragma unroll
-            for (int a = 0; a < TA; ++a)
-#pragma unroll
-                for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a], bf[b], acc[a][b], 0, 0, 0);
-        }
-        if (kt + 1 < nk) lstore(buf ^ 1);
-        __syncthreads();
-    }
-    nt_epilogue<TN, EPI, TM>(acc, C, bias, aux, pre, m0, n0, rows_a, N, wr, wc, i32, kh);
-}
-
 // gemm_nt_k with the fp32 products on the bf16 pipe (u3d_common.h, "bf16x3"): the staged fp32 rows are split into three exact
 // bf16 planes, a tile pair takes the six MFMAs h.h, h.m, m.h, h.l, m.m, l.h (smallest terms first) -- 6 x 32 cycles for a
 // 32 x 32 x 16 block instead of the 8 x 64 cycles of v_mfma_f32_32x32x2_f32.  With the matrix time cut to 3/8 the kernel must
@@ -254,6 +139,7 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_k(const float* __restrict__ 
 // (planes_batch_k below: the same split3_x8 on the same 8-element groups, so the staged planes and the results are bit-identical) --
 // and the thread that stages a W row piece loads three 16-byte plane pieces instead of 32 bytes of fp32 and runs no split for it: a
 // third of the kernel's split arithmetic (13 VALU per pair of values, issued in the matrix pipe's time) at TM = 128, TN = 64.
+// (frame, accumulator zeroing below repeat other kernels' text on purpose: shared helpers change the instruction stream, gemm_common.h)
 template <int TN, int EPI, int TM = GT, bool WP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM == 128 ? 3 : 1))) void gemm_nt_x3_k(const float* __restrict__ A, const float* __restrict__ W, const float* __restrict__ bias,
                                                     float* __restrict__ C, int64_t M, int N, int K, const float* __restrict__ aux,
@@ -430,6 +316,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM == 128 ?
 // the weight gradients of this decoder are small (256 x 256, 768 x 256, 256 x 32, 19 x 256 ...) -- with 128 x 128 tiles a
 // 256 x 256 output has 4 tiles and needs ~96 row splits to fill 256 CUs, i.e. 25 MB of partials written and read back for 0.26 MB
 // of result; 64 x 64 tiles quarter the splits and the partial traffic at the price of twice the LDS reads per MFMA.
+// (frame, accumulator zeroing, partial store below repeat other kernels' text on purpose: shared helpers change the instruction stream, gemm_common.h)
 template <int T>
 __global__ __launch_bounds__(256) void gemm_tn_k(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ partial,
                                                  int colsum, int64_t M, int N, int K, int64_t rows_per_split, int S) {
@@ -548,6 +435,7 @@ __global__ __launch_bounds__(256) void gemm_tn_k(const float* __restrict__ A, co
 //     its C operand's exponent, u3d_common.h) without leaving two waves per SIMD.
 // One LDS stage, two barriers per 32-row trip (the raw rows of trip t+1 wait in registers during the products of trip t).
 constexpr int TXK = 32;
+// (frame, accumulator zeroing and column-sum tail below repeat other kernels' text on purpose: shared helpers change the instruction stream, gemm_common.h)
 template <int TA, int TB>          // output rows (columns of A) x output columns (columns of B) per workgroup
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TA == 128 ? 3 : 1))) void gemm_tn_x3_k(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ partial,
                                                     int colsum, int64_t M, int N, int K, int64_t rows_per_split, int S) {
@@ -682,9 +570,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TA == 128 ?
 // receives column t; rounds 2-3 used eight 2-byte reads and four packing instructions).  320-byte rows put the four rows a
 // half-wave reads on four different 64-byte bank groups -- conflict free.  The column sums of A (bias gradient) are accumulated
 // from the fp32 values before they are rounded.
-constexpr int TKH = 32;              // rows per stage
-constexpr int TLH = GT + 32;         // padded LDS row (halves)
 
+// (frame, accumulator zeroing, partial store and column-sum tail below repeat other kernels' text on purpose: shared helpers change the instruction stream, gemm_common.h)
 __global__ __launch_bounds__(256) void gemm_tn_bf16_k(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ partial,
                                                       int colsum, int64_t M, int N, int K, int64_t rows_per_split) {
     __shared__ __attribute__((aligned(16))) __bf16 As[2][TKH * TLH];
@@ -814,6 +701,13 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_k(const float* __restrict_
     }
 }
 
+void launch_tn_reduce(const float* ws, int S, int N, int K, float* C, float* colsum, hipStream_t s) {
+    const int64_t n4_main = (int64_t)N * K / 4, n4 = n4_main + (colsum ? N / 4 : 0);
+    int64_t grid = ceil_div(n4, 256);
+    grid = grid > 1024 ? 1024 : grid;
+    hipLaunchKernelGGL(gemm_tn_reduce_k, dim3((unsigned)grid), dim3(256), 0, s, ws, S, n4, n4_main, C, colsum);
+}
+
 // stand-alone GELU (erf) passes over [n] floats -- the unfused alternative to epilogues 2 / 4 (HBM-bound, full occupancy)
 __global__ __launch_bounds__(256) void gelu_fwd_k(const float4* __restrict__ h, float4* __restrict__ a, int64_t n4) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -891,10 +785,7 @@ static int tn_splits(int64_t M, int N, int K, int T, bool bf) {
     // workgroups aimed at: ~3 per CU for the fp32 kernels (measured best of 384 / 768 / 1536), 1.5 for the bf16 one (its
     // workgroups are 16x shorter); every extra split costs N*K*4 bytes written and read again by the reduce
     static const int target = [] { const char* e = getenv("U3D_TN_WGS"); return e && atoi(e) > 0 ? atoi(e) : 768; }();
-    int64_t s = ceil_div(bf ? 384 : target, tiles);
-    const int64_t max_s = ceil_div(M, 4 * GK);
-    if (s > max_s) s = max_s;
-    return (int)(s < 1 ? 1 : (s > 256 ? 256 : s));
+    return tn_clamp_splits(ceil_div(bf ? 384 : target, tiles), M, GK);
 }
 
 // Tile choice by a small cost model.  All workgroups of these launches are resident at once (<= 5 per CU by LDS), so a launch
@@ -905,15 +796,14 @@ static int tn_splits(int64_t M, int N, int K, int T, bool bf) {
 // GEMMs 6.71 ms with 128x64 everywhere, 6.37 ms with 64x64 everywhere -> the overhead of the small tile is small: 4 % / 8 %.
 template <int EPI>
 static void launch_nt(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, const float* aux, float* pre,
-                      bool bf16_operands, bool x3, hipStream_t s, const void* wplanes = nullptr) {
+                      bool bf16_operands, bool x3, hipStream_t s, const void* wplanes) {
     static const int force = [] { const char* e = getenv("U3D_NT_TILE"); return e ? atoi(e) : 0; }();       // 1 / 2 / 3 = 128x128 / 128x64 / 64x64
-    const int tm[3] = {128, 128, 64}, tn[3] = {128, 64, 64};
     const double over[3] = {1.0, 1.04, 1.08};
     int best = 0;
     double best_t = 0.0;
     for (int c = x3 ? 1 : 0; c < 3; ++c) {         // bf16x3: 128 x 64 at most -- the low-order tile doubles the accumulator registers
-        const int64_t wgs = ceil_div(M, tm[c]) * ceil_div(N, tn[c]);
-        const double t = (double)ceil_div(wgs, 256) * tm[c] * tn[c] * over[c];
+        const int64_t wgs = ceil_div(M, NT_TM[c]) * ceil_div(N, NT_TN[c]);
+        const double t = (double)ceil_div(wgs, 256) * NT_TM[c] * NT_TN[c] * over[c];
         if (c == (x3 ? 1 : 0) || t < best_t) { best = c; best_t = t; }
     }
     // Round 4: under amdgpu_waves_per_eu(3) the three-plane 128 x 64 kernel takes 162 registers instead of 200 (no spills) and three
@@ -922,45 +812,30 @@ static void launch_nt(const float* A, const float* W, const float* bias, float* 
     if (x3 && M >= 4096) best = 1;
     if (force >= 1 && force <= 3) best = force - 1;
     if (x3 && best == 0) best = 1;
-    const dim3 grid((unsigned)(ceil_div(M, tm[best]) * ceil_div(N, tn[best])));       // (row tile, column tile) decoded in the kernel
-#define U3D_NT_LAUNCH(KERNEL)                                                                                                          \
-    if (best == 0) hipLaunchKernelGGL((KERNEL<128, EPI, 128>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre);                \
-    else if (best == 1) hipLaunchKernelGGL((KERNEL<64, EPI, 128>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre);            \
-    else hipLaunchKernelGGL((KERNEL<64, EPI, 64>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre);
-    if (bf16_operands) { U3D_NT_LAUNCH(gemm_nt_bf16_k) }
+    const dim3 grid = nt_grid(M, N, best);       // (row tile, column tile) decoded in the kernel
+    if (bf16_operands) launch_nt_b16_f32(EPI, best, A, W, bias, C, M, N, K, aux, pre, s);       // gemm_b16.hip's kernel on this tile
     else if (x3 && wplanes) {
         if (best == 1) hipLaunchKernelGGL((gemm_nt_x3_k<64, EPI, 128, true>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre, wplanes);
         else hipLaunchKernelGGL((gemm_nt_x3_k<64, EPI, 64, true>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre, wplanes);
     } else if (x3) {
         if (best == 1) hipLaunchKernelGGL((gemm_nt_x3_k<64, EPI, 128, false>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre, (const void*)nullptr);
         else hipLaunchKernelGGL((gemm_nt_x3_k<64, EPI, 64, false>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre, (const void*)nullptr);
-    } else { U3D_NT_LAUNCH(gemm_nt_k) }
-#undef U3D_NT_LAUNCH
+    } else if (best == 0) hipLaunchKernelGGL((gemm_nt_k<128, EPI, 128>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre);
+    else if (best == 1) hipLaunchKernelGGL((gemm_nt_k<64, EPI, 128>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre);
+    else hipLaunchKernelGGL((gemm_nt_k<64, EPI, 64>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux, pre);
 }
 
-// epi: 0..4 (see nt_epilogue); + 8: bf16 MFMA operands (fp32 data in HBM, fp32 accumulation)
-// The pre-split planes of the NEXT launch's W operand (u3d_gemm_w_planes): per host thread, consumed (and cleared) by the next NT
-// entry point called on that thread -- the caller sets them immediately before the call they belong to.
-// Each slot remembers the fp32 matrix the planes were made from: an entry point only uses planes whose owner is the W it was handed
-// (an exception between the hand-over and the launch must not leave planes behind for an unrelated product).
-static thread_local const void* g_wplanes[2] = {nullptr, nullptr};
-static thread_local const void* g_wowner[2] = {nullptr, nullptr};
-static const void* take_wplanes(int i, const void* W) {
-    const void* p = g_wowner[i] == W ? g_wplanes[i] : nullptr;
-    g_wplanes[i] = nullptr;
-    g_wowner[i] = nullptr;
-    return p;
-}
-
+// epi: 0..5 (see nt_epilogue); + 8: bf16 MFMA operands (fp32 data in HBM, fp32 accumulation).  wplanes: the pre-split planes of W
+// ([3][N][K] bf16, u3d_weight_planes_batch) or NULL; only the three-plane kernel reads them.
 static int gemm_nt_epi(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, int epi, const float* aux,
-                       float* pre, double flops_hint, hipStream_t s, const void* wplanes = nullptr) {
+                       float* pre, const void* wplanes, double flops_hint, hipStream_t s) {
     const bool bf = (epi & 8) != 0;
     epi &= 7;
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || epi < 0 || epi > 5 || (epi == 2 && !pre) || (epi >= 3 && !aux)) return U3D_EINVAL;
     const bool x3 = !bf && fp32_x3() && K % GKH == 0;        // K = 16 (mod 32) keeps the native fp32 kernel
     if (K % (bf ? GKH : GK)) { set_error("gemm_nt: K=%d must be a multiple of %d", K, bf ? GKH : GK); return U3D_EUNSUPPORTED; }
     ProfScope prof(U3D_K_GEMM, s, flops_hint);
-    if ((int64_t)GT * K * 4 >= 0x7fffffffLL || (int64_t)GT * N * 4 >= 0x7fffffffLL) { set_error("gemm_nt: N=%d / K=%d too large for 32-bit tile offsets", N, K); return U3D_EUNSUPPORTED; }
+    if (!nt_offsets_ok("gemm_nt", N, K)) return U3D_EUNSUPPORTED;
     switch (epi) {
         case 0: launch_nt<0>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
         case 1: launch_nt<1>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
@@ -979,66 +854,52 @@ using namespace u3d;
 extern "C" {
 
 
-int u3d_gemm_nt(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, double flops_hint,
+int u3d_gemm_nt(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, const void* w_planes, double flops_hint,
                 u3d_stream_t stream) {
-    const void* wp = take_wplanes(0, W);
-    take_wplanes(1, nullptr);
-    return gemm_nt_epi(A, W, bias, C, M, N, K, 0, nullptr, nullptr, flops_hint, (hipStream_t)stream, wp);
+    return gemm_nt_epi(A, W, bias, C, M, N, K, 0, nullptr, nullptr, w_planes, flops_hint, (hipStream_t)stream);
 }
 
 // `act` of the three entry points below: 0 none, 1 ReLU, 2 GELU; + U3D_BF16_OPERANDS (16) selects the bf16-operand kernels
 int u3d_linear_act(const float* X, const float* W, const float* bias, int act, float* pre, float* Y, int64_t M, int N, int K,
-                   double flops_hint, u3d_stream_t stream) {
+                   const void* w_planes, double flops_hint, u3d_stream_t stream) {
     const int bf = (act & U3D_BF16_OPERANDS) ? 8 : 0;
     act &= ~U3D_BF16_OPERANDS;
-    const void* wp = take_wplanes(0, W);
-    take_wplanes(1, nullptr);
     if (act < 0 || act > 2) return U3D_EINVAL;
-    return gemm_nt_epi(X, W, bias, Y, M, N, K, act | bf, nullptr, pre, flops_hint, (hipStream_t)stream, wp);
+    return gemm_nt_epi(X, W, bias, Y, M, N, K, act | bf, nullptr, pre, w_planes, flops_hint, (hipStream_t)stream);
 }
 
-int u3d_linear_dact(const float* dY, const float* Wt, const float* aux, int act, float* dX, int64_t M, int N, int K, double flops_hint,
-                    u3d_stream_t stream) {
+int u3d_linear_dact(const float* dY, const float* Wt, const float* aux, int act, float* dX, int64_t M, int N, int K, const void* w_planes,
+                    double flops_hint, u3d_stream_t stream) {
     const int bf = (act & U3D_BF16_OPERANDS) ? 8 : 0;
     act &= ~U3D_BF16_OPERANDS;
-    const void* wp = take_wplanes(0, Wt);
-    take_wplanes(1, nullptr);
     if (act < 0 || act > 2) return U3D_EINVAL;
-    return gemm_nt_epi(dY, Wt, nullptr, dX, M, N, K, (act == 0 ? 0 : act + 2) | bf, aux, nullptr, flops_hint, (hipStream_t)stream, wp);
+    return gemm_nt_epi(dY, Wt, nullptr, dX, M, N, K, (act == 0 ? 0 : act + 2) | bf, aux, nullptr, w_planes, flops_hint, (hipStream_t)stream);
 }
 
-int u3d_gemm_nt_add(const float* A, const float* W, const float* addend, int flags, float* C, int64_t M, int N, int K, double flops_hint,
-                    u3d_stream_t stream) {
-    const void* wp = take_wplanes(0, W);
-    take_wplanes(1, nullptr);
-    return gemm_nt_epi(A, W, nullptr, C, M, N, K, 5 | ((flags & U3D_BF16_OPERANDS) ? 8 : 0), addend, nullptr, flops_hint, (hipStream_t)stream, wp);
+int u3d_gemm_nt_add(const float* A, const float* W, const float* addend, int flags, float* C, int64_t M, int N, int K, const void* w_planes,
+                    double flops_hint, u3d_stream_t stream) {
+    return gemm_nt_epi(A, W, nullptr, C, M, N, K, 5 | ((flags & U3D_BF16_OPERANDS) ? 8 : 0), addend, nullptr, w_planes, flops_hint, (hipStream_t)stream);
 }
 
 int u3d_ln_linear(const float* X, const float* RES, const float* gamma, const float* beta, float eps, float* SUM, float* NQ, float* STATS,
-                  const float* W, const float* bias, int act, float* PRE, float* Y, int64_t M, int C, int N, double flops_hint,
-                  u3d_stream_t stream) {
-    const void* wp = take_wplanes(0, W);
-    take_wplanes(1, nullptr);
+                  const float* W, const float* bias, int act, float* PRE, float* Y, int64_t M, int C, int N, const void* w_planes,
+                  double flops_hint, u3d_stream_t stream) {
     if (!NQ || !Y || !W) return U3D_EINVAL;
     int rc = u3d_layer_norm_fwd(X, RES, gamma, beta, M, C, eps, SUM, NQ, STATS, stream);
     if (rc || M == 0) return rc;
-    g_wplanes[0] = wp;
-    g_wowner[0] = wp ? W : nullptr;
-    return u3d_linear_act(NQ, W, bias, act, PRE, Y, M, N, C, flops_hint, stream);
+    return u3d_linear_act(NQ, W, bias, act, PRE, Y, M, N, C, w_planes, flops_hint, stream);
 }
 
 int u3d_ffn_fwd(const float* X, const float* W1, const float* b1, const float* W2, const float* b2, int act, float* H, float* A, float* Z,
-                int64_t M, int d_in, int hid, int d_out, double flops_hint, u3d_stream_t stream) {
-    const void* wp1 = take_wplanes(0, W1);
-    const void* wp2 = take_wplanes(1, W2);
+                int64_t M, int d_in, int hid, int d_out, const void* w1_planes, const void* w2_planes, double flops_hint, u3d_stream_t stream) {
     const int bf = (act & U3D_BF16_OPERANDS) ? 8 : 0;
     act &= ~U3D_BF16_OPERANDS;
     if (act != 1 && act != 2) return U3D_EINVAL;
     if (!A || !Z) return U3D_EINVAL;
     const double f1 = flops_hint > 0 ? 2.0 * M * d_in * hid : 0.0, f2 = flops_hint > 0 ? 2.0 * M * hid * d_out : 0.0;
-    int rc = gemm_nt_epi(X, W1, b1, A, M, hid, d_in, act | bf, nullptr, H, f1, (hipStream_t)stream, wp1);
+    int rc = gemm_nt_epi(X, W1, b1, A, M, hid, d_in, act | bf, nullptr, H, w1_planes, f1, (hipStream_t)stream);
     if (rc) return rc;
-    return gemm_nt_epi(A, W2, b2, Z, M, d_out, hid, bf, nullptr, nullptr, f2, (hipStream_t)stream, wp2);
+    return gemm_nt_epi(A, W2, b2, Z, M, d_out, hid, bf, nullptr, nullptr, w2_planes, f2, (hipStream_t)stream);
 }
 
 // three-plane form (gemm_tn_x3_k): 128 x 64 tiles where gemm_tn_k takes 128 x 128 ones, 64 x 64 otherwise
@@ -1046,10 +907,7 @@ static bool tn_x3_on() { static const int on = [] { const char* e = getenv("U3D_
 static int tn_x3_ta(int N, int K) { return tn_tile(N, K) == GT ? 128 : 64; }
 static int tn_x3_splits(int64_t M, int N, int K) {
     const int64_t tiles = ceil_div(N, tn_x3_ta(N, K)) * ceil_div(K, 64);
-    int64_t s = ceil_div(768, tiles);
-    const int64_t max_s = ceil_div(M, 4 * TXK);
-    if (s > max_s) s = max_s;
-    return (int)(s < 1 ? 1 : (s > 256 ? 256 : s));
+    return tn_clamp_splits(ceil_div(768, tiles), M, TXK);
 }
 
 int64_t u3d_gemm_tn_ws_bytes(int64_t M, int N, int K) {
@@ -1075,25 +933,19 @@ static int gemm_tn_impl(const float* A, const float* B, float* C, float* colsum_
     const int T = bf ? GT : tn_tile(N, K);
     const int S = x3 ? tn_x3_splits(M, N, K) : tn_splits(M, N, K, T, bf);
     const int64_t rps = x3 ? ceil_div(ceil_div(M, S), TXK) * TXK : ceil_div(ceil_div(M, S), GK) * GK;
-    if ((int64_t)(rps + 2 * TXK) * N * 4 >= 0x7fffffffLL || (int64_t)(rps + 2 * TXK) * K * 4 >= 0x7fffffffLL || (int64_t)N * K * 4 >= 0x7fffffffLL) {
-        set_error("gemm_tn: M=%lld N=%d K=%d too large for 32-bit split offsets", (long long)M, N, K);
-        return U3D_EUNSUPPORTED;
-    }
+    if (!tn_offsets_ok("gemm_tn", M, N, K, rps)) return U3D_EUNSUPPORTED;
     if (x3) {
         const int ta = tn_x3_ta(N, K);
-        const unsigned grid = (unsigned)(ceil_div(S, 8) * 8 * ceil_div(N, ta) * ceil_div(K, 64));
+        const unsigned grid = tn_grid(S, N, K, ta, 64);
         if (ta == 128) hipLaunchKernelGGL((gemm_tn_x3_k<128, 64>), dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
         else hipLaunchKernelGGL((gemm_tn_x3_k<64, 64>), dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
     } else if (bf) hipLaunchKernelGGL(gemm_tn_bf16_k, dim3((unsigned)ceil_div(N, GT), (unsigned)ceil_div(K, GT), S), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps);
     else {
-        const unsigned grid = (unsigned)(ceil_div(S, 8) * 8 * ceil_div(N, T) * ceil_div(K, T));       // whole groups of 8 splits
+        const unsigned grid = tn_grid(S, N, K, T, T);
         if (T == 64) hipLaunchKernelGGL(gemm_tn_k<64>, dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
         else hipLaunchKernelGGL(gemm_tn_k<GT>, dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
     }
-    const int64_t n4_main = (int64_t)N * K / 4, n4 = n4_main + (colsum_A ? N / 4 : 0);
-    int64_t grid = ceil_div(n4, 256);
-    grid = grid > 1024 ? 1024 : grid;
-    hipLaunchKernelGGL(gemm_tn_reduce_k, dim3((unsigned)grid), dim3(256), 0, s, (const float*)ws, S, n4, n4_main, C, colsum_A);
+    launch_tn_reduce((const float*)ws, S, N, K, C, colsum_A, s);
     return check_launch("gemm_tn");
 }
 
@@ -1131,12 +983,6 @@ int u3d_weight_planes_batch(const void* desc, int n_desc, int64_t total_blocks, 
     if (!desc || n_desc <= 0 || total_blocks <= 0 || total_blocks >= 0x7fffffffLL) return U3D_EINVAL;
     hipLaunchKernelGGL(planes_batch_k, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const PlDesc*)desc, n_desc);
     return check_launch("weight_planes_batch");
-}
-
-int u3d_gemm_w_planes(const void* w, const void* planes, const void* w2, const void* planes2) {
-    g_wplanes[0] = planes; g_wowner[0] = planes ? w : nullptr;
-    g_wplanes[1] = planes2; g_wowner[1] = planes2 ? w2 : nullptr;
-    return U3D_OK;
 }
 
 int u3d_transpose_batch(const void* desc, int n_desc, int64_t total_blocks, u3d_stream_t stream) {

@@ -1,10 +1,12 @@
 // K14b: the decoder's Linear layers with bf16 ACTIVATIONS in HBM (BASELINE configs[2]; the reference's `--amp` run autocasts the
 // Linear / MultiheadAttention activations to 16 bits, tools/train.py:86-99 around unidet3d/encoder.py:19-21,55-61,138-163).
-// gemm.hip's bf16-operand kernels read fp32 tensors and round them on the way into LDS: every activation crosses HBM at 4 bytes an
+// gemm.hip's U3D_BF16_OPERANDS routes read fp32 tensors and round them on the way into LDS: every activation crosses HBM at 4 bytes an
 // element although only 8 mantissa bits enter the product (cfg3, round 5: 14.3 GB of GEMM traffic per step).  Here the streamed
 // operands and the results may BE bf16 tensors:
 //   gemm_nt_b16_k   C[M,N] = A[M,K] . W[N,K]^T (+ bias, ReLU, ReLU mask, addend): A bf16 or fp32, C (and the mask) bf16 or fp32,
 //                   W stays fp32 (a weight is <= 1 MB, re-read from L2, rounded while it is staged);
+//                   with fp32 A and C it is also the kernel of gemm.hip's U3D_BF16_OPERANDS route (launch_nt_b16_f32: gemm.hip's tile
+//                   choice, GELU epilogues 2 / 4 included);
 //   gemm_tn_b16_k   partial[N,K] = A[M,N]^T . B[M,K] (weight gradients): either operand bf16 or fp32, fp32 partials + the fixed-order
 //                   reduce of gemm.hip;
 //   gelu_*_b16_k    erf GELU between two bf16 tensors (the FFN's hidden activation never exists in fp32).
@@ -14,18 +16,19 @@
 // Values: a bf16 tensor written by one kernel and read by the next holds exactly the value gemm.hip's kernels would have formed by
 // rounding the fp32 tensor in flight (round to nearest even both ways), so the products are unchanged; what changes is that
 // ELEMENTWISE consumers (GELU and its derivative) see the rounded pre-activation and hand on a rounded gradient.
-#include "u3d_common.h"
+#include "gemm_common.h"
 
 namespace u3d {
 
-constexpr int HT = 128;        // macro tile
-constexpr int HK = 32;         // K-step
-constexpr int HL = HK + 8;     // padded LDS row of the NT tiles (halves): 80-byte rows, conflict-free 16-byte reads of 32 rows
+constexpr int HT = GT, HK = GKH, HL = GLH;        // macro tile, K-step and padded LDS row of the NT tiles (gemm_common.h)
 
 #ifndef U3D_NT16_ABL
 #define U3D_NT16_ABL 0          // timing ablations (wrong results): 1 no result stores, 2 no MFMAs, 4 no global loads in the loop, 8 no LDS stores in the loop
 #endif
 // EPI: 0 C = acc + bias | 1 C = relu(acc + bias) | 3 C = aux > 0 ? acc : 0 (aux = the ReLU output, C's dtype) | 5 C = acc + aux (fp32 both)
+// fp32 A and C only (the U3D_BF16_OPERANDS route of gemm.hip): 2 aux = acc + bias, C = gelu(aux) (aux is WRITTEN: the pre-activation)
+// | 4 C = acc * gelu'(aux)
+// (frame, accumulator zeroing and the fp32 epilogue of EPI 0 / 1 / 3 / 5 below repeat other kernels' text on purpose: shared helpers change the instruction stream, gemm_common.h)
 template <int TN, int EPI, int TM, bool A16, bool C16>
 __global__ __launch_bounds__(256) void gemm_nt_b16_k(const void* __restrict__ A_, const float* __restrict__ W, const float* __restrict__ bias,
                                                      void* __restrict__ C_, int64_t M, int N, int K, const void* __restrict__ aux_) {
@@ -60,9 +63,6 @@ __global__ __launch_bounds__(256) void gemm_nt_b16_k(const void* __restrict__ A_
             rb[j][0] = bload128(rs_b, vob + j * vsb, kt * (HK * 4));
             rb[j][1] = bload128(rs_b, vob + j * vsb + 16, kt * (HK * 4));
         }
-    };
-    auto cvt8 = [](const f32x4& lo, const f32x4& hi) {
-        return bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
     };
     // Loads run TWO k-steps ahead of their use (a workgroup's life is mostly load latency: tools/prof_gemm16.py ablations -- without the
     // loop's loads 25 instead of 37 us at N, K = 256, 1024, without MFMAs 36): the rows of step kt+1, loaded during step kt-1, move from
@@ -137,6 +137,12 @@ __global__ __launch_bounds__(256) void gemm_nt_b16_k(const void* __restrict__ A_
     compute(kt & 1);                                                   // step nk-1
     // ---- epilogue.  D layout of the 32 x 32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     if constexpr (U3D_NT16_ABL & 1) { if (acc[0][0][0] != 12345.678f) return; }
+    if constexpr (EPI == 2 || EPI == 4) {
+        static_assert(!A16 && !C16, "the GELU epilogues are fp32 in, fp32 out");
+        float* pre = const_cast<float*>(reinterpret_cast<const float*>(aux_));       // EPI 2 writes it, EPI 4 reads it: never both
+        nt_epilogue<TN, EPI, TM>(acc, reinterpret_cast<float*>(C_), bias, EPI == 2 ? nullptr : pre, EPI == 2 ? pre : nullptr, m0, n0, rows_a, N, wr, wc, i32, kh);
+        return;
+    }
     char* Cb = reinterpret_cast<char*>(C_) + m0 * N * EC;
     const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(Cb, (int64_t)rows_a * N * EC);
     const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(reinterpret_cast<const char*>(aux_) + (EPI >= 3 ? m0 * N * EC : 0), (int64_t)rows_a * N * EC);
@@ -192,9 +198,9 @@ __global__ __launch_bounds__(256) void gemm_nt_b16_k(const void* __restrict__ A_
 // The reduction index is the ROW of both operands: a lane's 8 k values are a column of the staged [32 rows][128 cols] tile, two
 // ds_read_b64_tr_b16 per fragment (gemm.hip gemm_tn_bf16_k).  A bf16 operand is staged by 16-byte copies: thread -> (row = tid >> 4
 // (+ 16), 8 columns at 8 (tid & 15)); an fp32 one as in gemm.hip: (row = tid >> 5 (+ 8 j), 4 columns at 4 (tid & 31)), rounded here.
-constexpr int WKH = 32;
-constexpr int WLH = HT + 32;         // padded LDS row (halves): the four rows a half-wave reads lie on four 64-byte bank groups
+constexpr int WKH = TKH, WLH = TLH;        // rows per stage and padded LDS row (gemm_common.h)
 
+// (frame, accumulator zeroing, partial store and column-sum tail below repeat other kernels' text on purpose: shared helpers change the instruction stream, gemm_common.h)
 template <bool A16, bool B16>
 __global__ __launch_bounds__(256) void gemm_tn_b16_k(const void* __restrict__ A_, const void* __restrict__ B_, float* __restrict__ partial,
                                                      int colsum, int64_t M, int N, int K, int64_t rows_per_split, int S) {
@@ -362,31 +368,6 @@ __global__ __launch_bounds__(256) void gemm_tn_b16_k(const void* __restrict__ A_
     }
 }
 
-// sums the splits in a fixed order (gemm.hip gemm_tn_reduce_k: same order, same four independent partial sums)
-__global__ __launch_bounds__(256) void gemm_tn_reduce16_k(const float* __restrict__ partial, int S, int64_t n4, int64_t n4_main, float* __restrict__ C,
-                                                          float* __restrict__ C2) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        int s = 0;
-        for (; s + 4 <= S; s += 4) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float4 t = reinterpret_cast<const float4*>(partial)[(int64_t)(s + u) * n4 + i];
-                v[u].x += t.x; v[u].y += t.y; v[u].z += t.z; v[u].w += t.w;
-            }
-        }
-        for (; s < S; ++s) {
-            const float4 t = reinterpret_cast<const float4*>(partial)[(int64_t)s * n4 + i];
-            v[0].x += t.x; v[0].y += t.y; v[0].z += t.z; v[0].w += t.w;
-        }
-        float4* dst = i < n4_main ? reinterpret_cast<float4*>(C) + i : reinterpret_cast<float4*>(C2) + (i - n4_main);
-        *dst = make_float4((v[0].x + v[1].x) + (v[2].x + v[3].x), (v[0].y + v[1].y) + (v[2].y + v[3].y),
-                           (v[0].z + v[1].z) + (v[2].z + v[3].z), (v[0].w + v[1].w) + (v[2].w + v[3].w));
-    }
-}
-
 // ---- erf GELU between bf16 tensors (8 values per thread): a = gelu(h); dh = da * gelu'(h); fp32 arithmetic, one rounding on the way out
 __global__ __launch_bounds__(256) void gelu_fwd_b16_k(const u32x4* __restrict__ h, u32x4* __restrict__ a, int64_t n8) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
@@ -421,22 +402,38 @@ __global__ __launch_bounds__(256) void gelu_bwd_b16_k(const u32x4* __restrict__ 
 }
 
 template <int EPI, bool A16, bool C16>
+static void launch_nt16_tile(int tile, const void* A, const float* W, const float* bias, void* C, int64_t M, int N, int K, const void* aux, hipStream_t s) {
+    const dim3 grid = nt_grid(M, N, tile);
+    if (tile == 0) hipLaunchKernelGGL((gemm_nt_b16_k<128, EPI, 128, A16, C16>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux);
+    else if (tile == 1) hipLaunchKernelGGL((gemm_nt_b16_k<64, EPI, 128, A16, C16>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux);
+    else hipLaunchKernelGGL((gemm_nt_b16_k<64, EPI, 64, A16, C16>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux);
+}
+
+template <int EPI, bool A16, bool C16>
 static void launch_nt16(const void* A, const float* W, const float* bias, void* C, int64_t M, int N, int K, const void* aux, hipStream_t s) {
     // tile choice: the largest tile that still gives every CU a workgroup.  gemm.hip's rounds-of-256-workgroups model does not
     // describe this kernel (three to four workgroups share a CU and most of a workgroup's life is load latency): measured at
     // M = 24 600 (tools/prof_gemm16.py, us, 128 x 128 | 128 x 64 | 64 x 64): N, K = 256, 256: 10.9 | 11.6 | 12.8; 768, 256: 24.6 | 28.6 |
     // 35.0; 1024, 256: 29.2 | 35.9 | 40.3; 256, 1024: 25.3 | 29.5 | 35.9
     static const int force = [] { const char* e = getenv("U3D_NT16_TILE"); return e ? atoi(e) : 0; }();      // 1 / 2 / 3 = 128x128 / 128x64 / 64x64
-    const int tm[3] = {128, 128, 64}, tn[3] = {128, 64, 64};
     int best = 2;
     for (int c = 0; c < 3; ++c)
-        if (ceil_div(M, tm[c]) * ceil_div(N, tn[c]) >= 256) { best = c; break; }
+        if (ceil_div(M, NT_TM[c]) * ceil_div(N, NT_TN[c]) >= 256) { best = c; break; }
     if (N <= 64 && best == 0) best = 1;               // narrow results (class / box heads): no empty half tile
     if (force >= 1 && force <= 3) best = force - 1;
-    const dim3 grid((unsigned)(ceil_div(M, tm[best]) * ceil_div(N, tn[best])));
-    if (best == 0) hipLaunchKernelGGL((gemm_nt_b16_k<128, EPI, 128, A16, C16>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux);
-    else if (best == 1) hipLaunchKernelGGL((gemm_nt_b16_k<64, EPI, 128, A16, C16>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux);
-    else hipLaunchKernelGGL((gemm_nt_b16_k<64, EPI, 64, A16, C16>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux);
+    launch_nt16_tile<EPI, A16, C16>(best, A, W, bias, C, M, N, K, aux, s);
+}
+
+void launch_nt_b16_f32(int epi, int tile, const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, const float* aux,
+                       float* pre, hipStream_t s) {
+    switch (epi) {
+        case 0: launch_nt16_tile<0, false, false>(tile, A, W, bias, C, M, N, K, aux, s); break;
+        case 1: launch_nt16_tile<1, false, false>(tile, A, W, bias, C, M, N, K, aux, s); break;
+        case 2: launch_nt16_tile<2, false, false>(tile, A, W, bias, C, M, N, K, pre, s); break;      // the kernel's one `aux` slot carries `pre`
+        case 3: launch_nt16_tile<3, false, false>(tile, A, W, bias, C, M, N, K, aux, s); break;
+        case 4: launch_nt16_tile<4, false, false>(tile, A, W, bias, C, M, N, K, aux, s); break;
+        default: launch_nt16_tile<5, false, false>(tile, A, W, bias, C, M, N, K, aux, s); break;
+    }
 }
 
 template <int EPI>
@@ -460,10 +457,7 @@ static int tn16_splits(int64_t M, int N, int K) {
     const int64_t tiles = ceil_div(N, HT) * ceil_div(K, HT);
     static const int forced = [] { const char* e = getenv("U3D_TN16_WGS"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
     const int target = forced ? forced : (tiles >= 16 ? 512 : 256);
-    int64_t s = ceil_div(target, tiles);
-    const int64_t max_s = ceil_div(M, 4 * WKH);
-    if (s > max_s) s = max_s;
-    return (int)(s < 1 ? 1 : (s > 256 ? 256 : s));
+    return tn_clamp_splits(ceil_div(target, tiles), M, WKH);
 }
 
 }  // namespace u3d
@@ -478,7 +472,7 @@ int u3d_gemm_nt_b16(const void* A, const float* W, const float* bias, int epi, c
     if (flags & ~(U3D_A_BF16 | U3D_C_BF16)) return U3D_EINVAL;
     if (K % HK) { set_error("gemm_nt_b16: K=%d must be a multiple of %d", K, HK); return U3D_EUNSUPPORTED; }
     if ((flags & U3D_C_BF16) && (N % 2 || epi == 5)) { set_error("gemm_nt_b16: a bf16 result needs an even N (%d) and epi != 5", N); return U3D_EUNSUPPORTED; }
-    if ((int64_t)HT * K * 4 >= 0x7fffffffLL || (int64_t)HT * N * 4 >= 0x7fffffffLL) { set_error("gemm_nt_b16: N=%d / K=%d too large for 32-bit tile offsets", N, K); return U3D_EUNSUPPORTED; }
+    if (!nt_offsets_ok("gemm_nt_b16", N, K)) return U3D_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_GEMM, s, flops_hint);
     switch (epi) {
@@ -501,20 +495,14 @@ int u3d_gemm_tn_b16(const void* A, const void* B, float* C, float* colsum_A, int
     ProfScope prof(U3D_K_GEMM, s, flops_hint);
     const int S = tn16_splits(M, N, K);
     const int64_t rps = ceil_div(ceil_div(M, S), WKH) * WKH;
-    if ((int64_t)(rps + 2 * WKH) * N * 4 >= 0x7fffffffLL || (int64_t)(rps + 2 * WKH) * K * 4 >= 0x7fffffffLL || (int64_t)N * K * 4 >= 0x7fffffffLL) {
-        set_error("gemm_tn_b16: M=%lld N=%d K=%d too large for 32-bit split offsets", (long long)M, N, K);
-        return U3D_EUNSUPPORTED;
-    }
-    const dim3 grid((unsigned)(ceil_div(S, 8) * 8 * ceil_div(N, HT) * ceil_div(K, HT)));          // whole groups of 8 splits
+    if (!tn_offsets_ok("gemm_tn_b16", M, N, K, rps)) return U3D_EUNSUPPORTED;
+    const dim3 grid(tn_grid(S, N, K, HT, HT));
     const int cs = colsum_A ? 1 : 0;
     if (a16 && b16) hipLaunchKernelGGL((gemm_tn_b16_k<true, true>), grid, dim3(256), 0, s, A, B, (float*)ws, cs, M, N, K, rps, S);
     else if (a16) hipLaunchKernelGGL((gemm_tn_b16_k<true, false>), grid, dim3(256), 0, s, A, B, (float*)ws, cs, M, N, K, rps, S);
     else if (b16) hipLaunchKernelGGL((gemm_tn_b16_k<false, true>), grid, dim3(256), 0, s, A, B, (float*)ws, cs, M, N, K, rps, S);
     else hipLaunchKernelGGL((gemm_tn_b16_k<false, false>), grid, dim3(256), 0, s, A, B, (float*)ws, cs, M, N, K, rps, S);
-    const int64_t n4_main = (int64_t)N * K / 4, n4 = n4_main + (colsum_A ? N / 4 : 0);
-    int64_t g = ceil_div(n4, 256);
-    g = g > 1024 ? 1024 : g;
-    hipLaunchKernelGGL(gemm_tn_reduce16_k, dim3((unsigned)g), dim3(256), 0, s, (const float*)ws, S, n4, n4_main, C, colsum_A);
+    launch_tn_reduce((const float*)ws, S, N, K, C, colsum_A, s);
     return check_launch("gemm_tn_b16");
 }
 

@@ -115,7 +115,7 @@ class transposed_weights:
         return False
 
 
-# Pre-split W operands of the three-plane NT products (u3d_weight_planes_batch + u3d_gemm_w_planes): built, bit-identical, and OFF by
+# Pre-split W operands of the three-plane NT products (u3d_weight_planes_batch, `w_planes` of the NT calls): built, bit-identical, and OFF by
 # default -- measured on MI355X (round 5, same box, two runs each): all GEMMs 5.40 / 5.34 ms with the planes, 5.41 / 5.41 without, step
 # 293.5 / 292.5 vs 294.8 / 295.7 scenes/s.  The W split is a third of the NT kernel's split arithmetic (loop VALU 156 -> 110
 # instructions, tools/isa_mix.py) and removing it buys nothing: the kernel is not bound by its VALU issue.  U3D_W_PLANES=1 turns it on.
@@ -132,13 +132,6 @@ def _planes_of(mat):
     if _WT_ACTIVE.get('_versions', {}).get(mat.data_ptr(), mat._version) != mat._version:
         return None
     return _WT_ACTIVE.get('_planes', {}).get(mat.data_ptr())
-
-
-def _use_planes(w1, p1, w2=None, p2=None):
-    """hand the next NT launch its pre-split W operand(s) together with the matrices they belong to (include/u3d.h
-    u3d_gemm_w_planes: the launch ignores planes of any other matrix); no call when there are none"""
-    if p1 is not None or p2 is not None:
-        L.lib().u3d_gemm_w_planes(L.ptr(w1) if p1 is not None else None, L.ptr(p1), L.ptr(w2) if p2 is not None else None, L.ptr(p2))
 
 
 def _wt_of(weight):
@@ -207,19 +200,17 @@ class _Flow32:
         if epi == EPI_BIAS:
             if self.bf:
                 a, w = _pad_cols(a, 32), _pad_cols(w, 32)
-                L.call('u3d_linear_act', L.ptr(a), L.ptr(w), L.ptr(bias), P.BF16_FLAG, None, L.ptr(c), M, N, a.shape[1],
+                L.call('u3d_linear_act', L.ptr(a), L.ptr(w), L.ptr(bias), P.BF16_FLAG, None, L.ptr(c), M, N, a.shape[1], None,
                        _book(M, N, a.shape[1]), L.stream())
             else:
-                _use_planes(w, planes)
-                L.call('u3d_gemm_nt', L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(c), M, N, K, _book(M, N, K), L.stream())
+                L.call('u3d_gemm_nt', L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(c), M, N, K, L.ptr(planes), _book(M, N, K), L.stream())
         elif epi == EPI_ADD:
-            L.call('u3d_gemm_nt_add', L.ptr(a), L.ptr(w), L.ptr(aux), self.flag, L.ptr(c), M, N, K, _book(M, N, K, extra_mn=1), L.stream())
+            L.call('u3d_gemm_nt_add', L.ptr(a), L.ptr(w), L.ptr(aux), self.flag, L.ptr(c), M, N, K, None, _book(M, N, K, extra_mn=1),
+                   L.stream())
         else:                                            # the input gradient THROUGH the activation (u3d_linear_dact)
             act = {EPI_RELU_MASK: ACT_RELU, EPI_GELU_MASK: ACT_GELU}[epi]
-            if not self.bf:
-                _use_planes(w, planes)
-            L.call('u3d_linear_dact', L.ptr(a), L.ptr(w), L.ptr(aux), act | self.flag, L.ptr(c), M, N, K, _book(M, N, K, extra_mn=1),
-                   L.stream())
+            L.call('u3d_linear_dact', L.ptr(a), L.ptr(w), L.ptr(aux), act | self.flag, L.ptr(c), M, N, K, L.ptr(planes),
+                   _book(M, N, K, extra_mn=1), L.stream())
         return c
 
     def tn(self, dy, x, want_bias):
@@ -249,10 +240,8 @@ class _Flow32:
         if M:
             _book(M, hid, d_in, extra_mn=1 if act == ACT_GELU else 0)
             _book(M, d_out, hid)
-            if not self.bf:
-                _use_planes(w1, p1, w2, p2)
             L.call('u3d_ffn_fwd', L.ptr(x), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), act | self.flag, L.ptr(h), L.ptr(a), L.ptr(z),
-                   M, d_in, hid, d_out, 1.0 if _PROFILE_FLOPS else 0.0, L.stream())
+                   M, d_in, hid, d_out, L.ptr(p1), L.ptr(p2), 1.0 if _PROFILE_FLOPS else 0.0, L.stream())
         return h, a, z
 
     def relu_nt(self, x, w, bias, planes=None):
@@ -261,9 +250,8 @@ class _Flow32:
         N = w.shape[0]
         a = torch.empty(M, N, dtype=torch.float32, device=x.device)
         if M:
-            if not self.bf:
-                _use_planes(w, planes)
-            L.call('u3d_linear_act', L.ptr(x), L.ptr(w), L.ptr(bias), ACT_RELU | self.flag, None, L.ptr(a), M, N, K, _book(M, N, K), L.stream())
+            L.call('u3d_linear_act', L.ptr(x), L.ptr(w), L.ptr(bias), ACT_RELU | self.flag, None, L.ptr(a), M, N, K, L.ptr(planes),
+                   _book(M, N, K), L.stream())
         return a
 
     def ln_linear(self, x, gamma, beta, eps, w, bias):
@@ -275,7 +263,7 @@ class _Flow32:
         y = torch.empty(M, N, dtype=torch.float32, device=x.device)
         if M:
             L.call('u3d_ln_linear', L.ptr(x), None, L.ptr(gamma), L.ptr(beta), float(eps), None, L.ptr(nq), L.ptr(stats), L.ptr(w),
-                   L.ptr(bias), self.flag, None, L.ptr(y), M, C, N, _book(M, N, C), L.stream())
+                   L.ptr(bias), self.flag, None, L.ptr(y), M, C, N, None, _book(M, N, C), L.stream())
         return nq, None, stats, y
 
 
