@@ -517,6 +517,27 @@ int64_t u3d_gemm_tn_b16_ws_bytes(int64_t M, int N, int K);
 int u3d_gelu_fwd_b16(const void* h, void* a, int64_t n, u3d_stream_t stream);
 int u3d_gelu_bwd_b16(const void* da, const void* h, void* dh, int64_t n, u3d_stream_t stream);
 
+/* ---- what a GEMM launch with the same sizes WOULD do (pure host functions: no GPU, no HIP call; like u3d_spconv_plan).  Each query
+ * calls the very function its launch path takes the decision from, so it reports the current fp32 math mode (u3d_fp32_math) and the
+ * environment overrides (U3D_NT_TILE, U3D_NT16_TILE, U3D_TN_WGS, U3D_TN16_WGS, U3D_TN_X3) as well, and returns the launch's own
+ * status for sizes the launch refuses (U3D_EINVAL: a size <= 0, an unknown epi / flag; U3D_EUNSUPPORTED with a message: K no multiple
+ * of 16 / 32, TN with N or K no multiple of 4 / 8, an odd N or epi 5 with a bf16 C, 32-bit offsets).  Output pointers may be NULL.
+ * Kernel families: */
+#define U3D_GEMM_NATIVE 0 /* v_mfma_f32_32x32x2_f32 on fp32 operands: gemm_nt_k, gemm_tn_k */
+#define U3D_GEMM_X3 1     /* three bf16 planes per fp32 operand: gemm_nt_x3_k (W split in flight or passed as w_planes), gemm_tn_x3_k */
+#define U3D_GEMM_B16 2    /* operands rounded to bf16: gemm_nt_b16_k; gemm_tn_bf16_k (u3d_gemm_tn_bf16), gemm_tn_b16_k (u3d_gemm_tn_b16) */
+/* u3d_gemm_nt / u3d_linear_act / u3d_linear_dact / u3d_gemm_nt_add / u3d_ffn_fwd (one query per product); flags: 0 or
+ * U3D_BF16_OPERANDS.  tile_m x tile_n: rows x columns of C per workgroup (128 x 128, 128 x 64 or 64 x 64). */
+int u3d_gemm_nt_plan(int64_t M, int N, int K, int flags, int* kernel, int* tile_m, int* tile_n);
+/* u3d_gemm_nt_b16 (always U3D_GEMM_B16); epi and flags as there */
+int u3d_gemm_nt_b16_plan(int64_t M, int N, int K, int epi, int flags, int* tile_m, int* tile_n);
+/* u3d_gemm_tn (bf16_operands = 0) / u3d_gemm_tn_bf16 (1).  tile_n x tile_k: rows x columns of C[N,K] per workgroup; the M rows are
+ * cut into `splits` pieces of rows_per_split rows (whole trips of the kernel: the last piece may be ragged, and pieces that begin at
+ * or past row M are empty -- they still write a zero partial, which the fixed-order reduce sums). */
+int u3d_gemm_tn_plan(int64_t M, int N, int K, int bf16_operands, int* kernel, int* tile_n, int* tile_k, int* splits, int64_t* rows_per_split);
+/* u3d_gemm_tn_b16 (always U3D_GEMM_B16, 128 x 128 tiles); flags as there */
+int u3d_gemm_tn_b16_plan(int64_t M, int N, int K, int flags, int* tile_n, int* tile_k, int* splits, int64_t* rows_per_split);
+
 /* =====================================================================================
  * K15 LayerNorm of the decoder (unidet3d/encoder.py:21,38-40,61,78-79,140,167) with the preceding residual add fused in.
  *      forward: s = x (+ res), y = (s - mean) * rstd * gamma + beta; sum_out receives s when res != NULL (the tensor

@@ -85,24 +85,25 @@ def test_gemm_tn_workspace_covers_every_kernel_plan():
     count depends on the kernel that runs (fp32 MFMA tiles 128 / 64, bf16, three-plane 128x64 / 64x64 tiles with 32-row trips,
     gemm.hip tn_splits / tn_x3_splits).  The size query must cover the largest of them for the decoder's shapes and the edge cases."""
     from unidet3d_amd import _lib
+    from unidet3d_amd import precision as P
     l = _lib.lib()
 
-    def cdiv(a, b):
-        return -(-a // b)
+    def splits(M, N, K, bf):      # u3d_gemm_tn_plan: the function the launch itself takes its split count from
+        s = ctypes.c_int(0)
+        assert l.u3d_gemm_tn_plan(M, N, K, bf, None, None, None, ctypes.byref(s), None) == 0, (M, N, K, bf)
+        return s.value
 
-    def x3_splits(M, N, K):      # gemm.hip tn_x3_splits
-        ta = 128 if cdiv(N, 128) * cdiv(K, 128) >= 16 else 64
-        tiles = cdiv(N, ta) * cdiv(K, 64)
-        return max(1, min(256, cdiv(768, tiles), cdiv(M, 4 * 32)))
-
-    def fp32_splits(M, N, K, T):  # gemm.hip tn_splits (default target of 768 workgroups, 16-row steps)
-        tiles = cdiv(N, T) * cdiv(K, T)
-        return max(1, min(256, cdiv(768, tiles), cdiv(M, 4 * 16)))
-
+    # the decoder's shapes and the edge cases; the last two have row splits that lie wholly past M (they still write a partial)
     for M, N, K in [(12300, 1024, 256), (12300, 256, 1024), (12300, 768, 256), (12300, 256, 256), (24600, 256, 32), (2500, 20, 256),
-                    (1, 256, 256), (333, 8, 256), (1_000_000, 256, 256)]:
-        need = max(x3_splits(M, N, K), fp32_splits(M, N, K, 128), fp32_splits(M, N, K, 64))
+                    (1, 256, 256), (333, 8, 256), (1_000_000, 256, 256), (2049, 512, 768), (32769, 64, 64)]:
+        need = 0
+        for mode in ('mfma', 'bf16x3'):       # the native and the three-plane kernel; the bf16-operand one under either
+            with P.fp32_math(mode):
+                need = max(need, splits(M, N, K, 0), splits(M, N, K, 1))
         assert l.u3d_gemm_tn_ws_bytes(M, N, K) >= (need + 8) * (N * K + N) * 4, (M, N, K)
+        s16 = ctypes.c_int(0)
+        assert l.u3d_gemm_tn_b16_plan(M, N, K, 0, None, None, ctypes.byref(s16), None) == 0
+        assert l.u3d_gemm_tn_b16_ws_bytes(M, N, K) >= s16.value * (N * K + N) * 4, (M, N, K)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason='CPU-only check')

@@ -120,6 +120,10 @@ PROTOTYPES = {
     'u3d_gemm_tn_b16_ws_bytes': (_i64, [_i64, _i32, _i32]),
     'u3d_gelu_fwd_b16': (_i32, [_vp, _vp, _i64, _vp]),
     'u3d_gelu_bwd_b16': (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    'u3d_gemm_nt_plan': (_i32, [_i64, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    'u3d_gemm_nt_b16_plan': (_i32, [_i64, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    'u3d_gemm_tn_plan': (_i32, [_i64, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
+    'u3d_gemm_tn_b16_plan': (_i32, [_i64, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
     'u3d_gemm_tn': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _f64, _vp]),
     'u3d_gemm_tn_bf16': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _f64, _vp]),
     'u3d_gemm_tn_ws_bytes': (_i64, [_i64, _i32, _i32]),

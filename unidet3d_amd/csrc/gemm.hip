@@ -794,9 +794,13 @@ static int tn_splits(int64_t M, int N, int K, int T, bool bf) {
 // (0.51 of the MFMA peak).  Candidates 128x128, 128x64, 64x64: time ~ ceil(wgs / 256) * tile area * (1 + overhead of the tile:
 // LDS fragment reads and staging per MFMA grow as the tile shrinks).  Measured on the bench step (MI355X, round 3 visit F): all
 // GEMMs 6.71 ms with 128x64 everywhere, 6.37 ms with 64x64 everywhere -> the overhead of the small tile is small: 4 % / 8 %.
-template <int EPI>
-static void launch_nt(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, const float* aux, float* pre,
-                      bool bf16_operands, bool x3, hipStream_t s, const void* wplanes) {
+// The ONE decision of an NT launch over fp32 tensors (gemm_nt_epi and the u3d_gemm_nt_plan query both call it): the refusals that
+// depend on the sizes alone, the kernel family under the current fp32 math mode, and the tile.
+static int nt_plan(int64_t M, int N, int K, bool bf, NtPlan* plan) {
+    if (M <= 0 || N <= 0 || K <= 0) return U3D_EINVAL;
+    const bool x3 = !bf && fp32_x3() && K % GKH == 0;        // K = 16 (mod 32) keeps the native fp32 kernel
+    if (K % (bf ? GKH : GK)) { set_error("gemm_nt: K=%d must be a multiple of %d", K, bf ? GKH : GK); return U3D_EUNSUPPORTED; }
+    if (!nt_offsets_ok("gemm_nt", N, K)) return U3D_EUNSUPPORTED;
     static const int force = [] { const char* e = getenv("U3D_NT_TILE"); return e ? atoi(e) : 0; }();       // 1 / 2 / 3 = 128x128 / 128x64 / 64x64
     const double over[3] = {1.0, 1.04, 1.08};
     int best = 0;
@@ -812,6 +816,16 @@ static void launch_nt(const float* A, const float* W, const float* bias, float* 
     if (x3 && M >= 4096) best = 1;
     if (force >= 1 && force <= 3) best = force - 1;
     if (x3 && best == 0) best = 1;
+    plan->kernel = bf ? U3D_GEMM_B16 : (x3 ? U3D_GEMM_X3 : U3D_GEMM_NATIVE);
+    plan->tile = best;
+    return U3D_OK;
+}
+
+template <int EPI>
+static void launch_nt(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, const float* aux, float* pre,
+                      const NtPlan& plan, hipStream_t s, const void* wplanes) {
+    const int best = plan.tile;
+    const bool bf16_operands = plan.kernel == U3D_GEMM_B16, x3 = plan.kernel == U3D_GEMM_X3;
     const dim3 grid = nt_grid(M, N, best);       // (row tile, column tile) decoded in the kernel
     if (bf16_operands) launch_nt_b16_f32(EPI, best, A, W, bias, C, M, N, K, aux, pre, s);       // gemm_b16.hip's kernel on this tile
     else if (x3 && wplanes) {
@@ -832,19 +846,48 @@ static int gemm_nt_epi(const float* A, const float* W, const float* bias, float*
     const bool bf = (epi & 8) != 0;
     epi &= 7;
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || epi < 0 || epi > 5 || (epi == 2 && !pre) || (epi >= 3 && !aux)) return U3D_EINVAL;
-    const bool x3 = !bf && fp32_x3() && K % GKH == 0;        // K = 16 (mod 32) keeps the native fp32 kernel
-    if (K % (bf ? GKH : GK)) { set_error("gemm_nt: K=%d must be a multiple of %d", K, bf ? GKH : GK); return U3D_EUNSUPPORTED; }
+    NtPlan plan;
+    if (const int rc = nt_plan(M, N, K, bf, &plan)) return rc;
     ProfScope prof(U3D_K_GEMM, s, flops_hint);
-    if (!nt_offsets_ok("gemm_nt", N, K)) return U3D_EUNSUPPORTED;
     switch (epi) {
-        case 0: launch_nt<0>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
-        case 1: launch_nt<1>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
-        case 2: launch_nt<2>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
-        case 3: launch_nt<3>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
-        case 4: launch_nt<4>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
-        default: launch_nt<5>(A, W, bias, C, M, N, K, aux, pre, bf, x3, s, wplanes); break;
+        case 0: launch_nt<0>(A, W, bias, C, M, N, K, aux, pre, plan, s, wplanes); break;
+        case 1: launch_nt<1>(A, W, bias, C, M, N, K, aux, pre, plan, s, wplanes); break;
+        case 2: launch_nt<2>(A, W, bias, C, M, N, K, aux, pre, plan, s, wplanes); break;
+        case 3: launch_nt<3>(A, W, bias, C, M, N, K, aux, pre, plan, s, wplanes); break;
+        case 4: launch_nt<4>(A, W, bias, C, M, N, K, aux, pre, plan, s, wplanes); break;
+        default: launch_nt<5>(A, W, bias, C, M, N, K, aux, pre, plan, s, wplanes); break;
     }
     return check_launch("gemm_nt");
+}
+
+// three-plane form (gemm_tn_x3_k): 128 x 64 tiles where gemm_tn_k takes 128 x 128 ones, 64 x 64 otherwise
+static bool tn_x3_on() { static const int on = [] { const char* e = getenv("U3D_TN_X3"); return e ? atoi(e) : 1; }(); return on != 0 && fp32_x3(); }
+static int tn_x3_ta(int N, int K) { return tn_tile(N, K) == GT ? 128 : 64; }
+static int tn_x3_splits(int64_t M, int N, int K) {
+    const int64_t tiles = ceil_div(N, tn_x3_ta(N, K)) * ceil_div(K, 64);
+    return tn_clamp_splits(ceil_div(768, tiles), M, TXK);
+}
+
+// The ONE decision of a TN launch over fp32 tensors (gemm_tn_impl and the u3d_gemm_tn_plan query both call it): kernel family under the
+// current fp32 math mode, tile, row splits and rows per split (whole trips of the kernel: splits past the last row stay empty).
+static int tn_plan(int64_t M, int N, int K, bool bf, TnPlan* plan) {
+    if (M <= 0 || N <= 0 || K <= 0) return U3D_EINVAL;
+    if (N % 4 || K % 4) { set_error("gemm_tn: N=%d, K=%d must be multiples of 4", N, K); return U3D_EUNSUPPORTED; }
+    // fp32 weight gradients: three-plane products (gemm_tn_x3_k) in the bf16x3 math mode since round 4 -- all GEMM launches of the
+    // bench step 5.87 -> 5.46 ms (U3D_TN_X3=0 keeps gemm_tn_k, same box).  Round 3's attempt (pair-packed planes, ds_read_b32
+    // fragments, every wave splitting what it read) had 64 x 64 tiles at 45 us against 45 us and 128 x 128 tiles out of registers
+    // once the low-order products got a tile of their own; the transpose read and the once-per-element split are what changed.
+    const bool x3 = !bf && tn_x3_on();
+    const int T = bf ? GT : tn_tile(N, K);
+    const int S = x3 ? tn_x3_splits(M, N, K) : tn_splits(M, N, K, T, bf);
+    const int64_t rps = x3 ? ceil_div(ceil_div(M, S), TXK) * TXK : ceil_div(ceil_div(M, S), GK) * GK;
+    if (!tn_offsets_ok("gemm_tn", M, N, K, rps)) return U3D_EUNSUPPORTED;
+    plan->kernel = x3 ? U3D_GEMM_X3 : (bf ? U3D_GEMM_B16 : U3D_GEMM_NATIVE);
+    plan->ta = x3 ? tn_x3_ta(N, K) : T;
+    plan->tb = x3 ? 64 : T;
+    plan->splits = S;
+    plan->rows_per_split = rps;
+    return U3D_OK;
 }
 
 }  // namespace u3d
@@ -902,14 +945,6 @@ int u3d_ffn_fwd(const float* X, const float* W1, const float* b1, const float* W
     return gemm_nt_epi(A, W2, b2, Z, M, d_out, hid, bf, nullptr, nullptr, w2_planes, f2, (hipStream_t)stream);
 }
 
-// three-plane form (gemm_tn_x3_k): 128 x 64 tiles where gemm_tn_k takes 128 x 128 ones, 64 x 64 otherwise
-static bool tn_x3_on() { static const int on = [] { const char* e = getenv("U3D_TN_X3"); return e ? atoi(e) : 1; }(); return on != 0 && fp32_x3(); }
-static int tn_x3_ta(int N, int K) { return tn_tile(N, K) == GT ? 128 : 64; }
-static int tn_x3_splits(int64_t M, int N, int K) {
-    const int64_t tiles = ceil_div(N, tn_x3_ta(N, K)) * ceil_div(K, 64);
-    return tn_clamp_splits(ceil_div(768, tiles), M, TXK);
-}
-
 int64_t u3d_gemm_tn_ws_bytes(int64_t M, int N, int K) {
     // the fp32 and the bf16 kernel pick their split counts independently (U3D_TN_WGS moves only the former): size for the larger
     const int s32 = tn_splits(M, N, K, GT, false), s32b = tn_splits(M, N, K, tn_tile(N, K), false), s16 = tn_splits(M, N, K, GT, true);
@@ -922,31 +957,45 @@ int64_t u3d_gemm_tn_ws_bytes(int64_t M, int N, int K) {
 static int gemm_tn_impl(const float* A, const float* B, float* C, float* colsum_A, int64_t M, int N, int K, void* ws, double flops_hint,
                         u3d_stream_t stream, bool bf) {
     if (!A || !B || !C || !ws || M <= 0 || N <= 0 || K <= 0) return U3D_EINVAL;
-    if (N % 4 || K % 4) { set_error("gemm_tn: N=%d, K=%d must be multiples of 4", N, K); return U3D_EUNSUPPORTED; }
+    TnPlan plan;
+    if (const int rc = tn_plan(M, N, K, bf, &plan)) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_GEMM, s, flops_hint);
-    // fp32 weight gradients: three-plane products (gemm_tn_x3_k) in the bf16x3 math mode since round 4 -- all GEMM launches of the
-    // bench step 5.87 -> 5.46 ms (U3D_TN_X3=0 keeps gemm_tn_k, same box).  Round 3's attempt (pair-packed planes, ds_read_b32
-    // fragments, every wave splitting what it read) had 64 x 64 tiles at 45 us against 45 us and 128 x 128 tiles out of registers
-    // once the low-order products got a tile of their own; the transpose read and the once-per-element split are what changed.
-    const bool x3 = !bf && tn_x3_on();
-    const int T = bf ? GT : tn_tile(N, K);
-    const int S = x3 ? tn_x3_splits(M, N, K) : tn_splits(M, N, K, T, bf);
-    const int64_t rps = x3 ? ceil_div(ceil_div(M, S), TXK) * TXK : ceil_div(ceil_div(M, S), GK) * GK;
-    if (!tn_offsets_ok("gemm_tn", M, N, K, rps)) return U3D_EUNSUPPORTED;
-    if (x3) {
-        const int ta = tn_x3_ta(N, K);
-        const unsigned grid = tn_grid(S, N, K, ta, 64);
-        if (ta == 128) hipLaunchKernelGGL((gemm_tn_x3_k<128, 64>), dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
+    const int S = plan.splits;
+    const int64_t rps = plan.rows_per_split;
+    if (plan.kernel == U3D_GEMM_X3) {
+        const unsigned grid = tn_grid(S, N, K, plan.ta, plan.tb);
+        if (plan.ta == 128) hipLaunchKernelGGL((gemm_tn_x3_k<128, 64>), dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
         else hipLaunchKernelGGL((gemm_tn_x3_k<64, 64>), dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
-    } else if (bf) hipLaunchKernelGGL(gemm_tn_bf16_k, dim3((unsigned)ceil_div(N, GT), (unsigned)ceil_div(K, GT), S), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps);
+    } else if (plan.kernel == U3D_GEMM_B16) hipLaunchKernelGGL(gemm_tn_bf16_k, dim3((unsigned)ceil_div(N, GT), (unsigned)ceil_div(K, GT), S), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps);
     else {
-        const unsigned grid = tn_grid(S, N, K, T, T);
-        if (T == 64) hipLaunchKernelGGL(gemm_tn_k<64>, dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
+        const unsigned grid = tn_grid(S, N, K, plan.ta, plan.tb);
+        if (plan.ta == 64) hipLaunchKernelGGL(gemm_tn_k<64>, dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
         else hipLaunchKernelGGL(gemm_tn_k<GT>, dim3(grid), dim3(256), 0, s, A, B, (float*)ws, colsum_A ? 1 : 0, M, N, K, rps, S);
     }
     launch_tn_reduce((const float*)ws, S, N, K, C, colsum_A, s);
     return check_launch("gemm_tn");
+}
+
+int u3d_gemm_nt_plan(int64_t M, int N, int K, int flags, int* kernel, int* tile_m, int* tile_n) {
+    if (flags & ~U3D_BF16_OPERANDS) return U3D_EINVAL;
+    NtPlan plan;
+    if (const int rc = nt_plan(M, N, K, (flags & U3D_BF16_OPERANDS) != 0, &plan)) return rc;
+    if (kernel) *kernel = plan.kernel;
+    if (tile_m) *tile_m = NT_TM[plan.tile];
+    if (tile_n) *tile_n = NT_TN[plan.tile];
+    return U3D_OK;
+}
+
+int u3d_gemm_tn_plan(int64_t M, int N, int K, int bf16_operands, int* kernel, int* tile_n, int* tile_k, int* splits, int64_t* rows_per_split) {
+    TnPlan plan;
+    if (const int rc = tn_plan(M, N, K, bf16_operands != 0, &plan)) return rc;
+    if (kernel) *kernel = plan.kernel;
+    if (tile_n) *tile_n = plan.ta;
+    if (tile_k) *tile_k = plan.tb;
+    if (splits) *splits = plan.splits;
+    if (rows_per_split) *rows_per_split = plan.rows_per_split;
+    return U3D_OK;
 }
 
 int u3d_gelu_fwd(const float* h, float* a, int64_t n, u3d_stream_t stream) {

@@ -409,8 +409,14 @@ static void launch_nt16_tile(int tile, const void* A, const float* W, const floa
     else hipLaunchKernelGGL((gemm_nt_b16_k<64, EPI, 64, A16, C16>), grid, dim3(256), 0, s, A, W, bias, C, M, N, K, aux);
 }
 
-template <int EPI, bool A16, bool C16>
-static void launch_nt16(const void* A, const float* W, const float* bias, void* C, int64_t M, int N, int K, const void* aux, hipStream_t s) {
+// The ONE decision of u3d_gemm_nt_b16 (the launch and the u3d_gemm_nt_b16_plan query both call it): the refusals that depend on the
+// sizes, epi and flags alone, and the tile.
+static int nt16_plan(int64_t M, int N, int K, int epi, int flags, NtPlan* plan) {
+    if (M <= 0 || N <= 0 || K <= 0 || (epi != 0 && epi != 1 && epi != 3 && epi != 5)) return U3D_EINVAL;
+    if (flags & ~(U3D_A_BF16 | U3D_C_BF16)) return U3D_EINVAL;
+    if (K % HK) { set_error("gemm_nt_b16: K=%d must be a multiple of %d", K, HK); return U3D_EUNSUPPORTED; }
+    if ((flags & U3D_C_BF16) && (N % 2 || epi == 5)) { set_error("gemm_nt_b16: a bf16 result needs an even N (%d) and epi != 5", N); return U3D_EUNSUPPORTED; }
+    if (!nt_offsets_ok("gemm_nt_b16", N, K)) return U3D_EUNSUPPORTED;
     // tile choice: the largest tile that still gives every CU a workgroup.  gemm.hip's rounds-of-256-workgroups model does not
     // describe this kernel (three to four workgroups share a CU and most of a workgroup's life is load latency): measured at
     // M = 24 600 (tools/prof_gemm16.py, us, 128 x 128 | 128 x 64 | 64 x 64): N, K = 256, 256: 10.9 | 11.6 | 12.8; 768, 256: 24.6 | 28.6 |
@@ -421,7 +427,9 @@ static void launch_nt16(const void* A, const float* W, const float* bias, void* 
         if (ceil_div(M, NT_TM[c]) * ceil_div(N, NT_TN[c]) >= 256) { best = c; break; }
     if (N <= 64 && best == 0) best = 1;               // narrow results (class / box heads): no empty half tile
     if (force >= 1 && force <= 3) best = force - 1;
-    launch_nt16_tile<EPI, A16, C16>(best, A, W, bias, C, M, N, K, aux, s);
+    plan->kernel = U3D_GEMM_B16;
+    plan->tile = best;
+    return U3D_OK;
 }
 
 void launch_nt_b16_f32(int epi, int tile, const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, const float* aux,
@@ -437,16 +445,16 @@ void launch_nt_b16_f32(int epi, int tile, const float* A, const float* W, const 
 }
 
 template <int EPI>
-static void launch_nt16_types(const void* A, const float* W, const float* bias, void* C, int64_t M, int N, int K, const void* aux, int flags, hipStream_t s) {
+static void launch_nt16_types(int tile, const void* A, const float* W, const float* bias, void* C, int64_t M, int N, int K, const void* aux, int flags, hipStream_t s) {
     const bool a16 = flags & U3D_A_BF16, c16 = flags & U3D_C_BF16;
     if constexpr (EPI == 5) {          // the addend form is fp32 out only
-        if (a16) launch_nt16<EPI, true, false>(A, W, bias, C, M, N, K, aux, s);
-        else launch_nt16<EPI, false, false>(A, W, bias, C, M, N, K, aux, s);
+        if (a16) launch_nt16_tile<EPI, true, false>(tile, A, W, bias, C, M, N, K, aux, s);
+        else launch_nt16_tile<EPI, false, false>(tile, A, W, bias, C, M, N, K, aux, s);
     } else {
-        if (a16 && c16) launch_nt16<EPI, true, true>(A, W, bias, C, M, N, K, aux, s);
-        else if (a16) launch_nt16<EPI, true, false>(A, W, bias, C, M, N, K, aux, s);
-        else if (c16) launch_nt16<EPI, false, true>(A, W, bias, C, M, N, K, aux, s);
-        else launch_nt16<EPI, false, false>(A, W, bias, C, M, N, K, aux, s);
+        if (a16 && c16) launch_nt16_tile<EPI, true, true>(tile, A, W, bias, C, M, N, K, aux, s);
+        else if (a16) launch_nt16_tile<EPI, true, false>(tile, A, W, bias, C, M, N, K, aux, s);
+        else if (c16) launch_nt16_tile<EPI, false, true>(tile, A, W, bias, C, M, N, K, aux, s);
+        else launch_nt16_tile<EPI, false, false>(tile, A, W, bias, C, M, N, K, aux, s);
     }
 }
 
@@ -460,6 +468,21 @@ static int tn16_splits(int64_t M, int N, int K) {
     return tn_clamp_splits(ceil_div(target, tiles), M, WKH);
 }
 
+// The ONE decision of u3d_gemm_tn_b16 (the launch and the u3d_gemm_tn_b16_plan query both call it)
+static int tn16_plan(int64_t M, int N, int K, int flags, TnPlan* plan) {
+    if (M <= 0 || N <= 0 || K <= 0 || (flags & ~(U3D_A_BF16 | U3D_B_BF16))) return U3D_EINVAL;
+    const bool a16 = flags & U3D_A_BF16, b16 = flags & U3D_B_BF16;
+    if (N % (a16 ? 8 : 4) || K % (b16 ? 8 : 4)) { set_error("gemm_tn_b16: N=%d, K=%d must be multiples of 4 (fp32 operand) / 8 (bf16 operand)", N, K); return U3D_EUNSUPPORTED; }
+    const int S = tn16_splits(M, N, K);
+    const int64_t rps = ceil_div(ceil_div(M, S), WKH) * WKH;
+    if (!tn_offsets_ok("gemm_tn_b16", M, N, K, rps)) return U3D_EUNSUPPORTED;
+    plan->kernel = U3D_GEMM_B16;
+    plan->ta = plan->tb = HT;
+    plan->splits = S;
+    plan->rows_per_split = rps;
+    return U3D_OK;
+}
+
 }  // namespace u3d
 
 using namespace u3d;
@@ -469,19 +492,25 @@ extern "C" {
 int u3d_gemm_nt_b16(const void* A, const float* W, const float* bias, int epi, const void* aux, void* C, int flags, int64_t M, int N, int K,
                     double flops_hint, u3d_stream_t stream) {
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || (epi != 0 && epi != 1 && epi != 3 && epi != 5) || (epi >= 3 && !aux)) return U3D_EINVAL;
-    if (flags & ~(U3D_A_BF16 | U3D_C_BF16)) return U3D_EINVAL;
-    if (K % HK) { set_error("gemm_nt_b16: K=%d must be a multiple of %d", K, HK); return U3D_EUNSUPPORTED; }
-    if ((flags & U3D_C_BF16) && (N % 2 || epi == 5)) { set_error("gemm_nt_b16: a bf16 result needs an even N (%d) and epi != 5", N); return U3D_EUNSUPPORTED; }
-    if (!nt_offsets_ok("gemm_nt_b16", N, K)) return U3D_EUNSUPPORTED;
+    NtPlan plan;
+    if (const int rc = nt16_plan(M, N, K, epi, flags, &plan)) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_GEMM, s, flops_hint);
     switch (epi) {
-        case 0: launch_nt16_types<0>(A, W, bias, C, M, N, K, aux, flags, s); break;
-        case 1: launch_nt16_types<1>(A, W, bias, C, M, N, K, aux, flags, s); break;
-        case 3: launch_nt16_types<3>(A, W, bias, C, M, N, K, aux, flags, s); break;
-        default: launch_nt16_types<5>(A, W, bias, C, M, N, K, aux, flags, s); break;
+        case 0: launch_nt16_types<0>(plan.tile, A, W, bias, C, M, N, K, aux, flags, s); break;
+        case 1: launch_nt16_types<1>(plan.tile, A, W, bias, C, M, N, K, aux, flags, s); break;
+        case 3: launch_nt16_types<3>(plan.tile, A, W, bias, C, M, N, K, aux, flags, s); break;
+        default: launch_nt16_types<5>(plan.tile, A, W, bias, C, M, N, K, aux, flags, s); break;
     }
     return check_launch("gemm_nt_b16");
+}
+
+int u3d_gemm_nt_b16_plan(int64_t M, int N, int K, int epi, int flags, int* tile_m, int* tile_n) {
+    NtPlan plan;
+    if (const int rc = nt16_plan(M, N, K, epi, flags, &plan)) return rc;
+    if (tile_m) *tile_m = NT_TM[plan.tile];
+    if (tile_n) *tile_n = NT_TN[plan.tile];
+    return U3D_OK;
 }
 
 int64_t u3d_gemm_tn_b16_ws_bytes(int64_t M, int N, int K) { return (int64_t)(tn16_splits(M, N, K) + 1) * ((int64_t)N * K + N) * 4 + 256; }
@@ -489,14 +518,14 @@ int64_t u3d_gemm_tn_b16_ws_bytes(int64_t M, int N, int K) { return (int64_t)(tn1
 int u3d_gemm_tn_b16(const void* A, const void* B, float* C, float* colsum_A, int flags, int64_t M, int N, int K, void* ws, double flops_hint,
                     u3d_stream_t stream) {
     if (!A || !B || !C || !ws || M <= 0 || N <= 0 || K <= 0 || (flags & ~(U3D_A_BF16 | U3D_B_BF16))) return U3D_EINVAL;
+    TnPlan plan;
+    if (const int rc = tn16_plan(M, N, K, flags, &plan)) return rc;
     const bool a16 = flags & U3D_A_BF16, b16 = flags & U3D_B_BF16;
-    if (N % (a16 ? 8 : 4) || K % (b16 ? 8 : 4)) { set_error("gemm_tn_b16: N=%d, K=%d must be multiples of 4 (fp32 operand) / 8 (bf16 operand)", N, K); return U3D_EUNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(U3D_K_GEMM, s, flops_hint);
-    const int S = tn16_splits(M, N, K);
-    const int64_t rps = ceil_div(ceil_div(M, S), WKH) * WKH;
-    if (!tn_offsets_ok("gemm_tn_b16", M, N, K, rps)) return U3D_EUNSUPPORTED;
-    const dim3 grid(tn_grid(S, N, K, HT, HT));
+    const int S = plan.splits;
+    const int64_t rps = plan.rows_per_split;
+    const dim3 grid(tn_grid(S, N, K, plan.ta, plan.tb));
     const int cs = colsum_A ? 1 : 0;
     if (a16 && b16) hipLaunchKernelGGL((gemm_tn_b16_k<true, true>), grid, dim3(256), 0, s, A, B, (float*)ws, cs, M, N, K, rps, S);
     else if (a16) hipLaunchKernelGGL((gemm_tn_b16_k<true, false>), grid, dim3(256), 0, s, A, B, (float*)ws, cs, M, N, K, rps, S);
@@ -504,6 +533,16 @@ int u3d_gemm_tn_b16(const void* A, const void* B, float* C, float* colsum_A, int
     else hipLaunchKernelGGL((gemm_tn_b16_k<false, false>), grid, dim3(256), 0, s, A, B, (float*)ws, cs, M, N, K, rps, S);
     launch_tn_reduce((const float*)ws, S, N, K, C, colsum_A, s);
     return check_launch("gemm_tn_b16");
+}
+
+int u3d_gemm_tn_b16_plan(int64_t M, int N, int K, int flags, int* tile_n, int* tile_k, int* splits, int64_t* rows_per_split) {
+    TnPlan plan;
+    if (const int rc = tn16_plan(M, N, K, flags, &plan)) return rc;
+    if (tile_n) *tile_n = plan.ta;
+    if (tile_k) *tile_k = plan.tb;
+    if (splits) *splits = plan.splits;
+    if (rows_per_split) *rows_per_split = plan.rows_per_split;
+    return U3D_OK;
 }
 
 int u3d_gelu_fwd_b16(const void* h, void* a, int64_t n, u3d_stream_t stream) {

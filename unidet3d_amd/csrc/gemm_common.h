@@ -87,6 +87,10 @@ inline bool tn_offsets_ok(const char* who, int64_t M, int N, int K, int64_t rows
 }
 // 1-D grid of the TN kernels, padded to whole groups of 8 splits (a workgroup whose split is >= S returns)
 inline unsigned tn_grid(int S, int N, int K, int ta, int tb) { return (unsigned)(ceil_div(S, 8) * 8 * ceil_div(N, ta) * ceil_div(K, tb)); }
+// What a launch does, decided in ONE host function per dispatcher (gemm.hip nt_plan / tn_plan, gemm_b16.hip nt16_plan / tn16_plan)
+// that the launch path and the u3d_gemm_*_plan queries both call: kernel family (U3D_GEMM_* of include/u3d.h), tile, row splits.
+struct NtPlan { int kernel, tile; };                                  // tile: index into NT_TM / NT_TN
+struct TnPlan { int kernel, ta, tb, splits; int64_t rows_per_split; };  // ta x tb: output rows (columns of A) x output columns (columns of B)
 // C [N*K] (and colsum [N], nullable) = the S blocks of `ws` summed in a fixed order (gemm.hip)
 void launch_tn_reduce(const float* ws, int S, int N, int K, float* C, float* colsum, hipStream_t s);
 // gemm_b16.hip's gemm_nt_b16_k<.., A16 = false, C16 = false> on tile `tile` of the table above, for gemm.hip's U3D_BF16_OPERANDS route
