@@ -57,6 +57,15 @@ int u3d_fp32_math(int mode);
  * of one row (none: both accumulate offsets in ascending order).  Returns the previous mode; other arguments only query. */
 int u3d_conv_kernel(int mode);
 
+/* How many waves of 16 query rows (dK / dV: key rows) share a workgroup of the plane attention kernels (csrc/attn_x3.hip) and with
+ * it every staged 64-row K / V (Q / dO) tile:
+ *   0 (default; env U3D_ATTN_TILE_WAVES unset or neither 4 nor 8): the launch plan -- per kernel, data flow, head dim and dropout the
+ *     form that measured fastest (DESIGN 4.2 "tile waves");
+ *   4 | 8: that form for the three kernels of every call (tests, A/B runs).
+ * A wave runs the same program in every form: results are bit-identical.  Returns the previous value; other arguments -- 6 among
+ * them: a six-wave form was built, measured slower everywhere and removed -- only query. */
+int u3d_attn_tile_waves(int waves);
+
 /* ---- kernel timing (HIP events on the launch stream; used by bench.py's roofline) ---- */
 enum { U3D_K_CONV_FWD = 0, U3D_K_CONV_WGRAD = 1, U3D_K_BN = 2, U3D_K_POOL = 3, U3D_K_ATTN_FWD = 4,
        U3D_K_ATTN_BWD = 5, U3D_K_RULEBOOK = 6, U3D_K_VOXELIZE = 7, U3D_K_GEMM = 8, U3D_K_COUNT = 9 };

@@ -17,7 +17,10 @@ of its own (--no-sdpa --reps 5 under rocprofv3 --kernel-trace --stats).
 softmax probabilities, mask regenerated in the kernels) beside the p = 0 ones, gives torch's per-scene call dropout_p = P -- what a user
 without these kernels would run -- and prints the ratios `_drop` / p = 0 and `_drop` / torch.
 
-    python tools/attn_time.py [--reps 30] [--warmup 5] [--dropout 0.1] [--out profiles/attn_hd64_time.txt]
+--waves 4,8 (DESIGN 4.2 "tile waves") adds, alternating with the others, the same calls with that many waves per workgroup forced
+(precision.attn_tile_waves) beside the launch plan's choice, and prints each forced form over the first one listed.
+
+    python tools/attn_time.py [--reps 30] [--warmup 5] [--dropout 0.1] [--waves 4,8] [--out profiles/attn_hd64_time.txt]
 """
 import argparse
 import contextlib
@@ -56,6 +59,7 @@ def main():
     ap.add_argument('--d', type=int, default=256)
     ap.add_argument('--no-sdpa', action='store_true')
     ap.add_argument('--dropout', type=float, default=0.0)
+    ap.add_argument('--waves', default='', help='comma-separated tile waves to force beside the plan, e.g. 4,8')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -73,12 +77,14 @@ def main():
     flows = [('fp32', torch.float32, contextlib.nullcontext), ('bf16 ops', torch.float32, lambda: P.operands('bf16')),
              ('bf16', torch.bfloat16, contextlib.nullcontext)]
 
-    def lib_variant(flow, dtype, ctx, H, p=0.0):
+    waves = [int(w) for w in args.waves.split(',') if w]
+
+    def lib_variant(flow, dtype, ctx, H, p=0.0, nw=None):
         x = qkv32.clone().to(dtype).requires_grad_()
         go = go32.to(dtype)
 
         def run():
-            with ctx():
+            with ctx(), (P.attn_tile_waves(nw) if nw is not None else contextlib.nullcontext()):
                 x.grad = None
                 out, ef = _timed(lambda: attention_varlen(x, cu, n, H, 0, p, (1234, 5)))
                 _, eb = _timed(lambda: out.backward(go))
@@ -106,6 +112,13 @@ def main():
         for flow, dtype, ctx in flows:
             for H, hd in splits:
                 variants.append((f'library  {flow:<8} H={H} hd={hd} dropout {args.dropout}', flow + ' drop', hd, lib_variant(flow, dtype, ctx, H, args.dropout)))
+    for nw in waves:
+        for flow, dtype, ctx in flows:
+            for H, hd in splits:
+                variants.append((f'library  {flow:<8} H={H} hd={hd} waves {nw}', f'{flow} waves {nw}', hd, lib_variant(flow, dtype, ctx, H, 0.0, nw)))
+                if args.dropout:
+                    variants.append((f'library  {flow:<8} H={H} hd={hd} dropout {args.dropout} waves {nw}', f'{flow} drop waves {nw}', hd,
+                                     lib_variant(flow, dtype, ctx, H, args.dropout, nw)))
     sdpa_tag = f' dropout {args.dropout}' if args.dropout else ''
     if not args.no_sdpa:
         for flow, dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
@@ -152,6 +165,18 @@ def main():
                 s = by.get('sdpa ' + ('bf16' if flow == 'bf16' else 'fp32'))
                 if s:
                     line += f'   | over torch  fwd {med(fwd[d]) / med(fwd[s[hd]]):.3f}   bwd {med(bwd[d]) / med(bwd[s[hd]]):.3f}'
+                lines.append(line)
+    if len(waves) > 1:
+        med = statistics.median
+        lines += ['', f'tile waves: each forced form over waves {waves[0]} of the same flow and head dim (medians, with the (max - min) / median of the '
+                      f'waves {waves[0]} samples: a form is ahead only by more than that)']
+        for tag in [f for f, _, _ in flows] + ([f + ' drop' for f, _, _ in flows] if args.dropout else []):
+            for _, hd in splits:
+                z = by[f'{tag} waves {waves[0]}'][hd]
+                line = f'{tag:<14} hd={hd}  spread fwd {(max(fwd[z]) - min(fwd[z])) / med(fwd[z]):.3f} bwd {(max(bwd[z]) - min(bwd[z])) / med(bwd[z]):.3f}'
+                for nw in waves[1:]:
+                    d = by[f'{tag} waves {nw}'][hd]
+                    line += f'   | waves {nw}: fwd {med(fwd[d]) / med(fwd[z]):.3f}  bwd {med(bwd[d]) / med(bwd[z]):.3f}'
                 lines.append(line)
     text = '\n'.join(lines) + '\n'
     print(text)

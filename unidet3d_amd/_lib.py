@@ -23,6 +23,7 @@ PROTOTYPES = {
     'u3d_last_error': (C.c_char_p, []),
     'u3d_fp32_math': (_i32, [_i32]),
     'u3d_conv_kernel': (_i32, [_i32]),
+    'u3d_attn_tile_waves': (_i32, [_i32]),
     'u3d_prof_enable': (_i32, [_i32, _i32]),
     'u3d_prof_collect': (_i32, [_i32, C.POINTER(_f64), C.POINTER(_i64), C.POINTER(_f64)]),
     'u3d_vox_scene_stats': (_i32, [_vp, _vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp]),

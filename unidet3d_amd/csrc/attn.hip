@@ -324,7 +324,7 @@ int attn_fwd(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_l
     ProfScope prof(U3D_K_ATTN_FWD, s, flops_hint);
     if (max_len <= 0) return U3D_OK;
     if (mode == ATTN_NATIVE) {
-        const int n_tiles = (max_len + 63) / 64;
+        const int n_tiles = attn_tiles(max_len, 64);
         hipLaunchKernelGGL(attn_fwd_k, dim3(attn_grid(H, B, n_tiles)), dim3(256), 0, s, (const float*)qkv, cu, H, scale, (float*)out, lse, n_total, B, n_tiles);
     } else {
         attn_fwd_x3_launch(mode, qkv, cu, B, max_len, n_total, H, hd, scale, out, lse, s, dr);
@@ -349,7 +349,7 @@ int attn_bwd(AttnMode mode, const void* qkv, const void* out, const void* dout, 
         else hipLaunchKernelGGL((attn_delta_k<float, 32>), dgrid, dim3(256), 0, s, (const float*)out, (const float*)dout, n_total, H, delta_ws);
     }
     if (mode == ATTN_NATIVE) {
-        const int n_tiles = (max_len + 63) / 64;
+        const int n_tiles = attn_tiles(max_len, 64);
         const dim3 grid(attn_grid(H, B, n_tiles));
         hipLaunchKernelGGL(attn_bwd_dq_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);
         hipLaunchKernelGGL(attn_bwd_dkv_k, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, (const float*)delta_ws, cu, H, scale, (float*)dqkv, n_total, B, n_tiles);

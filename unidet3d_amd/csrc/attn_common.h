@@ -7,7 +7,7 @@
 namespace u3d {
 
 // 1-D launch decode: workgroup b runs on XCD b % 8 (private L2).  XCD x takes the (scene, head) pairs x, x+8, ...
-// and all their 64-row tiles back to back, so the K/V (or Q/dO) rows of one (scene, head) stay in that XCD's
+// and all their tiles (64 rows; attn_x3.hip: 16 rows per wave of the workgroup, attn_tiles) back to back, so the K/V (or Q/dO) rows of one (scene, head) stay in that XCD's
 // L2 while its tiles stream them (PMC before: 321 MB fetched per forward launch for 49 MB of qkv).
 struct AttnWork { int b, h, tile; };
 __device__ __forceinline__ AttnWork attn_decode(int H, int B, int n_tiles) {
@@ -19,6 +19,7 @@ __device__ __forceinline__ AttnWork attn_decode(int H, int B, int n_tiles) {
     w.b = hb / H;          // >= B for the padding workgroups of the last group
     return w;
 }
+static inline int attn_tiles(int max_len, int tile_rows) { return (max_len + tile_rows - 1) / tile_rows; }
 static inline unsigned attn_grid(int H, int B, int n_tiles) { return (unsigned)(((H * B + 7) / 8) * 8 * n_tiles); }
 
 // delta[h][i] = sum_d dO[i][h*HD+d] * O[i][h*HD+d]; T = float, or __bf16 for bf16 tensors (products and sum in fp32)

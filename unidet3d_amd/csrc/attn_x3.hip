@@ -26,12 +26,13 @@
 //   outputs     O, dQ, dK, dV are CB = HD / 16 blocks of 16 columns; the running sums keep their separate low-order accumulators
 //               (mfma_x3_2b, called per pair of column blocks with the same P / dS operand planes).
 //   staging     a thread holds dims 4c .. 4c+3 (c = tid % (HD / 4)) of the R = HD / 16 rows R p .. R p + R-1 (p = tid / (HD / 4)): 8 (16)
-//               lanes cover a row's 128 (256) bytes.
+//               lanes cover a row's 128 (256) bytes.  (Four waves per workgroup; with eight, half the rows per thread: "tile waves" below.)
 //   LDS         the chunk XOR of the unpadded natural planes, xswz<HD> -- the one place where the two widths differ in logic.
 //   registers   DESIGN 4.2 "head_dim 64": no instantiation uses scratch; dK / dV with three planes runs three (HD = 64: two) workgroups
 //               per CU (DKV_WAVES).
 #include <mutex>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "attn_common.h"
 
@@ -151,26 +152,37 @@ __device__ __forceinline__ void mfma_x3_2c(const bf16x8 (&a)[KK][NP], const bf16
             }
 }
 
-// Stage 64 rows x HD floats of `base` (rows >= len are zero, values scaled before the split): thread (p = tid / (HD / 4), c = tid % (HD / 4))
-// holds dims 4c .. 4c+3 of the R = HD / 16 rows R p .. R p + R-1; load_x3 issues the global loads (one tile ahead of their use: the
-// compute phase of the tile before covers their latency), store_x3 splits and writes the natural planes nat[NP][64][HD] halves.
-template <int HD> struct StageRegs { f32x4 v[HD / 16]; };
-template <int HD>
-__device__ __forceinline__ StageRegs<HD> load_x3(const float* __restrict__ base, int ld, int row0, int len, int tid) {
-    constexpr int R = HD / 16;
+// Stage 64 rows x HD floats of `base` (rows >= len are zero, values scaled before the split).  A workgroup of NW waves (16 NW query / key
+// rows of its own, DESIGN 4.2 "tile waves") stages every 64-row tile ONCE for all of them: its 64 NW threads share the tile, thread
+// (p = tid / (HD / 4), c = tid % (HD / 4)) holding dims 4c .. 4c+3 of the R = STG_R rows R p .. R p + R-1 -- HD / 16 rows at NW = 4, HD / 32
+// at NW = 8.  load_x3 issues the global loads (one tile ahead of their use: the compute phase of the tile before covers their latency),
+// store_x3 splits and writes the natural planes nat[NP][64][HD] halves.  The LDS image does not depend on NW.
+// The loads are raw buffer loads through a descriptor over the tile's rows below `len` (tile_rsrc): a row past the end of the scene reads
+// zeros in the range check of the load itself -- no branch, no zero fill, no 64-bit address per row -- and the descriptor is rebuilt per
+// tile from wave-uniform values, so a thread's byte offset (tile_voff, the same for every tile, plus a scalar row offset) stays below 64 rows whatever `len` is.
+template <int HD, int NW> constexpr int STG_R = HD / (4 * NW);
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const T* __restrict__ base, int ld, int row0, int len) {
+    const int rows = len - row0 < 64 ? len - row0 : 64;
+    return make_rsrc(base + (int64_t)row0 * ld, rows > 0 ? (int64_t)rows * ld * (int)sizeof(T) : 0);
+}
+template <int HD, int NW, typename T>
+__device__ __forceinline__ int tile_voff(int ld, int tid) {          // of the thread's first row; row j of its R: + j * ld elements, a scalar offset
     const int p = tid / (HD / 4), c = tid % (HD / 4);
-    const int r0 = row0 + R * p;
-    StageRegs<HD> r;
+    return (STG_R<HD, NW> * p * ld + c * 4) * (int)sizeof(T);
+}
+template <int HD, int NW> struct StageRegs { f32x4 v[STG_R<HD, NW>]; };
+template <int HD, int NW>
+__device__ __forceinline__ StageRegs<HD, NW> load_x3(const float* __restrict__ base, int ld, int row0, int len, int tid) {
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, ld, row0, len);
+    StageRegs<HD, NW> r;
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
-        r.v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (r0 + j < len) r.v[j] = *reinterpret_cast<const f32x4*>(base + (int64_t)(r0 + j) * ld + c * 4);
-    }
+    for (int j = 0; j < STG_R<HD, NW>; ++j) r.v[j] = bload128(rs, tile_voff<HD, NW, float>(ld, tid), j * ld * (int)sizeof(float));
     return r;
 }
-template <int HD, int NP>
-__device__ __forceinline__ void store_x3(StageRegs<HD> r, float scale, __bf16* nat, int tid) {
-    constexpr int R = HD / 16;
+template <int HD, int NP, int NW>
+__device__ __forceinline__ void store_x3(StageRegs<HD, NW> r, float scale, __bf16* nat, int tid) {
+    constexpr int R = STG_R<HD, NW>;
     const int p = tid / (HD / 4), c = tid % (HD / 4);
     unsigned w[R][2][NP];
 #pragma unroll
@@ -190,23 +202,18 @@ __device__ __forceinline__ void store_x3(StageRegs<HD> r, float scale, __bf16* n
 
 // bf16 tensors in HBM (IO16; one plane, include/u3d.h u3d_attn_varlen_*_b16): the same staging map with 8-byte loads and no arithmetic --
 // the staged values are the tensor's own, so a scale cannot be folded in here (the kernels apply it to the scores / to dK instead)
-template <int HD> struct StageRegs16 { uint2 v[HD / 16]; };
-template <int HD>
-__device__ __forceinline__ StageRegs16<HD> load_x16(const __bf16* __restrict__ base, int ld, int row0, int len, int tid) {
-    constexpr int R = HD / 16;
-    const int p = tid / (HD / 4), c = tid % (HD / 4);
-    const int r0 = row0 + R * p;
-    StageRegs16<HD> r;
+template <int HD, int NW> struct StageRegs16 { uint2 v[STG_R<HD, NW>]; };
+template <int HD, int NW>
+__device__ __forceinline__ StageRegs16<HD, NW> load_x16(const __bf16* __restrict__ base, int ld, int row0, int len, int tid) {
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, ld, row0, len);
+    StageRegs16<HD, NW> r;
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
-        r.v[j] = make_uint2(0u, 0u);
-        if (r0 + j < len) r.v[j] = *reinterpret_cast<const uint2*>(base + (int64_t)(r0 + j) * ld + c * 4);
-    }
+    for (int j = 0; j < STG_R<HD, NW>; ++j) r.v[j] = bload64(rs, tile_voff<HD, NW, __bf16>(ld, tid), j * ld * (int)sizeof(__bf16));
     return r;
 }
-template <int HD>
-__device__ __forceinline__ void store_x16(StageRegs16<HD> r, __bf16* nat, int tid) {
-    constexpr int R = HD / 16;
+template <int HD, int NW>
+__device__ __forceinline__ void store_x16(StageRegs16<HD, NW> r, __bf16* nat, int tid) {
+    constexpr int R = STG_R<HD, NW>;
     const int p = tid / (HD / 4), c = tid % (HD / 4);
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -214,19 +221,19 @@ __device__ __forceinline__ void store_x16(StageRegs16<HD> r, __bf16* nat, int ti
         *reinterpret_cast<uint2*>(nat + row * HD + (((c >> 1) ^ xswz<HD>(row)) * 8) + (c & 1) * 4) = r.v[j];
     }
 }
-template <bool IO16> struct IoT { typedef float t; template <int HD> using regs = StageRegs<HD>; };
-template <> struct IoT<true> { typedef __bf16 t; template <int HD> using regs = StageRegs16<HD>; };
+template <bool IO16> struct IoT { typedef float t; template <int HD, int NW> using regs = StageRegs<HD, NW>; };
+template <> struct IoT<true> { typedef __bf16 t; template <int HD, int NW> using regs = StageRegs16<HD, NW>; };
 template <bool IO16> using io_of = typename IoT<IO16>::t;                                        // the tensors' element type
-template <int HD, bool IO16> using io_regs = typename IoT<IO16>::template regs<HD>;            // a thread's share of a staged tile
-template <int HD, bool IO16>
-__device__ __forceinline__ io_regs<HD, IO16> load_io(const io_of<IO16>* __restrict__ base, int ld, int row0, int len, int tid) {
-    if constexpr (IO16) return load_x16<HD>(base, ld, row0, len, tid);
-    else return load_x3<HD>(base, ld, row0, len, tid);
+template <int HD, bool IO16, int NW> using io_regs = typename IoT<IO16>::template regs<HD, NW>;   // a thread's share of a staged tile
+template <int HD, bool IO16, int NW>
+__device__ __forceinline__ io_regs<HD, IO16, NW> load_io(const io_of<IO16>* __restrict__ base, int ld, int row0, int len, int tid) {
+    if constexpr (IO16) return load_x16<HD, NW>(base, ld, row0, len, tid);
+    else return load_x3<HD, NW>(base, ld, row0, len, tid);
 }
-template <int HD, int NP, bool IO16>
-__device__ __forceinline__ void store_io(io_regs<HD, IO16> r, float scale, __bf16* nat, int tid) {
-    if constexpr (IO16) store_x16<HD>(r, nat, tid);
-    else store_x3<HD, NP>(r, scale, nat, tid);
+template <int HD, int NP, bool IO16, int NW>
+__device__ __forceinline__ void store_io(io_regs<HD, IO16, NW> r, float scale, __bf16* nat, int tid) {
+    if constexpr (IO16) store_x16<HD, NW>(r, nat, tid);
+    else store_x3<HD, NP, NW>(r, scale, nat, tid);
 }
 template <bool IO16>
 __device__ __forceinline__ void put_io(io_of<IO16>* p, float v) {
@@ -264,8 +271,8 @@ __device__ __forceinline__ DropNone drop_of() { return DropNone{}; }
 __device__ __forceinline__ DropArgs drop_of(DropArgs a) { return a; }
 template <typename... DR> constexpr bool DROP_ON = sizeof...(DR) == 1;
 
-template <int HD, int NP, bool IO16, typename... DR>
-__global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restrict__ qkv, const int32_t* __restrict__ cu, int H, float scale,
+template <int HD, int NP, bool IO16, int NW, typename... DR>
+__global__ __launch_bounds__(64 * NW) void attn_fwd_x3_k(const io_of<IO16>* __restrict__ qkv, const int32_t* __restrict__ cu, int H, float scale,
                                                      io_of<IO16>* __restrict__ out, float* __restrict__ lse, int64_t n_total, int B, int n_tiles,
                                                      DR... dr_) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
@@ -279,7 +286,7 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restri
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
-    const int q0 = wk_.tile * 64;
+    const int q0 = wk_.tile * (16 * NW);
     if (q0 >= len) return;
     const int D = H * HD, ld = 3 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
@@ -299,14 +306,14 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restri
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) o[cb] = ol[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntiles = (len + 63) >> 6;
-    io_regs<HD, IO16> rk = load_io<HD, IO16>(base + D, ld, 0, len, tid), rv = load_io<HD, IO16>(base + 2 * D, ld, 0, len, tid);
+    io_regs<HD, IO16, NW> rk = load_io<HD, IO16, NW>(base + D, ld, 0, len, tid), rv = load_io<HD, IO16, NW>(base + 2 * D, ld, 0, len, tid);
     for (int kt = 0; kt < ntiles; ++kt) {
         __syncthreads();
-        store_io<HD, NP, IO16>(rk, 1.f, Kn, tid);
-        store_io<HD, NP, IO16>(rv, 1.f, Vn, tid);
+        store_io<HD, NP, IO16, NW>(rk, 1.f, Kn, tid);
+        store_io<HD, NP, IO16, NW>(rv, 1.f, Vn, tid);
         if (kt + 1 < ntiles) {
-            rk = load_io<HD, IO16>(base + D, ld, kt * 64 + 64, len, tid);
-            rv = load_io<HD, IO16>(base + 2 * D, ld, kt * 64 + 64, len, tid);
+            rk = load_io<HD, IO16, NW>(base + D, ld, kt * 64 + 64, len, tid);
+            rv = load_io<HD, IO16, NW>(base + 2 * D, ld, kt * 64 + 64, len, tid);
         }
         __syncthreads();
         float st[4][4];
@@ -400,8 +407,8 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_k(const io_of<IO16>* __restri
 
 // dQ: one workgroup per 64-query tile, keys streamed.  K is read by rows for S and by columns for dQ += dS . K.
 // DROP: dS = P . (M . dP' / (1 - p) - delta); the lane's query and keys are those of the forward kernel
-template <int HD, int NP, bool IO16, typename... DR>
-__global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
+template <int HD, int NP, bool IO16, int NW, typename... DR>
+__global__ __launch_bounds__(64 * NW) void attn_bwd_dq_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
                                                         const float* __restrict__ delta, const int32_t* __restrict__ cu, int H, float scale,
                                                         io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles, DR... dr_) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
@@ -415,7 +422,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __res
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
-    const int q0 = wk_.tile * 64;
+    const int q0 = wk_.tile * (16 * NW);
     if (q0 >= len) return;
     const int D = H * HD, ld = 3 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
@@ -443,14 +450,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __res
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) dq[cb] = dql[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntiles = (len + 63) >> 6;
-    io_regs<HD, IO16> rk = load_io<HD, IO16>(base + D, ld, 0, len, tid), rv = load_io<HD, IO16>(base + 2 * D, ld, 0, len, tid);
+    io_regs<HD, IO16, NW> rk = load_io<HD, IO16, NW>(base + D, ld, 0, len, tid), rv = load_io<HD, IO16, NW>(base + 2 * D, ld, 0, len, tid);
     for (int kt = 0; kt < ntiles; ++kt) {
         __syncthreads();
-        store_io<HD, NP, IO16>(rk, 1.f, Kn, tid);
-        store_io<HD, NP, IO16>(rv, 1.f, Vn, tid);
+        store_io<HD, NP, IO16, NW>(rk, 1.f, Kn, tid);
+        store_io<HD, NP, IO16, NW>(rv, 1.f, Vn, tid);
         if (kt + 1 < ntiles) {
-            rk = load_io<HD, IO16>(base + D, ld, kt * 64 + 64, len, tid);
-            rv = load_io<HD, IO16>(base + 2 * D, ld, kt * 64 + 64, len, tid);
+            rk = load_io<HD, IO16, NW>(base + D, ld, kt * 64 + 64, len, tid);
+            rv = load_io<HD, IO16, NW>(base + 2 * D, ld, kt * 64 + 64, len, tid);
         }
         __syncthreads();
         const bool last = kt == ntiles - 1 && (len & 63);          // wave-uniform
@@ -502,12 +509,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_x3_k(const io_of<IO16>* __res
 // dK, dV: one workgroup per 64-key tile, queries streamed.  Q and dO are read by rows (S, dP) and by columns (dK, dV).
 // (HD = 32, three planes: three workgroups per CU -- the compiler settles at 178 VGPRs without the bound and 166, no spills, with it.
 // HD = 64: the accumulators and the register-resident K / V planes double; DKV_WAVES asks for what leaves no scratch -- DESIGN 4.2.
-// DROP: the keep mask and the hash temporaries take HD = 32 with three planes from 154 to over 168 registers -- two workgroups per CU there, no scratch)
-template <int HD, int NP, bool DROP> constexpr int DKV_WAVES = NP == 3 ? (HD == 32 && !DROP ? 3 : 2) : 1;
+// DROP: the keep mask and the hash temporaries take HD = 32 with three planes from 154 to over 168 registers -- two workgroups per CU there, no scratch.
+// NW = 8: a workgroup is two waves per SIMD, so three per SIMD cannot be had: two it is -- four costs 52 bytes of scratch at 128 registers
+// and measured 467 us against 428 us of NW = 4, DESIGN 4.2 "tile waves")
+template <int HD, int NP, bool DROP, int NW> constexpr int DKV_WAVES = NP == 3 ? (HD == 32 && !DROP && NW != 8 ? 3 : 2) : 1;
 // DROP: dV += (P . M)^T dO / (1 - p) (the factor at the end), dS = P . (M . dP' / (1 - p) - delta).  Here a lane holds ONE key (c = start +
 // krow) and four consecutive queries (b = start + 64 qt + 16 qb + 4g + r): the row stage of the hash runs per element.
-template <int HD, int NP, bool IO16, typename... DR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<HD, NP, DROP_ON<DR...>>))) void attn_bwd_dkv_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
+template <int HD, int NP, bool IO16, int NW, typename... DR>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<HD, NP, DROP_ON<DR...>, NW>))) void attn_bwd_dkv_x3_k(const io_of<IO16>* __restrict__ qkv, const io_of<IO16>* __restrict__ dout, const float* __restrict__ lse,
                                                          const float* __restrict__ delta, const int32_t* __restrict__ cu, int H, float scale,
                                                          io_of<IO16>* __restrict__ dqkv, int64_t n_total, int B, int n_tiles, DR... dr_) {
     static_assert(!IO16 || NP == 1, "bf16 tensors carry one plane");
@@ -522,7 +531,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<H
     const int b = wk_.b, h = wk_.h;
     if (b >= B) return;
     const int start = cu[b], len = cu[b + 1] - start;
-    const int k0 = wk_.tile * 64;
+    const int k0 = wk_.tile * (16 * NW);
     if (k0 >= len) return;
     const int D = H * HD, ld = 3 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
@@ -547,14 +556,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DKV_WAVES<H
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) dk[cb] = dv[cb] = dkl[cb] = dvl[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntiles = (len + 63) >> 6;
-    io_regs<HD, IO16> rq = load_io<HD, IO16>(base, ld, 0, len, tid), ro = load_io<HD, IO16>(dobase, D, 0, len, tid);
+    io_regs<HD, IO16, NW> rq = load_io<HD, IO16, NW>(base, ld, 0, len, tid), ro = load_io<HD, IO16, NW>(dobase, D, 0, len, tid);
     for (int qt = 0; qt < ntiles; ++qt) {
         __syncthreads();
-        store_io<HD, NP, IO16>(rq, scale * X_LOG2E, Qn, tid);  // log2 units; dK is rescaled by ln 2 at the end (IO16: Q as it is, scores scaled, dK by `scale`)
-        store_io<HD, NP, IO16>(ro, 1.f, On, tid);
+        store_io<HD, NP, IO16, NW>(rq, scale * X_LOG2E, Qn, tid);  // log2 units; dK is rescaled by ln 2 at the end (IO16: Q as it is, scores scaled, dK by `scale`)
+        store_io<HD, NP, IO16, NW>(ro, 1.f, On, tid);
         if (qt + 1 < ntiles) {
-            rq = load_io<HD, IO16>(base, ld, qt * 64 + 64, len, tid);
-            ro = load_io<HD, IO16>(dobase, D, qt * 64 + 64, len, tid);
+            rq = load_io<HD, IO16, NW>(base, ld, qt * 64 + 64, len, tid);
+            ro = load_io<HD, IO16, NW>(dobase, D, qt * 64 + 64, len, tid);
         }
         if (tid < 64) {
             const int q = qt * 64 + tid;
@@ -649,16 +658,43 @@ static void attn_x3_dispatch(int hd, AttnMode mode, F&& f) {
     else attn_x3_by_mode<32>(mode, f);
 }
 
+// ---- tile waves: how many waves -- 16 query (dK / dV: key) rows each -- share one workgroup and with it every staged tile ----
+// The per-wave program does not depend on NW, so every form gives the same bits; the plan holds, per kernel, what measured ahead of
+// NW = 4 (profiles/attn_tile_waves_time.txt), and u3d_attn_tile_waves (include/u3d.h) forces one form for tests and A/B runs.
+enum AttnKernel { ATTN_K_FWD, ATTN_K_DQ, ATTN_K_DKV };
+static int attn_plan_waves(AttnKernel k, AttnMode mode, int hd, bool drop) {
+    const int forced = u3d_attn_tile_waves(-1);
+    if (forced) return forced;
+    // Eight waves win where the staging they halve is largest and the registers they free raise the occupancy: three planes at head_dim 32,
+    // forward (120 -> 107 VGPRs, four waves per SIMD either way: 257.6 -> 252.7 us at 8 x 2125 queries) and dQ (164 -> 116, three -> four
+    // waves: 334.0 -> 322.4 us).  dK / dV needs 136 registers -- one 8-wave workgroup per CU instead of three 4-wave ones: 427.8 -> 499.9 us.
+    // One plane, head_dim 64 and the dropout forms measured level or behind at that size (ahead only at 3000 queries) and stay on four.
+    if (mode == ATTN_X3 && hd == 32 && !drop && (k == ATTN_K_FWD || k == ATTN_K_DQ)) return 8;
+    return 4;
+}
+template <typename F>
+static void attn_x3_by_waves(int nw, F&& f) {
+    if (nw == 8) f(std::integral_constant<int, 8>());
+    else f(std::integral_constant<int, 4>());
+}
+struct AttnGrid { dim3 grid; int n_tiles; };
+static AttnGrid attn_x3_grid(int H, int B, int max_len, int nw) {
+    const int n_tiles = attn_tiles(max_len, 16 * nw);
+    return {dim3(attn_grid(H, B, n_tiles)), n_tiles};
+}
+
 // launchers, called from attn.hip's attn_fwd / attn_bwd for every mode but ATTN_NATIVE (arguments already validated there: hd is 32 or 64)
 void attn_fwd_x3_launch(AttnMode mode, const void* qkv, const int32_t* cu, int B, int max_len, int64_t n_total, int H, int hd, float scale, void* out,
                         float* lse, hipStream_t s, const DropArgs* dr) {
-    const int n_tiles = (max_len + 63) / 64;
-    const dim3 grid(attn_grid(H, B, n_tiles));
     attn_x3_dispatch(hd, mode, [&](auto form) {
         typedef decltype(form) F;
         typedef typename F::io_t T;
-        if (dr) hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16, DropArgs>), grid, dim3(256), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, n_tiles, *dr);
-        else hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, n_tiles);
+        attn_x3_by_waves(attn_plan_waves(ATTN_K_FWD, mode, hd, dr != nullptr), [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            const AttnGrid g = attn_x3_grid(H, B, max_len, NW);
+            if (dr) hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16, NW, DropArgs>), g.grid, dim3(64 * NW), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, g.n_tiles, *dr);
+            else hipLaunchKernelGGL((attn_fwd_x3_k<F::HD, F::NP, F::IO16, NW>), g.grid, dim3(64 * NW), 0, s, (const T*)qkv, cu, H, scale, (T*)out, lse, n_total, B, g.n_tiles);
+        });
     });
 }
 
@@ -691,8 +727,6 @@ static AttnFork* attn_fork_of_device() {
 
 void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const float* lse, const int32_t* cu, int B, int max_len,
                         int64_t n_total, int H, int hd, float scale, void* dqkv, const float* delta, hipStream_t s, const DropArgs* dr) {
-    const int n_tiles = (max_len + 63) / 64;
-    const dim3 grid(attn_grid(H, B, n_tiles));
     AttnFork* f = attn_fork_of_device();
     hipStream_t sq = s;
     if (f) {
@@ -703,13 +737,18 @@ void attn_bwd_x3_launch(AttnMode mode, const void* qkv, const void* dout, const 
     attn_x3_dispatch(hd, mode, [&](auto form) {
         typedef decltype(form) F;
         typedef typename F::io_t T;
-        if (dr) {
-            hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16, DropArgs>), grid, dim3(256), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles, *dr);
-            hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16, DropArgs>), grid, dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles, *dr);
-        } else {
-            hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
-            hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16>), grid, dim3(256), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, n_tiles);
-        }
+        attn_x3_by_waves(attn_plan_waves(ATTN_K_DQ, mode, hd, dr != nullptr), [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            const AttnGrid g = attn_x3_grid(H, B, max_len, NW);
+            if (dr) hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16, NW, DropArgs>), g.grid, dim3(64 * NW), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, g.n_tiles, *dr);
+            else hipLaunchKernelGGL((attn_bwd_dq_x3_k<F::HD, F::NP, F::IO16, NW>), g.grid, dim3(64 * NW), 0, sq, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, g.n_tiles);
+        });
+        attn_x3_by_waves(attn_plan_waves(ATTN_K_DKV, mode, hd, dr != nullptr), [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            const AttnGrid g = attn_x3_grid(H, B, max_len, NW);
+            if (dr) hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16, NW, DropArgs>), g.grid, dim3(64 * NW), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, g.n_tiles, *dr);
+            else hipLaunchKernelGGL((attn_bwd_dkv_x3_k<F::HD, F::NP, F::IO16, NW>), g.grid, dim3(64 * NW), 0, s, (const T*)qkv, (const T*)dout, lse, delta, cu, H, scale, (T*)dqkv, n_total, B, g.n_tiles);
+        });
     });
     if (f) {
         hipEventRecord(f->join, f->side);

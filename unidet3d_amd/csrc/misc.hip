@@ -15,6 +15,7 @@ static thread_local char g_err[512] = "";
 
 int g_fp32_math = -1;
 int g_conv_kernel = -1;
+int g_attn_tile_waves = -1;
 bool fp32_x3() {
     if (g_fp32_math < 0) {
         const char* e = getenv("U3D_FP32_MATH");
@@ -264,6 +265,16 @@ int u3d_conv_kernel(int mode) {
     }
     const int prev = u3d::g_conv_kernel;
     if (mode == 0 || mode == 1 || mode == 2) u3d::g_conv_kernel = mode;
+    return prev;
+}
+int u3d_attn_tile_waves(int waves) {
+    if (u3d::g_attn_tile_waves < 0) {
+        const char* e = getenv("U3D_ATTN_TILE_WAVES");
+        const int v = e ? atoi(e) : 0;
+        u3d::g_attn_tile_waves = (v == 4 || v == 8) ? v : 0;
+    }
+    const int prev = u3d::g_attn_tile_waves;
+    if (waves == 0 || waves == 4 || waves == 8) u3d::g_attn_tile_waves = waves;
     return prev;
 }
 int u3d_fp32_math(int mode) {

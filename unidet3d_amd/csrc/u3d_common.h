@@ -58,6 +58,9 @@ using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 __device__ __forceinline__ f32x4 bload128(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
+__device__ __forceinline__ uint2 bload64(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
+    return __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+}
 __device__ __forceinline__ int bload32(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     return (int)__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
 }
@@ -77,6 +80,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, int64
 // fp64, per kernel and end to end).  U3D_FP32_MATH=mfma selects the native fp32 MFMA kernels instead.
 extern int g_fp32_math;
 extern int g_conv_kernel;      // 1: workgroup-tile sparse convolution (spconv_wg.hip), 0: wave tiles (u3d_conv_kernel)
+extern int g_attn_tile_waves;  // 0: the launch plan of attn_x3.hip, 4 / 8: that many waves per workgroup (u3d_attn_tile_waves)
 bool fp32_x3();
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 // ---- vector types and bf16 / MFMA helpers of the device code: ONE definition each, used by every .hip file ----

@@ -100,6 +100,25 @@ def conv_kernel(kind: str):
         set_conv_kernel(prev)
 
 
+def set_attn_tile_waves(waves: int) -> int:
+    """0 (default: the launch plan of csrc/attn_x3.hip) | 4 | 8 waves of 16 rows per workgroup of the plane attention kernels
+    (include/u3d.h: u3d_attn_tile_waves; env U3D_ATTN_TILE_WAVES).  Every form computes the same bits.  Returns the previous value.
+    Process-wide; A/B measurements and tests."""
+    from . import _lib as L
+    if waves not in (0, 4, 8):
+        raise ValueError('attention tile waves must be 0 (plan), 4 or 8')
+    return L.lib().u3d_attn_tile_waves(waves)
+
+
+@contextlib.contextmanager
+def attn_tile_waves(waves: int):
+    prev = set_attn_tile_waves(waves)
+    try:
+        yield
+    finally:
+        set_attn_tile_waves(prev)
+
+
 FMT_FP32, FMT_BF16, FMT_X3 = 0, 1, 2
 
 # bf16 operands (BASELINE configs[2]): batch-norm outputs and the gradients a batch norm hands back are ALSO written as bf16 rows
