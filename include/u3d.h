@@ -210,6 +210,35 @@ int u3d_spconv_gmm_x3(const float* src, int64_t n_src, const void* w_rows_x3, co
                       const int32_t* tile_starts, int K, int64_t cap, int Cs, int Cd, int64_t n_dst, int tile_rows,
                       int k_groups, const float* addend, float* dst, void* ws, float* bn_partial, double flops_hint, u3d_stream_t stream);
 int u3d_weight_pack_x3(const float* w, void* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream);
+/* ---- forward convolution with an OUTPUT EPILOGUE (fused inference: eval-mode batch norm + ReLU, the U-Net's concat buffer).
+ * The four launches above in one entry point -- fmt 0: u3d_spconv_gmm, 1: _bf16, 2: _x3, 3: _bf16a (src = bf16 rows); same kernels,
+ * same packed weights, same sums -- whose dst rows leave the accumulator tile through the host struct below instead of into dst.
+ * With x the fp32 value the plain launch stores (after the addend, after the fixed-order sum over offset groups):
+ *   raw (nullable)          raw[row * raw_ld + raw_col + c] = x[row][c]: dst as a column block of a wider buffer;
+ *   act[j], j < n_act <= 2  act[j][row * act_ld[j] + act_col[j] + c] = f(x[row][c] * scale[j][act_col[j] + c] + shift[j][act_col[j] + c]),
+ *                           f = max(., 0) where relu[j], else the identity: u3d_bn_apply's expression and rounding, bit for bit.
+ *                           scale / shift are indexed by the column of act[j] itself, so a norm over a wider tensor is applied to its
+ *                           column blocks by the launches that produce them.
+ * Contract: at least one output; every ld >= col + Cd, every ld and col a multiple of 4 floats (16-byte vector stores only), otherwise
+ * U3D_EINVAL; n_act outside [0, 2], or bn_partial non-NULL (the statistics epilogue of training and this one exclude each other):
+ * U3D_EUNSUPPORTED -- each with a u3d_last_error text and before any launch.  tile_rows in {32, 64} and k_groups in {1} (any K) or
+ * {3, 9} (K >= 27) are the CALLER'S choice here (u3d_spconv_plan[_bf16a] give the measured ones); ws = k_groups * n_dst * Cd * 4 bytes
+ * when k_groups > 1 -- the main kernel then writes partials as always and the epilogue runs in the reduce.  addend is [n_dst][Cd].
+ * Outputs must not overlap each other or the inputs.  Added entry point: U3D_ABI_VERSION is unchanged. */
+typedef struct u3d_conv_epilogue {
+    float* raw;
+    int64_t raw_ld, raw_col;
+    int n_act;
+    float* act[2];
+    const float* scale[2];
+    const float* shift[2];
+    int64_t act_ld[2], act_col[2];
+    int relu[2];
+} u3d_conv_epilogue;
+int u3d_spconv_gmm_ep(int fmt, const void* src, int64_t n_src, const void* w_rows, const int32_t* gather, const int32_t* scatter,
+                      const int32_t* tile_starts, int K, int64_t cap, int Cs, int Cd, int64_t n_dst, int tile_rows,
+                      int k_groups, const float* addend, void* ws, float* bn_partial, const u3d_conv_epilogue* ep, double flops_hint,
+                      u3d_stream_t stream);
 /* all packs of a model in one launch: desc = device array of n_desc records of eight int64
  * {src pointer, dst pointer, Cd, K, Cs, transposed, format (0 fp32, 1 bf16, 2 x3), first block}; record i owns blocks
  * [first_i, first_{i+1}) of 256 threads: one 16-byte output vector per thread in the fp32 (Cd*K*Cs/4 threads) and bf16 (Cd*K*Cs/8)

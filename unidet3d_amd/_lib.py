@@ -17,6 +17,14 @@ LIB_PATH = os.environ.get('U3D_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libu3d
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _u64 = C.c_uint64
 
+
+class ConvEpilogue(C.Structure):
+    """u3d_conv_epilogue (include/u3d.h): where the rows of a forward convolution go -- raw into a column block, up to two
+    batch norm (+ ReLU) outputs."""
+    _fields_ = [('raw', _vp), ('raw_ld', _i64), ('raw_col', _i64), ('n_act', _i32), ('act', _vp * 2), ('scale', _vp * 2), ('shift', _vp * 2),
+                ('act_ld', _i64 * 2), ('act_col', _i64 * 2), ('relu', _i32 * 2)]
+
+
 # name -> (restype, argtypes)   (mirrors include/u3d.h, checked by tests/test_cabi.py)
 PROTOTYPES = {
     'u3d_version': (_i32, []),
@@ -54,6 +62,8 @@ PROTOTYPES = {
     'u3d_weight_pack_batch': (_i32, [_vp, _i32, _i64, _vp]),
     'u3d_weight_pack_bf16': (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'u3d_spconv_gmm_x3': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp]),
+    'u3d_spconv_gmm_ep': (_i32, [_i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(ConvEpilogue),
+                                 _f64, _vp]),
     'u3d_weight_pack_x3': (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'u3d_spconv_rs_x3': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f64, _vp]),
     'u3d_spconv_rs_bf16a': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f64, _vp]),

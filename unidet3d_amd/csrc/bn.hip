@@ -223,8 +223,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const float* __restrict__ x, c
         const float4 v = reinterpret_cast<const float4*>(x)[i];
         const float4 sc = reinterpret_cast<const float4*>(scale)[c4];
         const float4 sf = reinterpret_cast<const float4*>(shift)[c4];
-        float4 o = make_float4(v.x * sc.x + sf.x, v.y * sc.y + sf.y, v.z * sc.z + sf.z, v.w * sc.w + sf.w);
-        if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+        const float4 o = bn_affine_relu(v, sc, sf, relu);
         reinterpret_cast<float4*>(y)[i] = o;
         if (yb) store_shadow(yb, i / C4, c4, C4, o);
     }

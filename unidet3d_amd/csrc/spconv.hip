@@ -428,8 +428,9 @@ constexpr int gmm_wave_lds(int cs16, int r) { return gmm_acc_rows(r) * GMM_ALD +
 // CHUNKED (wide layers: Cs / 16 outside the instantiated set, up to 512 channels): CS16 is the width of a CHUNK and the wave program runs
 // over a RUN-TIME number of chunks of the source row -- three chunk widths (32, 64, 128 channels) serve every multiple of 32 instead
 // of one fully unrolled body per width.
-template <int CS16, int R, int PR = 0, bool CHUNKED = false>
-__global__ __launch_bounds__(256) void spconv_gmm_k(GmmParams p) {
+template <int CS16, int R, int PR = 0, bool CHUNKED = false, bool EP = false>
+__global__ __launch_bounds__(256) void spconv_gmm_k(typename GmmArg<EP>::type pp) {
+    const GmmParams& p = pp;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: everything derived from it stays in SGPRs
@@ -477,6 +478,13 @@ __global__ __launch_bounds__(256) void spconv_gmm_k(GmmParams p) {
     // sum x^2 per channel: accumulated on the way out (lane = column quad c4, rows lane/8 + 8 i), folded over the 8 row groups
     // with three shuffles and stored as ONE partial row per tile -- bn_partials_k adds the tiles in fp64.  This replaces a
     // pass over dst (bn_reduce_k<0>) per layer; ~60 VALU instructions per tile, outside the MFMA loop.
+    if constexpr (EP) {                                // fused inference: raw into a wider buffer / norm + ReLU outputs (never with p.stats)
+        for (int idx = lane; idx < rows * (GMM_CDS / 4); idx += 64) {
+            const int r = idx >> 3, c4 = idx & 7;
+            gmm_write_out(pp.ep, row0 + r, n0 + c4 * 4, *reinterpret_cast<const float4*>(acc + gmm_acc_idx(r, c4)));
+        }
+        return;
+    }
     if (!p.stats) {                                    // wave-uniform (input-gradient launches, eval mode)
         for (int idx = lane; idx < rows * (GMM_CDS / 4); idx += 64) {
             const int r = idx >> 3, c4 = idx & 7;
@@ -518,6 +526,18 @@ __global__ __launch_bounds__(256) void gmm_reduce_k(const float* __restrict__ pa
         reinterpret_cast<float4*>(dst)[i] = v;
     }
 }
+// fused inference: the same sum in the same order, leaving through the epilogue (C4 = Cd / 4 locates the row and column of piece i)
+__global__ __launch_bounds__(256) void gmm_reduce_ep_k(const float* __restrict__ partial, int G, int64_t n4, const float* __restrict__ addend,
+                                                       int C4, GmmEpilogue ep) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 v = addend ? reinterpret_cast<const float4*>(addend)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int g = 0; g < G; ++g) {
+            const float4 t = reinterpret_cast<const float4*>(partial)[(int64_t)g * n4 + i];
+            v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+        }
+        gmm_write_out(ep, i / C4, (int)(i % C4) * 4, v);
+    }
+}
 
 // rows per wave-tile and offset groups.  Measured on MI355X at the cfg2 level sizes (tools/prof_gmm.py sweep, round 4,
 // profiles/round4_gmm_plan_sweep.txt): 64-row tiles win at every level once a level that cannot fill the chip with them
@@ -545,11 +565,19 @@ static void plan_gmm(int Cs, int Cd, int K, int64_t n_dst, int* R, int* G, bool 
     *G = g;
 }
 
+static GmmParamsEp gmm_with_epilogue(const GmmParams& p, const GmmEpilogue& ep) {
+    GmmParamsEp pe;
+    static_cast<GmmParams&>(pe) = p;
+    pe.ep = ep;
+    return pe;
+}
+
 template <int CS16, int R, int PR = 0>
-static int launch_gmm(const GmmParams& p, hipStream_t s) {
+static int launch_gmm(const GmmParams& p, hipStream_t s, const GmmEpilogue* ep) {
     const size_t lds = (size_t)4 * gmm_wave_lds(CS16, R) * sizeof(float);
     const int64_t waves = p.n_sub * p.n_slices * p.G;
-    hipLaunchKernelGGL((spconv_gmm_k<CS16, R, PR>), dim3((unsigned)ceil_div(waves, 4)), dim3(256), lds, s, p);
+    if (ep) hipLaunchKernelGGL((spconv_gmm_k<CS16, R, PR, false, true>), dim3((unsigned)ceil_div(waves, 4)), dim3(256), lds, s, gmm_with_epilogue(p, *ep));
+    else hipLaunchKernelGGL((spconv_gmm_k<CS16, R, PR>), dim3((unsigned)ceil_div(waves, 4)), dim3(256), lds, s, p);
     return check_launch("spconv_gmm");
 }
 
@@ -559,17 +587,21 @@ static int gmm_chunk16(int cs16) { return cs16 % 8 == 0 ? 8 : (cs16 % 4 == 0 ? 4
 static bool gmm_fixed_width(int cs16) { return cs16 == 1 || cs16 == 2 || cs16 == 4 || cs16 == 6 || cs16 == 8 || cs16 == 10 || cs16 == 12 || cs16 == 16; }
 
 template <int CH16, int PR>
-static int launch_gmm_chunk(const GmmParams& p, int R, hipStream_t s) {
+static int launch_gmm_chunk(const GmmParams& p, int R, hipStream_t s, const GmmEpilogue* ep) {
     const size_t lds = (size_t)4 * gmm_wave_lds(CH16, R) * sizeof(float);
     const unsigned grid = (unsigned)ceil_div(p.n_sub * p.n_slices * p.G, 4);
-    if (R == 64) hipLaunchKernelGGL((spconv_gmm_k<CH16, 64, PR, true>), dim3(grid), dim3(256), lds, s, p);
+    if (ep) {
+        const GmmParamsEp pe = gmm_with_epilogue(p, *ep);
+        if (R == 64) hipLaunchKernelGGL((spconv_gmm_k<CH16, 64, PR, true, true>), dim3(grid), dim3(256), lds, s, pe);
+        else hipLaunchKernelGGL((spconv_gmm_k<CH16, 32, PR, true, true>), dim3(grid), dim3(256), lds, s, pe);
+    } else if (R == 64) hipLaunchKernelGGL((spconv_gmm_k<CH16, 64, PR, true>), dim3(grid), dim3(256), lds, s, p);
     else hipLaunchKernelGGL((spconv_gmm_k<CH16, 32, PR, true>), dim3(grid), dim3(256), lds, s, p);
     return check_launch("spconv_gmm_chunk");
 }
 template <int PR>
-static int launch_gmm_wide(const GmmParams& p, int R, hipStream_t s) {
+static int launch_gmm_wide(const GmmParams& p, int R, hipStream_t s, const GmmEpilogue* ep) {
     const int ch = gmm_chunk16(p.Cs / 16);
-    return ch == 8 ? launch_gmm_chunk<8, PR>(p, R, s) : (ch == 4 ? launch_gmm_chunk<4, PR>(p, R, s) : launch_gmm_chunk<2, PR>(p, R, s));
+    return ch == 8 ? launch_gmm_chunk<8, PR>(p, R, s, ep) : (ch == 4 ? launch_gmm_chunk<4, PR>(p, R, s, ep) : launch_gmm_chunk<2, PR>(p, R, s, ep));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1055,9 +1087,35 @@ int u3d_spconv_gmm_bf16a_supported(int Cs, int Cd) {
 
 static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows, const int32_t* gather, const int32_t* scatter,
                            const int32_t* tile_starts, int K, int64_t cap, int Cs, int Cd, int64_t n_dst, int tile_rows,
-                           int k_groups, const float* addend, float* dst, void* ws, float* bn_partial, double flops_hint, u3d_stream_t stream, int pr) {
+                           int k_groups, const float* addend, float* dst, void* ws, float* bn_partial, double flops_hint, u3d_stream_t stream, int pr,
+                           const u3d_conv_epilogue* ep = nullptr) {
+    // with an epilogue (u3d_spconv_gmm_ep) dst is unused: the descriptor says where the rows go, and the caller states the plan
+    GmmEpilogue ge = {};
+    if (ep) {
+        if (bn_partial) { set_error("spconv_gmm_ep: an output epilogue and per-tile statistics (bn_partial) exclude each other"); return U3D_EUNSUPPORTED; }
+        if (ep->n_act < 0 || ep->n_act > 2) { set_error("spconv_gmm_ep: %d activated outputs (at most two)", ep->n_act); return U3D_EUNSUPPORTED; }
+        bool any = ep->raw != nullptr;
+        if (ep->raw && (ep->raw_ld < Cd || ep->raw_col < 0 || ep->raw_col + Cd > ep->raw_ld || ep->raw_ld % 4 || ep->raw_col % 4 || ep->raw_ld > (1 << 20))) {
+            set_error("spconv_gmm_ep: raw output ld=%lld col=%lld: ld >= col + Cd (Cd=%d), both multiples of 4 floats", (long long)ep->raw_ld, (long long)ep->raw_col, Cd);
+            return U3D_EINVAL;
+        }
+        ge.raw = ep->raw; ge.raw_ld = (int)ep->raw_ld; ge.raw_col = (int)ep->raw_col;
+        for (int j = 0; j < ep->n_act; ++j) {
+            if (!ep->act[j] || !ep->scale[j] || !ep->shift[j]) { set_error("spconv_gmm_ep: activated output %d: NULL act / scale / shift", j); return U3D_EINVAL; }
+            if (ep->act_ld[j] < Cd || ep->act_col[j] < 0 || ep->act_col[j] + Cd > ep->act_ld[j] || ep->act_ld[j] % 4 || ep->act_col[j] % 4 || ep->act_ld[j] > (1 << 20)) {
+                set_error("spconv_gmm_ep: activated output %d ld=%lld col=%lld: ld >= col + Cd (Cd=%d), both multiples of 4 floats", j,
+                          (long long)ep->act_ld[j], (long long)ep->act_col[j], Cd);
+                return U3D_EINVAL;
+            }
+            any = true;
+            ge.act[j] = ep->act[j]; ge.scale[j] = ep->scale[j]; ge.shift[j] = ep->shift[j];
+            ge.act_ld[j] = (int)ep->act_ld[j]; ge.act_col[j] = (int)ep->act_col[j]; ge.relu[j] = ep->relu[j] ? 1 : 0;
+        }
+        if (!any) { set_error("spconv_gmm_ep: no output (raw NULL and no activated output)"); return U3D_EINVAL; }
+        ge.n_act = ep->n_act;
+    }
     if (pr && Cs % 32) { set_error("spconv_gmm_%s: Cs=%d must be a multiple of 32", pr == 1 ? "bf16" : (pr == 2 ? "x3" : "bf16a"), Cs); return U3D_EUNSUPPORTED; }
-    if (!src || !w_rows || !gather || !scatter || !tile_starts || !dst || K <= 0 || K > 32 || n_dst <= 0 || n_src <= 0 || cap <= 0) return U3D_EINVAL;
+    if (!src || !w_rows || !gather || !scatter || !tile_starts || (!dst && !ep) || K <= 0 || K > 32 || n_dst <= 0 || n_src <= 0 || cap <= 0) return U3D_EINVAL;
     // the kernel addresses through 32-bit buffer offsets and multiplies row indices with v_mul_u32_u24
     if (pr == 3 && bn_partial) { set_error("spconv_gmm_bf16a: per-tile statistics are not produced by this kernel"); return U3D_EUNSUPPORTED; }
     if (n_src >= (1 << 24) || n_dst >= (1 << 24) || n_src * Cs * 4 >= 0x7fffffffLL || (int64_t)K * cap * 4 >= 0x7fffffffLL) {
@@ -1066,7 +1124,12 @@ static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows,
         return U3D_EUNSUPPORTED;
     }
     int R = 0, G = 0;
-    if (spconv_plan_impl(Cs, Cd, K, n_dst, &R, &G, pr == 3) != U3D_OK || R != tile_rows || G != k_groups || (G > 1 && !ws)) {
+    int plan_rc = spconv_plan_impl(Cs, Cd, K, n_dst, &R, &G, pr == 3);
+    if (ep && plan_rc == U3D_OK && (tile_rows == 32 || tile_rows == 64) && (k_groups == 1 || ((k_groups == 3 || k_groups == 9) && K >= 27))) {
+        R = tile_rows;            // every (tile height, offset groups) pair the kernels run: the caller's choice
+        G = k_groups;
+    }
+    if (plan_rc != U3D_OK || R != tile_rows || G != k_groups || (G > 1 && !ws)) {
         set_error("spconv_gmm: unsupported Cs=%d Cd=%d or plan mismatch (tile %d/%d groups %d/%d)", Cs, Cd, tile_rows, R, k_groups, G);
         return U3D_EUNSUPPORTED;
     }
@@ -1079,11 +1142,12 @@ static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows,
     p.stats = bn_partial;
     p.K = K; p.cap = cap; p.Cs = Cs; p.Cd = Cd; p.n_dst = n_dst; p.n_src = n_src; p.n_sub = ceil_div(n_dst, R);
     p.n_slices = Cd / GMM_CDS; p.G = G; p.kper = (int)ceil_div(K, G);
+    const GmmEpilogue* kep = ep && G == 1 ? &ge : nullptr;      // offset groups: the plain kernels write partials as always, the epilogue runs in the reduce
     const int cs16 = Cs / 16;
     int rc = U3D_EUNSUPPORTED;
-#define U3D_GMM_CASE(cs) if (cs16 == cs) rc = (R == 64) ? launch_gmm<cs, 64>(p, s) : launch_gmm<cs, 32>(p, s);
-#define U3D_GMM_CASE_BF(cs) if (cs16 == cs) rc = (R == 64) ? launch_gmm<cs, 64, 1>(p, s) : launch_gmm<cs, 32, 1>(p, s);
-#define U3D_GMM_CASE_X3(cs) if (cs16 == cs) rc = (R == 64) ? launch_gmm<cs, 64, 2>(p, s) : launch_gmm<cs, 32, 2>(p, s);
+#define U3D_GMM_CASE(cs) if (cs16 == cs) rc = (R == 64) ? launch_gmm<cs, 64>(p, s, kep) : launch_gmm<cs, 32>(p, s, kep);
+#define U3D_GMM_CASE_BF(cs) if (cs16 == cs) rc = (R == 64) ? launch_gmm<cs, 64, 1>(p, s, kep) : launch_gmm<cs, 32, 1>(p, s, kep);
+#define U3D_GMM_CASE_X3(cs) if (cs16 == cs) rc = (R == 64) ? launch_gmm<cs, 64, 2>(p, s, kep) : launch_gmm<cs, 32, 2>(p, s, kep);
     // bf16 / three-plane operands: the workgroup-tile kernel (spconv_wg.hip, weights of an offset shared through LDS) unless the
     // launch asks for per-tile statistics (wave-tile epilogue only) or u3d_conv_kernel(0) / U3D_GMM_WG=0 selected the wave-tile kernel
     // (offset groups -- the small levels -- stay on the wave-tile kernel: there the workgroup form measured level or behind)
@@ -1091,9 +1155,9 @@ static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows,
     // u3d_conv_kernel(2) takes the workgroup form wherever it is instantiated (tests, A/B runs)
     const int ck = u3d_conv_kernel(-1);
     if (pr == 3 || (pr && (ck == 2 || (ck == 1 && pr == 2 && G == 1)) && !bn_partial && gmm_wg_supported(cs16, R, pr))) {
-        rc = launch_gmm_wg(p, cs16, R, pr, s);
+        rc = launch_gmm_wg(p, cs16, R, pr, s, kep);
     } else if (!gmm_fixed_width(cs16)) {
-        rc = pr == 1 ? launch_gmm_wide<1>(p, R, s) : (pr == 2 ? launch_gmm_wide<2>(p, R, s) : launch_gmm_wide<0>(p, R, s));
+        rc = pr == 1 ? launch_gmm_wide<1>(p, R, s, kep) : (pr == 2 ? launch_gmm_wide<2>(p, R, s, kep) : launch_gmm_wide<0>(p, R, s, kep));
     } else if (pr == 1) {
         U3D_GMM_CASE_BF(2) U3D_GMM_CASE_BF(4) U3D_GMM_CASE_BF(6) U3D_GMM_CASE_BF(8) U3D_GMM_CASE_BF(10) U3D_GMM_CASE_BF(12) U3D_GMM_CASE_BF(16)
     } else if (pr == 2) {
@@ -1109,7 +1173,8 @@ static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows,
         const int64_t n4 = n_dst * Cd / 4;
         int64_t grid = ceil_div(n4, 256);
         grid = grid > 2048 ? 2048 : grid;
-        hipLaunchKernelGGL(gmm_reduce_k, dim3((unsigned)grid), dim3(256), 0, s, (const float*)ws, G, n4, addend, dst);
+        if (ep) hipLaunchKernelGGL(gmm_reduce_ep_k, dim3((unsigned)grid), dim3(256), 0, s, (const float*)ws, G, n4, addend, Cd / 4, ge);
+        else hipLaunchKernelGGL(gmm_reduce_k, dim3((unsigned)grid), dim3(256), 0, s, (const float*)ws, G, n4, addend, dst);
         rc = check_launch("gmm_reduce");
     }
     return rc;
@@ -1141,6 +1206,15 @@ int u3d_spconv_gmm_bf16a(const void* src_bf16, int64_t n_src, const void* w_rows
                          int k_groups, const float* addend, float* dst, void* ws, double flops_hint, u3d_stream_t stream) {
     return spconv_gmm_impl((const float*)src_bf16, n_src, (const float*)w_rows_bf16, gather, scatter, tile_starts, K, cap, Cs, Cd, n_dst, tile_rows,
                            k_groups, addend, dst, ws, nullptr, flops_hint, stream, 3);
+}
+
+int u3d_spconv_gmm_ep(int fmt, const void* src, int64_t n_src, const void* w_rows, const int32_t* gather, const int32_t* scatter,
+                      const int32_t* tile_starts, int K, int64_t cap, int Cs, int Cd, int64_t n_dst, int tile_rows,
+                      int k_groups, const float* addend, void* ws, float* bn_partial, const u3d_conv_epilogue* ep, double flops_hint,
+                      u3d_stream_t stream) {
+    if (fmt < 0 || fmt > 3 || !ep) { set_error("spconv_gmm_ep: fmt=%d (0 fp32, 1 bf16, 2 three planes, 3 bf16 rows) / NULL epilogue", fmt); return U3D_EINVAL; }
+    return spconv_gmm_impl((const float*)src, n_src, (const float*)w_rows, gather, scatter, tile_starts, K, cap, Cs, Cd, n_dst, tile_rows,
+                           k_groups, addend, nullptr, ws, bn_partial, flops_hint, stream, fmt, ep);
 }
 
 static int weight_pack_impl(int format, const float* w, void* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {

@@ -5,6 +5,35 @@
 
 namespace u3d {
 
+// Output epilogue of the forward launches (u3d_spconv_gmm_ep, fused inference): where the rows of dst go as they leave the LDS
+// accumulator tile (or gmm_reduce_ep_k's registers when the offsets are split over groups).  x = the fp32 value the plain launch stores.
+//   raw (nullable): x itself, into columns [raw_col, raw_col + Cd) of a buffer with leading dimension raw_ld;
+//   act[j], j < n_act <= 2: x * scale[j][c] + shift[j][c] (+ ReLU), c = the column of act[j] the value lands in (act_col[j] + dst column):
+//   a norm over a wider tensor (the U-Net's concat) is applied to its column blocks by the convolutions that produce them.
+// All leading dimensions and column offsets are multiples of 4 floats: every store is a 16-byte vector store.
+struct GmmEpilogue {
+    float* raw;
+    float* act[2];
+    const float* scale[2];
+    const float* shift[2];
+    int raw_ld, raw_col;
+    int act_ld[2], act_col[2], relu[2];
+    int n_act;
+};
+
+// one 16-byte piece of dst (row, dst columns col .. col + 3) through the epilogue
+__device__ __forceinline__ void gmm_write_out(const GmmEpilogue& ep, int64_t row, int col, const float4& v) {
+    if (ep.raw) *reinterpret_cast<float4*>(ep.raw + row * ep.raw_ld + ep.raw_col + col) = v;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {        // constant indices into the kernel argument: no private copy of the struct
+        if (j < ep.n_act) {
+            const int c = ep.act_col[j] + col;
+            const float4 sc = *reinterpret_cast<const float4*>(ep.scale[j] + c), sf = *reinterpret_cast<const float4*>(ep.shift[j] + c);
+            *reinterpret_cast<float4*>(ep.act[j] + row * ep.act_ld[j] + c) = bn_affine_relu(v, sc, sf, ep.relu[j]);
+        }
+    }
+}
+
 struct GmmParams {
     const float* src;
     const float* w;
@@ -26,6 +55,18 @@ struct GmmParams {
     int kper;
 };
 
+// Argument of the EP = true instantiations of the two kernels (fused inference; G == 1 and stats == nullptr: with offset groups the
+// plain kernels write partials as always and the epilogue runs in gmm_reduce_ep_k).  The epilogue is a TEMPLATE parameter, not a
+// branch: one kernel with a wave-uniform `if (ep.on)` in front of its write-out measured 0.1 - 0.2 ms per training step behind the
+// parent on bench.py (25.54 / 25.56 -> 25.65 / 25.63 ms and 25.65 / 25.77 -> 25.85 / 25.86 ms, two sessions: outside the parent's
+// spread) -- the descriptor's 22 dwords are loaded ahead of the main loop and held in SGPRs through it, and the register allocation
+// of the whole kernel moves.  The EP = false kernels are the parent's, instruction for instruction.
+struct GmmParamsEp : GmmParams {
+    GmmEpilogue ep;
+};
+template <bool EP> struct GmmArg { using type = GmmParams; };
+template <> struct GmmArg<true> { using type = GmmParamsEp; };
+
 constexpr int GMM_CDS = 32;            // output columns per wave
 // Accumulator tile of a wave in LDS: R rows x 32 floats.  Default layout (round 3): 128-byte rows, the eight 16-byte quads of
 // row r stored at quad ^ (r & 7) -- the XOR spreads the random-row 16-byte accesses of the MFMA read-modify-write over the
@@ -42,7 +83,7 @@ constexpr int GMM_ALD = 32;
 #endif
 
 // workgroup-tile kernel (spconv_wg.hip): pr = 1 bf16 operands, 2 three bf16 planes, 3 bf16 source rows (p.src points at bf16 [n_src][Cs]); p.n_sub counts R-row tiles
-int launch_gmm_wg(const GmmParams& p, int cs16, int R, int pr, hipStream_t s);
+int launch_gmm_wg(const GmmParams& p, int cs16, int R, int pr, hipStream_t s, const GmmEpilogue* ep = nullptr);      // ep: the EP = true kernels
 bool gmm_wg_supported(int cs16, int R, int pr);
 
 // channel-blocked weight gradient (spconv_wgrad_blk.hip): every (Cs, Cd) pair of the C ABI contract that spconv_wgrad_k (spconv.hip) has

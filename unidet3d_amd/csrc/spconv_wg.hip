@@ -370,8 +370,9 @@ struct GmmWgWave {
     }
 };
 
-template <int CS16, int R, int PR>
-__global__ __launch_bounds__(256) void spconv_gmm_wg_k(GmmParams p) {
+template <int CS16, int R, int PR, bool EP = false>
+__global__ __launch_bounds__(256) void spconv_gmm_wg_k(typename GmmArg<EP>::type pp) {
+    const GmmParams& p = pp;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using WV = GmmWgWave<CS16, R, PR>;
     constexpr int TR = 4 * R;
@@ -427,6 +428,13 @@ __global__ __launch_bounds__(256) void spconv_gmm_wg_k(GmmParams p) {
     w.ts_e = min(e, s + 16 * c1);
     w.run(k_lo);
 
+    if constexpr (EP) {                                // fused inference: raw into a wider buffer / norm + ReLU outputs
+        for (int idx = tid; idx < rows * (GMM_CDS / 4); idx += 256) {
+            const int r = idx >> 3, c4 = idx & 7;
+            gmm_write_out(pp.ep, row0 + r, n0 + c4 * 4, *reinterpret_cast<const float4*>(acc + wg_acc_idx(r, c4)));
+        }
+        return;
+    }
     float* out = p.out + (p.G > 1 ? (int64_t)g * p.n_dst * p.Cd : 0);
     for (int idx = tid; idx < rows * (GMM_CDS / 4); idx += 256) {
         const int r = idx >> 3, c4 = idx & 7;
@@ -434,20 +442,28 @@ __global__ __launch_bounds__(256) void spconv_gmm_wg_k(GmmParams p) {
     }
 }
 
-template <int CS16, int R, int PR>
-static int launch_wg(const GmmParams& p, hipStream_t s) {
+template <int CS16, int R, int PR, bool EP>
+static int launch_wg_ep(const typename GmmArg<EP>::type& p, hipStream_t s) {
     constexpr int lds = wg_lds_bytes(CS16, R, PR);
     static_assert(lds <= 160 * 1024, "workgroup tile exceeds the LDS");
     static DeviceOnce attr_set;              // the attribute is per DEVICE
     int dev = 0;
     hipGetDevice(&dev);
     if (attr_set.needed(dev)) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&spconv_gmm_wg_k<CS16, R, PR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&spconv_gmm_wg_k<CS16, R, PR, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set.done(dev);
     }
     const int64_t wgs = ceil_div(p.n_sub, 4) * p.n_slices * p.G;
-    hipLaunchKernelGGL((spconv_gmm_wg_k<CS16, R, PR>), dim3((unsigned)wgs), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((spconv_gmm_wg_k<CS16, R, PR, EP>), dim3((unsigned)wgs), dim3(256), lds, s, p);
     return check_launch("spconv_gmm_wg");
+}
+template <int CS16, int R, int PR>
+static int launch_wg(const GmmParams& p, hipStream_t s, const GmmEpilogue* ep) {
+    if (!ep) return launch_wg_ep<CS16, R, PR, false>(p, s);
+    GmmParamsEp pe;
+    static_cast<GmmParams&>(pe) = p;
+    pe.ep = *ep;
+    return launch_wg_ep<CS16, R, PR, true>(pe, s);
 }
 
 bool gmm_wg_supported(int cs16, int R, int pr) {
@@ -456,12 +472,12 @@ bool gmm_wg_supported(int cs16, int R, int pr) {
     return cs16 == 2 || cs16 == 4 || cs16 == 6 || cs16 == 8 || cs16 == 10 || cs16 == 12 || cs16 == 16;
 }
 
-int launch_gmm_wg(const GmmParams& p, int cs16, int R, int pr, hipStream_t s) {
+int launch_gmm_wg(const GmmParams& p, int cs16, int R, int pr, hipStream_t s, const GmmEpilogue* ep) {
 #define U3D_WG_CASE(cs) \
     if (cs16 == cs) { \
-        if (pr == 2) return R == 64 ? launch_wg<cs, 64, 2>(p, s) : launch_wg<cs, 32, 2>(p, s); \
-        if (pr == 3) return R == 64 ? launch_wg<cs, 64, 3>(p, s) : launch_wg<cs, 32, 3>(p, s); \
-        return R == 64 ? launch_wg<cs, 64, 1>(p, s) : launch_wg<cs, 32, 1>(p, s); \
+        if (pr == 2) return R == 64 ? launch_wg<cs, 64, 2>(p, s, ep) : launch_wg<cs, 32, 2>(p, s, ep); \
+        if (pr == 3) return R == 64 ? launch_wg<cs, 64, 3>(p, s, ep) : launch_wg<cs, 32, 3>(p, s, ep); \
+        return R == 64 ? launch_wg<cs, 64, 1>(p, s, ep) : launch_wg<cs, 32, 1>(p, s, ep); \
     }
     U3D_WG_CASE(2) U3D_WG_CASE(4) U3D_WG_CASE(6) U3D_WG_CASE(8) U3D_WG_CASE(10) U3D_WG_CASE(12) U3D_WG_CASE(16)
 #undef U3D_WG_CASE

@@ -50,6 +50,15 @@ __device__ __forceinline__ int64_t xcd_swizzle(int64_t b, int64_t n) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
+// Batch norm as an affine map (+ ReLU) of four channels: THE expression of bn_apply_k (bn.hip) and of the convolution epilogues
+// that write a norm's result on the way out of their accumulator tile (spconv_gmm.h gmm_write_out) -- one definition, so both
+// contract and round alike and return the same bits.
+__device__ __forceinline__ float4 bn_affine_relu(const float4& v, const float4& sc, const float4& sf, int relu) {
+    float4 o = make_float4(v.x * sc.x + sf.x, v.y * sc.y + sf.y, v.z * sc.z + sf.z, v.w * sc.w + sf.w);
+    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+    return o;
+}
+
 // ---- raw buffer loads (32-bit offsets from a scalar base: one VALU instruction or none per address) ------------------
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;

@@ -15,7 +15,8 @@ PyTorch fallback.  Rows must be in canonical order (ascending
 produce.
 
 What a layer leaves for the next one rides on the feature TENSOR (bf16 shadow, ``_u3d_from_conv``, the batch-norm statistics of a
-convolution's epilogue: ``shadow_of`` / ``stats_of``); ``SparseConvTensor`` carries geometry only.  A norm on a sparse tensor is one
+convolution's epilogue, in inference the norm's whole result: ``shadow_of`` / ``stats_of`` / ``activated_of``); ``SparseConvTensor``
+carries geometry only (and, in its ``indice_dict``, the ``FusionRun`` of a forward on the fused inference path).  A norm on a sparse tensor is one
 call, ``SparseBatchNorm.on``; a convolution layer is: find the geometry, ``_ConvBase._conv``, build the output tensor.
 """
 from __future__ import annotations
@@ -317,6 +318,26 @@ def stats_of(t: torch.Tensor):
     return None
 
 
+# ---- batch norm + ReLU from the convolution epilogue (fused inference) ---------------------------------------------------------
+# The activated tensor(s) a convolution launch wrote for the norm(s) behind it travel the same way, keyed by the norm module: a norm in
+# inference finds its own entry on exactly the tensor it is called on and returns it without a launch.
+def attach_activated(t: torch.Tensor, norm, y: torch.Tensor, relu: bool):
+    e = getattr(t, '_u3d_act', None)
+    if e is None or e[0] != t._version:
+        e = t._u3d_act = (t._version, {})
+    e[1][norm] = (y, bool(relu))
+
+
+def activated_of(t: torch.Tensor, norm, relu: bool):
+    """``norm``(t) (+ ReLU as ``relu`` says) as the producing convolution(s) wrote it, or None"""
+    e = getattr(t, '_u3d_act', None)
+    if e is not None and e[0] == t._version:
+        hit = e[1].get(norm)
+        if hit is not None and hit[1] == bool(relu) and hit[0].device == t.device:
+            return hit[0]
+    return None
+
+
 # ---- all weight packs of a model in one launch ------------------------------------------------------------------------------
 _PACKED: Dict = {}          # (weight data_ptr, transposed, bf16) -> (buffer, weight tensor, version at pack time)
 
@@ -440,6 +461,40 @@ def _flag_toggle(name: str):
 set_conv_ts, conv_ts = _flag_toggle('_CONV_TS')
 set_conv_rs, conv_rs = _flag_toggle('_CONV_RS')
 set_conv_rs_bf16, conv_rs_bf16 = _flag_toggle('_CONV_RS_BF16')
+# Fused inference: in eval mode under torch.no_grad() the pair-list convolutions write the batch norm + ReLU of the
+# norm(s) that read their result on the way out of the LDS tile (u3d_spconv_gmm_ep), and the U-Net's concat buffer directly.  Same bits
+# as the unfused path.  Three states: None (the default) = on, except under ``precision.bf16_rows`` -- there inference keeps gathering the
+# bf16 shadows u3d_bn_apply writes (the epilogue writes none; tests/test_gpu_bf16.py pins that data flow); True = on everywhere (under
+# bf16_rows the fused launches gather fp32 rows and round them: same bits, measured faster); False = off.
+# U3D_FUSED_INFERENCE=1 / 0, set_fused_inference(True / False / None).
+_FUSED_INFERENCE = {'1': True, '0': False}.get(os.environ.get('U3D_FUSED_INFERENCE', ''))
+
+
+def set_fused_inference(on):
+    """True / False / None (module comment above); returns the previous state"""
+    global _FUSED_INFERENCE
+    prev, _FUSED_INFERENCE = _FUSED_INFERENCE, None if on is None else bool(on)
+    return prev
+
+
+@contextlib.contextmanager
+def fused_inference(on):
+    prev = set_fused_inference(on)
+    try:
+        yield
+    finally:
+        set_fused_inference(prev)
+
+
+def fused_inference_on() -> bool:
+    return (not P.bf16_rows()) if _FUSED_INFERENCE is None else _FUSED_INFERENCE
+
+
+def fusion_active(*modules) -> bool:
+    """The one condition of the fused inference path: toggle on, no autograd, none of ``modules`` in training mode, and none of the
+    experimental kernels ('rs' / 'ts' / 'rsb') selected -- ``_conv_route`` then sends every convolution to the pair-list kernels."""
+    return (fused_inference_on() and not torch.is_grad_enabled() and not (_CONV_TS or _CONV_RS or _CONV_RS_BF16)
+            and not any(m.training for m in modules))
 
 
 def _ts_plan(Cs, Cd, n):
@@ -642,6 +697,103 @@ def sparse_conv(src, weight, rb, mode='fwd', addend=None, want_stats=False):
     return dst
 
 
+def sparse_conv_fused(src, weight, rb, mode, addend, raw, acts):
+    """Forward convolution of the fused inference path (no autograd): u3d_spconv_gmm_ep.
+    ``raw``: (fp32 buffer [n_dst, ld], first column) that receives dst, or None for no raw output; ``acts``: up to two
+    (buffer [n_dst, ld], first column, scale, shift, relu) that receive relu(dst * scale + shift) -- scale / shift indexed by the buffer's
+    own columns.  Same kernel, operand format and offset groups as ``_gmm`` takes for this shape, so dst has the bits ``sparse_conv``
+    returns.  Under ``precision.bf16_rows`` a source without a bf16 shadow that a fused launch activated (``_u3d_fused_act``) is gathered
+    as fp32 rows and rounded as the operand is formed, under the plan of the bf16-row kernel the unfused path would have run on its
+    shadow: same values, same offset groups, same sums."""
+    cout, cin = weight.shape[0], weight.shape[-1]
+    w = weight.reshape(cout, rb.K, cin).contiguous()
+    src = src.contiguous()
+    g, s, role, n_dst = _roles(rb, mode)
+    if not n_dst:
+        return
+    flops = 2.0 * rb.total_pairs * cin * cout if _PROFILE_FLOPS else 0.0
+    bf = P.conv_format()
+    shadow = shadow_of(src) if bf == P.FMT_BF16 and P.bf16_rows() and cin % 32 == 0 else None
+    route, fmt, plan = _conv_route(cin, cout, n_dst, rb, bf, shadow is not None, False)
+    if route != 'pairs':
+        raise L.U3DError(f'fused inference: the {route!r} kernel has no output epilogue')
+    R, G, rows = plan
+    if (fmt == P.FMT_BF16 and not rows and P.bf16_rows() and getattr(src, '_u3d_fused_act', False)
+            and L.lib().u3d_spconv_gmm_bf16a_supported(cin, cout)):
+        R, G = _plan(cin, cout, rb.K, n_dst, True)
+    if _PROFILE_FLOPS:
+        account.add('conv_gmm', flops, 4.0 * (src.shape[0] * cin + n_dst * cout) + 8.0 * rb.total_pairs + 4.0 * rb.K * cin * cout)
+    wp = _packed_weight(w, False, fmt, cout, rb.K, cin, src.device)
+    ep = L.ConvEpilogue()
+    if raw is not None:
+        ep.raw, ep.raw_ld, ep.raw_col = raw[0].data_ptr(), raw[0].shape[1], raw[1]
+    ep.n_act = len(acts)
+    for j, (buf, col, scale, shift, relu) in enumerate(acts):
+        ep.act[j], ep.act_ld[j], ep.act_col[j] = buf.data_ptr(), buf.shape[1], col
+        ep.scale[j], ep.shift[j], ep.relu[j] = L.ptr(scale), L.ptr(shift), int(relu)
+    ws = torch.empty(G * n_dst * cout, dtype=torch.float32, device=src.device) if G > 1 else None
+    tiles = rb.tile_starts(role, R)
+    L.call('u3d_spconv_gmm_ep', 3 if rows else fmt, L.ptr(shadow if rows else src), src.shape[0], L.ptr(wp), L.ptr(g), L.ptr(s), L.ptr(tiles),
+           rb.K, rb.cap, cin, cout, n_dst, R, G, L.ptr(None if addend is None else addend.contiguous()), L.ptr(ws), None, ctypes.byref(ep),
+           float(flops), L.stream())
+
+
+FUSE_KEY = '__fused_inference__'       # indice_dict entry of a forward on the fused inference path: its FusionRun
+
+
+class FusionRun:
+    """One forward pass on the fused inference path: the plan (``spconv_unet.fusion_plan``: which norm(s) read each convolution's
+    result, which column block of a U-Net concat buffer it writes) and the buffers of this pass.  It rides in the ``indice_dict`` all
+    sparse tensors of a forward share; ``_ConvBase._conv`` looks its layer up there."""
+
+    def __init__(self, plan):
+        self.plan = plan
+        self.cats: Dict = {}
+        self.used = False                  # set when the planned U-Net starts its forward: a pass's buffers are never handed out twice
+
+    def cat(self, owner, n: int, device):
+        """(raw, activated) [n, 2c] buffers of U-Net level ``owner``: the concatenation its tail blocks read, and the first tail norm of it"""
+        if owner not in self.cats:
+            width = self.plan.cats[owner].width
+            self.cats[owner] = tuple(torch.empty(n, width, dtype=torch.float32, device=device) for _ in range(2))
+        return self.cats[owner]
+
+    def conv(self, layer, cp, x: 'SparseConvTensor', rb: Rulebook, mode: str, addend=None) -> torch.Tensor:
+        src, weight = _pad16(x.features), layer._w16()
+        n_dst, Cd, dev = _roles(rb, mode)[3], layer.out_channels, src.device
+        if cp.raw is None:                 # only the norm behind this layer reads the result
+            raw, dst = None, torch.empty(0, Cd, dtype=torch.float32, device=dev)
+            dst._u3d_no_raw = True
+        elif cp.raw == 'own':
+            dst = torch.empty(n_dst, Cd, dtype=torch.float32, device=dev)
+            raw = (dst, 0)
+        else:
+            buf = self.cat(cp.raw[0], n_dst, dev)[0]
+            raw, dst = (buf, cp.raw[1]), buf[:, cp.raw[1]:cp.raw[1] + Cd]
+        acts, own = [], []
+        for norm, relu, where in cp.acts:
+            scale, shift = norm.eval_affine()
+            if where is None:
+                y = torch.empty(n_dst, Cd, dtype=torch.float32, device=dev)
+                y._u3d_fused_act = True
+                acts.append((y, 0, scale, shift, relu))
+                own.append((norm, y, relu))
+            else:
+                acts.append((self.cat(where[0], n_dst, dev)[1], where[1], scale, shift, relu))
+        sparse_conv_fused(src, weight, rb, mode, addend, raw, acts)
+        for norm, y, relu in own:
+            attach_activated(dst, norm, y, relu)
+        return dst
+
+    def concat(self, owner, n: int, device) -> torch.Tensor:
+        """The concatenation of level ``owner`` after both producers ran, with its first tail norm's result attached"""
+        buf, act = self.cat(owner, n, device)
+        c = self.plan.cats[owner]
+        act._u3d_fused_act = True
+        attach_activated(buf, c.norm, act, c.relu)
+        return buf
+
+
 # ----------------------------------------------------------------------------------------
 # batch norm (+ReLU)
 # ----------------------------------------------------------------------------------------
@@ -664,13 +816,17 @@ class _BNReLUFn(torch.autograd.Function):
         eps, momentum, relu, training, sync, want_skip, and
         ``nbt``: num_batches_tracked where the statistics kernel is to increment it, else None;
         ``stats``: (partial, n_tiles) from the epilogue of the convolution that produced x (``stats_of``), or None;
+        ``affine``: the [4, C] rows mean | invstd | scale | shift of the running statistics (eval mode: computed once per parameter
+        version, ``SparseBatchNorm.eval_affine``), or None;
         ``yb`` (bf16 [n, C] or None): receives y rounded to bf16 in the same pass (precision.bf16_rows); ``dx_shadow``: the backward
         writes such a copy of dx too and attaches it to the gradient it returns (x came out of a sparse convolution)."""
         x = x.contiguous()
         n, C = x.shape
         dev = x.device
         relu, yb, nbt = int(cfg.relu), cfg.yb, cfg.nbt
-        st = torch.empty(4, C, dtype=torch.float32, device=dev)     # mean, invstd, scale, shift
+        # mean, invstd, scale, shift: in inference the module's cached rows (``SparseBatchNorm.eval_affine``), never written here
+        cached = cfg.affine is not None and not cfg.training and cfg.affine.device == dev
+        st = cfg.affine if cached else torch.empty(4, C, dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
         ws = L.scratch(L.lib().u3d_bn_ws_bytes(C), dev)
         part, n_tiles = cfg.stats or (None, 0)
@@ -689,7 +845,7 @@ class _BNReLUFn(torch.autograd.Function):
                 allreduce_bn_sums(sums)           # rows ride along: no host read-back on the critical path
                 L.call('u3d_bn_finalize', L.ptr(sums), -1.0, L.ptr(gamma), L.ptr(beta), cfg.eps, cfg.momentum, L.ptr(running_mean),
                        L.ptr(running_var), C, L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), L.ptr(nbt), L.stream())
-            else:                                 # the running statistics
+            elif not cached:                      # the running statistics
                 st[0] = running_mean
                 st[1] = torch.rsqrt(running_var + cfg.eps)
                 st[2] = gamma * st[1]
@@ -757,6 +913,8 @@ class SparseBatchNorm(nn.Module):
     ``sync=True`` all-reduces the statistics across ranks when a process group exists
     (nn.SyncBatchNorm degenerates to plain batch norm without one -- SURVEY.md 2.3)."""
 
+    _affine_cache = None        # eval-mode (scale, shift) rows, ``_eval_rows``
+
     def __init__(self, num_features, eps=1e-4, momentum=0.1, sync=True):
         super().__init__()
         self.num_features, self.eps, self.momentum, self.sync = num_features, eps, momentum, sync
@@ -765,20 +923,62 @@ class SparseBatchNorm(nn.Module):
         self.register_buffer('running_mean', torch.zeros(num_features))
         self.register_buffer('running_var', torch.ones(num_features))
         self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
+        self._affine_cache = None
+
+    def _eval_rows(self):
+        """(key, st [4, C] = mean | invstd | scale | shift, (scale, shift)) of the running statistics, by exactly the torch expressions
+        the eval arm of ``_BNReLUFn.forward`` evaluates; recomputed when ``_version`` (or the storage) of weight, bias, running_mean or
+        running_var changed.  What changes them behind ``_version``'s back is covered the way ``WeightPacks`` covers it: a training-mode
+        forward (the statistics kernels update the running buffers in place) drops the rows, and rows computed while an optimizer may be
+        stepping weight / bias (autograd enabled, either requires a gradient: fused AdamW leaves ``_version`` alone) are used once and
+        recomputed by the next call.  Other writers that bypass ``_version`` (``.data``): ``invalidate_affine`` /
+        ``UniDet3D.invalidate_weight_packs``."""
+        src = (self.weight, self.bias, self.running_mean, self.running_var)
+        # (rows made under torch.inference_mode() cannot be saved for a later backward pass: they are not shared across that boundary)
+        key = tuple((t._version, t.data_ptr()) for t in src) + (float(self.eps), str(self.running_var.device), torch.is_inference_mode_enabled())
+        c = getattr(self, '_affine_cache', None)
+        tuned = torch.is_grad_enabled() and (self.weight.requires_grad or self.bias.requires_grad)
+        if c is None or c[0] != key or c[3] or tuned:
+            with torch.no_grad():
+                st = torch.empty(4, self.running_var.shape[0], dtype=torch.float32, device=self.running_var.device)
+                st[0] = self.running_mean
+                st[1] = torch.rsqrt(self.running_var + self.eps)
+                st[2] = self.weight * st[1]
+                st[3] = self.bias - self.running_mean * st[2]
+            c = self._affine_cache = (key, st, (st[2], st[3]), tuned)
+        return c
+
+    def eval_affine(self):
+        """The cached (scale, shift) of inference: y = x * scale + shift.  The same two tensors until a parameter or buffer changes."""
+        return self._eval_rows()[2]
+
+    def invalidate_affine(self):
+        self._affine_cache = None
 
     def forward(self, x: torch.Tensor, relu: bool = False, skip: bool = False, shadow: bool = True):
         """``skip=True`` -> (y, x_id): ``x_id`` is x for a second consumer (the identity branch next to this norm); the gradient that
         consumer sends back is added to dx inside this layer's backward kernel.
+        In inference (eval mode under ``torch.no_grad()``) the result the producing convolution's epilogue attached for this norm to
+        exactly this ``x`` (``activated_of``) is returned where there is one: no launch.
         In training mode the per-tile column sums the producing convolution's epilogue attached to exactly this ``x`` (``stats_of``)
         are used where there are any: the statistics then cost no pass over x."""
         # bf16 operands with bf16 rows in HBM (precision.bf16_rows): y (when a ReLU follows -- the input of a sparse convolution -- and
         # the channel count suits the bf16 kernels) and the gradient handed back to a producing convolution get a bf16 shadow
+        if self.training and self._affine_cache is not None:
+            self._affine_cache = None       # the running statistics (and, by the optimizer, weight and bias) move without a ``_version`` bump
+        if not self.training and not torch.is_grad_enabled():
+            # fused inference: the convolution(s) that produced x wrote this norm's result already (``attach_activated``)
+            y = activated_of(x, self, relu)
+            if y is not None:
+                return (y, x) if skip else y
+            if getattr(x, '_u3d_no_raw', False):
+                raise L.U3DError('SparseBatchNorm: the producing convolution wrote no raw output and nothing for this norm')
         rows = P.bf16_rows() and x.is_cuda and x.shape[0] > 0 and x.shape[1] % 32 == 0
         yb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if rows and relu and shadow else None
         # num_batches_tracked is incremented by the statistics kernel (one launch less per layer)
         cfg = SimpleNamespace(eps=self.eps, momentum=self.momentum, relu=relu, training=self.training, sync=self.sync, want_skip=skip,
                               nbt=self.num_batches_tracked if self.training and (x.shape[0] or (self.sync and _dist_on())) else None,
-                              stats=stats_of(x) if self.training else None, yb=yb, dx_shadow=bool(rows and getattr(x, '_u3d_from_conv', False)))
+                              stats=stats_of(x) if self.training else None, affine=None if self.training else self._eval_rows()[1], yb=yb, dx_shadow=bool(rows and getattr(x, '_u3d_from_conv', False)))
         out = _BNReLUFn.apply(cfg, x, self.weight, self.bias, self.running_mean, self.running_var)
         if yb is not None:
             attach_shadow(out[0] if skip else out, yb)
@@ -893,7 +1093,13 @@ class _ConvBase(SparseModule):
         return self.weight if c % 16 == 0 else F.pad(self.weight, (0, 16 - c % 16))
 
     def _conv(self, x: 'SparseConvTensor', rb: Rulebook, mode: str, addend=None) -> torch.Tensor:
-        """pad -> sparse_conv -> result features; in training mode with the statistics for a norm behind this layer asked for"""
+        """pad -> sparse_conv -> result features; in training mode with the statistics for a norm behind this layer asked for.
+        On the fused inference path (a ``FusionRun`` in the tensor's ``indice_dict`` that plans this layer, ``fusion_active``) the
+        launch writes the result of the norm(s) behind this layer as well, and the result itself where the plan says."""
+        run = x.indice_dict.get(FUSE_KEY)
+        cp = run.plan.convs.get(self) if run is not None else None
+        if cp is not None and fusion_active(self, *(a[0] for a in cp.acts)):
+            return run.conv(self, cp, x, rb, mode, addend)
         return sparse_conv(_pad16(x.features), self._w16(), rb, mode, addend, self.training)
 
 

@@ -11,15 +11,19 @@ HIP kernels through include/u3d.h, BN+ReLU is one fused kernel, and the residual
 convolution.  A norm that does not sit in a ``SparseSequential`` of its own (the two of a block, the one the U-Net's skip
 connection leaves next to) runs through ``SparseBatchNorm.on``, which also says that a convolution reads the result; what a
 convolution leaves for the norm behind it travels on the feature tensor (``sparse.stats_of``), not through these classes.
+In inference (``eval()`` under ``torch.no_grad()``) the convolutions write the norms behind them and the concat buffers themselves:
+``fusion_plan`` says which convolution writes which norm, ``begin_fusion`` starts such a pass.
 """
 from __future__ import annotations
 
 import functools
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 from torch import nn
 
+from . import sparse as S
 from ._lib import U3DError
 from .registry import MODELS
 from .sparse import (SparseBatchNorm, SparseConv3d, SparseConvTensor, SparseInverseConv3d, SparseModule,
@@ -65,6 +69,181 @@ class ResidualBlock(SparseModule):
         return mods[5](x, addend=skip)          # conv + residual in one kernel
 
 
+# ----------------------------------------------------------------------------------------
+# fused inference: which convolution writes which norm
+# ----------------------------------------------------------------------------------------
+class FusionPlan:
+    """Successor plan of a pre-activation U-Net for the fused inference path.  Pure bookkeeping (no tensors):
+      ``norms``  SparseBatchNorm -> (name, relu, producers [(convolution, first column, end column)], fused); no producers = unfused:
+                 that norm runs u3d_bn_apply as always;
+      ``convs``  convolution -> (raw, acts): raw = 'own' (a tensor of its own), None (nobody reads the raw result) or (level, first
+                 column) of that U-Net level's concat buffer; acts = up to two (norm, relu, None | (level, first column)): the activated
+                 tensor of its own, or a column block of the level's activated concat buffer;
+      ``cats``   U-Net level -> (width 2c, the first tail norm, relu): the two [n, 2c] buffers ``sparse.FusionRun`` allocates."""
+
+    def __init__(self, root):
+        self.root = root
+        self.norms: OrderedDict = OrderedDict()
+        self.convs = {}
+        self.cats = {}
+        self.names = {}
+
+    def conv(self, m):
+        if m not in self.convs:
+            self.convs[m] = SimpleNamespace(raw='own', acts=[])
+        return self.convs[m]
+
+    def norm(self, m, relu, producers):
+        assert m not in self.norms
+        self.norms[m] = SimpleNamespace(relu=bool(relu), producers=list(producers), fused=bool(producers))
+
+    def feed(self, conv, norm, relu, lo, hi, where=None):
+        """``conv`` writes columns [lo, hi) of ``norm``'s result"""
+        self.conv(conv).acts.append((norm, bool(relu), where))
+        if norm in self.norms:
+            self.norms[norm].producers.append((conv, lo, hi))
+            self.norms[norm].fused = True
+        else:
+            self.norm(norm, relu, [(conv, lo, hi)])
+
+    @property
+    def modules(self):
+        return [*self.convs, *self.norms]
+
+    def name(self, m):
+        return self.names.get(m, type(m).__name__)
+
+    def describe(self):
+        """{norm name: [(producer name, first column, end column)]} ([] = unfused) and {convolution name: (raw, [norm names])}"""
+        norms = OrderedDict((self.name(n), [(self.name(c), lo, hi) for c, lo, hi in e.producers]) for n, e in self.norms.items())
+        convs = {self.name(c): (e.raw if not isinstance(e.raw, tuple) else (self.name(e.raw[0]), e.raw[1]),
+                                [(self.name(a[0]), None if a[2] is None else (self.name(a[2][0]), a[2][1])) for a in e.acts])
+                 for c, e in self.convs.items()}
+        return norms, convs
+
+
+def _pre_act_block(b):
+    """(norm1, conv1, norm2, conv2) of a pre-activation ResidualBlock, or None for anything else"""
+    if type(b) is not ResidualBlock or not b.normalize_before:
+        return None
+    m = list(b.conv_branch._modules.values())
+    ok = len(m) == 6 and all(isinstance(m[i], SparseBatchNorm) and isinstance(m[i + 1], nn.ReLU) and isinstance(m[i + 2], SubMConv3d)
+                             and m[i + 2].kernel_size == 3 for i in (0, 3))
+    return (m[0], m[2], m[3], m[5]) if ok else None
+
+
+def _norm_relu_conv(seq, conv_type):
+    m = list(seq._modules.values()) if isinstance(seq, SparseSequential) else []
+    if len(m) == 3 and isinstance(m[0], SparseBatchNorm) and isinstance(m[1], nn.ReLU) and isinstance(m[2], conv_type):
+        return m[0], m[2]
+    return None
+
+
+def _plan_level(plan, u, feed, sink):
+    """``feed``: the convolution whose result is this level's input (None: unknown); ``sink``: (norm, relu) that reads this level's
+    output (None: none known).  False where the level is not the pre-activation structure."""
+    c = u.num_planes[0]
+
+    def chain(blocks, prod, width):
+        for b in blocks:
+            parts = _pre_act_block(b)
+            if parts is None:
+                return False, None
+            n1, conv1, n2, conv2 = parts
+            if n1 in plan.norms:              # the first tail norm: planned with its two producers
+                pass
+            elif prod is None:
+                plan.norm(n1, True, [])       # nobody known to produce its input: unfused
+            else:
+                plan.feed(prod, n1, True, 0, width)
+            plan.conv(conv1).raw = None       # only norm 2 reads conv 1
+            plan.feed(conv1, n2, True, 0, conv1.out_channels)
+            plan.conv(conv2)
+            prod, width = conv2, conv2.out_channels
+        return True, prod
+
+    blocks = list(u.blocks._modules.values())
+    if not blocks:
+        return False
+    ok, prod = chain(blocks, feed, c)
+    if not ok:
+        return False
+    if len(u.num_planes) > 1:
+        down, up = _norm_relu_conv(u.conv, SparseConv3d), _norm_relu_conv(u.deconv, SparseInverseConv3d)
+        tail = list(u.blocks_tail._modules.values())
+        if down is None or up is None or not tail or _pre_act_block(tail[0]) is None:
+            return False
+        tnorm = _pre_act_block(tail[0])[0]
+        plan.cats[u] = SimpleNamespace(width=2 * c, norm=tnorm, relu=True)
+        # the last convolution of ``blocks``: raw -> concat columns [0, c); the norm in front of the down convolution; the first tail
+        # norm's columns [0, c)
+        plan.conv(prod).raw = (u, 0)
+        plan.feed(prod, down[0], True, 0, c)
+        plan.feed(prod, tnorm, True, 0, c, (u, 0))
+        if not _plan_level(plan, u.u, down[1], (up[0], True)):
+            return False
+        # the inverse convolution: raw and the first tail norm, columns [c, 2c)
+        plan.conv(up[1]).raw = (u, c)
+        plan.feed(up[1], tnorm, True, c, 2 * c, (u, c))
+        ok, prod = chain(tail, None, 2 * c)
+        if not ok:
+            return False
+    if sink is not None:
+        plan.feed(prod, sink[0], sink[1], 0, c)
+    return True
+
+
+def fusion_plan(unet, first_producer=None, last_consumer=None) -> FusionPlan:
+    """Which convolution writes which norm on the fused inference path (pure Python, cached on ``unet``).
+    ``first_producer``: the convolution (or a SparseSequential ending in one) whose result is the U-Net's input;
+    ``last_consumer``: the norm that reads the U-Net's output -- a SparseSequential starting with it tells whether a ReLU follows, a bare
+    SparseBatchNorm is taken without one.  U-Nets with ``normalize_before=False`` or foreign block classes get an EMPTY plan: the
+    current path.  A convolution has at most two activated outputs; a norm that would be a third stays unfused (none in this U-Net)."""
+    key = (id(first_producer), id(last_consumer), tuple(id(m) for m in unet.modules()))
+    hit = unet.__dict__.get('_u3d_fusion_plan')
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    plan = FusionPlan(unet)
+    feed = sink = None
+    if isinstance(first_producer, SparseSequential) and len(first_producer):
+        first_producer = first_producer[len(first_producer) - 1]
+    if isinstance(first_producer, S._ConvBase) and first_producer.kernel_size != 1:
+        feed = first_producer
+        plan.names[feed] = '<first_producer>'
+    if isinstance(last_consumer, SparseSequential) and len(last_consumer) and isinstance(last_consumer[0], SparseBatchNorm):
+        sink = (last_consumer[0], len(last_consumer) > 1 and isinstance(last_consumer[1], nn.ReLU))
+    elif isinstance(last_consumer, SparseBatchNorm):
+        sink = (last_consumer, False)
+    if sink is not None:
+        plan.names[sink[0]] = '<last_consumer>'
+    for name, m in unet.named_modules():
+        plan.names[m] = name or '<unet>'
+    if not _plan_level(plan, unet, feed, sink):
+        plan = FusionPlan(unet)
+    for conv, e in plan.convs.items():          # at most two activated outputs per launch
+        for norm, _, _ in e.acts[2:]:
+            plan.norms[norm].producers, plan.norms[norm].fused = [], False
+        del e.acts[2:]
+    for cat in plan.cats.values():              # (a concat norm that lost a producer above cannot be assembled)
+        assert plan.norms[cat.norm].fused and len(plan.norms[cat.norm].producers) == 2
+    unet.__dict__['_u3d_fusion_plan'] = (key, plan)
+    return plan
+
+
+def begin_fusion(x: SparseConvTensor, unet, first_producer=None, last_consumer=None) -> bool:
+    """Announce a forward pass over ``first_producer`` -> ``unet`` -> ``last_consumer`` on the sparse tensor ``x`` that enters it: where
+    the fused inference path applies (``sparse.fusion_active`` for every planned layer) the pass's ``sparse.FusionRun`` is put into
+    ``x.indice_dict``, where the layers find it; otherwise any earlier one is removed and every call is the current one."""
+    x.indice_dict.pop(S.FUSE_KEY, None)
+    if not S.fused_inference_on() or torch.is_grad_enabled():
+        return False
+    plan = fusion_plan(unet, first_producer, last_consumer)
+    if not plan.convs or not S.fusion_active(*plan.modules, *plan.cats):
+        return False
+    x.indice_dict[S.FUSE_KEY] = S.FusionRun(plan)
+    return True
+
+
 POOL_WIDTHS = (32, 64, 128, 256)       # channel counts the superpoint pooling that reads the U-Net's output is built for (ops.superpoint_pool)
 
 
@@ -84,6 +263,7 @@ class SpConvUNet(nn.Module):
     def __init__(self, num_planes, use_sync_bn=True, block_reps=2, block=ResidualBlock, indice_key_id=1,
                  normalize_before=True, return_blocks=False, *, _inner=False):
         super().__init__()
+        self._outer = not _inner
         self.return_blocks = return_blocks
         self.num_planes = list(num_planes)
         if not _inner:                     # the outermost U-Net checks the whole list (an inner level's first plane is not pooled)
@@ -134,6 +314,14 @@ class SpConvUNet(nn.Module):
             self.u.prepare_geometry(SparseConvTensor(None, oc, oshape, x.batch_size, x.indice_dict, ix2))
 
     def forward(self, input: SparseConvTensor, previous_outputs=None):
+        run = input.indice_dict.get(S.FUSE_KEY)
+        if getattr(self, '_outer', False):
+            if run is None or run.plan.root is not self or run.used:      # not announced by the caller (begin_fusion), or an earlier pass's
+                begin_fusion(input, self)
+                run = input.indice_dict.get(S.FUSE_KEY)
+            if run is not None:
+                run.used = True
+        fused_cat = run is not None and self in run.plan.cats and S.fusion_active(self)
         output = self.blocks(input)
         identity = output
         if len(self.num_planes) > 1:
@@ -148,7 +336,10 @@ class SpConvUNet(nn.Module):
             else:
                 dec = self.u(dec)
             dec = self.deconv(dec)
-            output = output.replace_feature(torch.cat((identity.features, dec.features), dim=1))
+            if fused_cat:      # both producers wrote their column block of the concatenation, and of the first tail norm of it
+                output = output.replace_feature(run.concat(self, output.features.shape[0], output.features.device))
+            else:
+                output = output.replace_feature(torch.cat((identity.features, dec.features), dim=1))
             output = self.blocks_tail(output)
         if self.return_blocks:
             if previous_outputs is None:

@@ -27,6 +27,7 @@ from torch import nn
 from . import dense, ops
 from .registry import MODELS
 from .sparse import SparseBatchNorm, SparseConvTensor, SparseSequential, SubMConv3d
+from .spconv_unet import SpConvUNet, begin_fusion
 from .structures import DepthInstance3DBoxes, InstanceData_
 
 
@@ -133,6 +134,10 @@ class UniDet3D(nn.Module):
             from .sparse import WeightPacks
             self._packs = WeightPacks(self)
         self._packs.refresh()                 # all convolution weights -> MFMA fragment order in one launch, when they changed
+        if isinstance(self.unet, SpConvUNet):
+            # inference: the convolutions write the batch norm + ReLU behind them and the concat buffers; the input
+            # convolution produces the first block's norm, the output layer's norm reads the last convolution
+            begin_fusion(x, self.unet, self.input_conv, self.output_layer)
         x = self.input_conv(x)
         x, _ = self.unet(x)
         x = self.output_layer(x)
@@ -417,9 +422,14 @@ class UniDet3D(nn.Module):
 
     def invalidate_weight_packs(self):
         """For code that writes convolution weights through ``.data`` (which does not bump ``Tensor._version``; e.g. an EMA
-        parameter swap) while the model is in eval mode: the MFMA-order weight copies are rebuilt at the next forward."""
+        parameter swap) while the model is in eval mode: the MFMA-order weight copies are rebuilt at the next forward.  The same holds
+        for ``.data`` writers of batch-norm parameters and running statistics: the eval-mode (scale, shift) every ``SparseBatchNorm``
+        caches by ``Tensor._version`` (``eval_affine``) is dropped here too."""
         if self._packs is not None:
             self._packs.invalidate()
+        for m in self.modules():
+            if isinstance(m, SparseBatchNorm):
+                m.invalidate_affine()
 
     def prefetch_step(self, data):
         """``prefetch`` for loops that drive the model through ``train_step``: preprocess the NEXT raw batch (host -> device copies
