@@ -26,6 +26,34 @@ struct BnFin {
     int64_t* nbt;
 };
 
+// Channel c's layer constants (mean / invstd / scale / shift, running statistics) from its two fp64 sums: the ONE definition behind
+// bn_sum_k (u3d_bn_forward) and bn_finalize_k (the split path of SyncBatchNorm).  Every fp32 step is spelled out -- shift as one fused
+// multiply-add, the running statistics as two products and a sum -- and contraction is off for the rest, so that both kernels return
+// the same bits: left to the compiler, bn_finalize_k fused the running variance's update and bn_sum_k did not.
+__device__ __forceinline__ void bn_finalize_channel(double s1, double s2, double rows, const float* gamma, const float* beta, float eps,
+                                                    float momentum, float* running_mean, float* running_var, float* mean, float* invstd,
+                                                    float* scale, float* shift, int c) {
+#pragma clang fp contract(off)
+    const double m = s1 / rows;
+    double var = fma(-m, m, s2 / rows);
+    if (var < 0.0) var = 0.0;
+    const float is = (float)(1.0 / sqrt(var + (double)eps));
+    const float mf = (float)m;
+    mean[c] = mf;
+    invstd[c] = is;
+    const float sc = gamma[c] * is;
+    scale[c] = sc;
+    shift[c] = fmaf(-mf, sc, beta[c]);
+    if (running_mean) {
+        const double unbiased = rows > 1.0 ? var * rows / (rows - 1.0) : var;
+        const float keep = 1.f - momentum;
+        const float km = keep * running_mean[c], kv = keep * running_var[c];
+        const float nm = momentum * mf, nv = momentum * (float)unbiased;
+        running_mean[c] = km + nm;
+        running_var[c] = kv + nv;
+    }
+}
+
 // channels c = wave0, wave0 + nw, ...: one wave per channel, lanes over the partial rows, fixed shuffle tree
 __device__ __forceinline__ void bn_finish_body(const double* partial, int nblk, int C, const BnFin& f, int wave0, int nw, bool first) {
     const int lane = threadIdx.x & 63;
@@ -41,21 +69,8 @@ __device__ __forceinline__ void bn_finish_body(const double* partial, int nblk, 
         f.sums[c] = t1;
         f.sums[C + c] = t2;
         if (!f.st) continue;
-        const double m = t1 / f.rows;
-        double var = t2 / f.rows - m * m;
-        if (var < 0.0) var = 0.0;
-        const float is = (float)(1.0 / sqrt(var + (double)f.eps));
-        const float mf = (float)m;
-        f.st[c] = mf;
-        f.st[C + c] = is;
-        const float sc = f.gamma[c] * is;
-        f.st[2 * C + c] = sc;
-        f.st[3 * C + c] = f.beta[c] - mf * sc;
-        if (f.running_mean) {
-            const double unbiased = f.rows > 1.0 ? var * f.rows / (f.rows - 1.0) : var;
-            f.running_mean[c] = (1.f - f.momentum) * f.running_mean[c] + f.momentum * mf;
-            f.running_var[c] = (1.f - f.momentum) * f.running_var[c] + f.momentum * (float)unbiased;
-        }
+        bn_finalize_channel(t1, t2, f.rows, f.gamma, f.beta, f.eps, f.momentum, f.running_mean, f.running_var, f.st, f.st + C,
+                            f.st + 2 * C, f.st + 3 * C, c);
     }
     if (first && threadIdx.x == 0) {
         if (f.set_rows) f.sums[2 * C] = f.rows;
@@ -187,21 +202,7 @@ __global__ void bn_finalize_k(const double* __restrict__ sums, double count, con
     if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
     if (c >= C) return;
     if (!(count > 0.0)) count = sums[2 * C];      // count travels with the (all-reduced) sums
-    const double m = sums[c] / count;
-    double var = sums[C + c] / count - m * m;
-    if (var < 0.0) var = 0.0;
-    const float is = (float)(1.0 / sqrt(var + (double)eps));
-    const float mf = (float)m;
-    mean[c] = mf;
-    invstd[c] = is;
-    const float sc = gamma[c] * is;
-    scale[c] = sc;
-    shift[c] = beta[c] - mf * sc;
-    if (running_mean) {
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mf;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
+    bn_finalize_channel(sums[c], sums[C + c], count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift, c);
 }
 
 // A bf16 SHADOW of an output ([n][C] bf16, rounded to nearest even, C % 32 == 0) can be written next to the fp32 tensor: the
@@ -381,7 +382,9 @@ int u3d_bn_forward(const float* x, int64_t n, int C, const float* partial, int64
                    float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, int relu, float* y, void* y_bf16,
                    float* st, double* sums, void* ws, u3d_stream_t stream) {
     // statistics (per-workgroup partial rows) -> bn_sum_k (sums them and finalizes the layer) -> apply
-    if (!x || !sums || !ws || !gamma || !beta || !st || !y || !bn_ok(n, C)) return U3D_EINVAL;
+    // (every refusal before the first launch: the statistics kernels move the running buffers and num_batches_tracked)
+    if (!x || !sums || !ws || !gamma || !beta || !st || !y || !bn_ok(n, C) || !shadow_ok(y_bf16, C)) return U3D_EINVAL;
+    if (partial && n_tiles <= 0) return U3D_EINVAL;
     BnFin f = bn_fin(sums, (double)n, 1);
     f.gamma = gamma; f.beta = beta; f.eps = eps; f.momentum = momentum; f.running_mean = running_mean; f.running_var = running_var;
     f.st = st; f.nbt = num_batches_tracked;
@@ -393,10 +396,9 @@ int u3d_bn_forward(const float* x, int64_t n, int C, const float* partial, int64
 int u3d_bn_backward(const float* x, const float* dy, const float* st, int relu, const double* fwd_sums, double* sums, int64_t n, int C,
                     float* dx, void* dx_bf16, float* dgamma, float* dbeta, const float* addend, void* ws, u3d_stream_t stream) {
     // sums[0..2C) are overwritten; sums[2C] (the row count) is taken from the forward pass's vector
-    if (!fwd_sums) return U3D_EINVAL;
+    if (!fwd_sums || !st || !dx || !shadow_ok(dx_bf16, C)) return U3D_EINVAL;       // before the first launch
     int rc = u3d_bn_bwd_stats(x, dy, st, st + C, st + 2 * C, st + 3 * C, relu, n, C, sums, ws, stream);
     if (rc) return rc;
-    if (!dx || !shadow_ok(dx_bf16, C)) return U3D_EINVAL;
     hipStream_t s = (hipStream_t)stream;       // the row count is read from the forward pass's vector (no copy launch)
     ProfScope prof(U3D_K_BN, s, (double)n * C * 12);
     const int64_t n4 = n * (C / 4);
