@@ -224,7 +224,17 @@ int u3d_weight_pack_x3(const float* w, void* wp, int Cd, int K, int Cs, int tran
  * U3D_EUNSUPPORTED -- each with a u3d_last_error text and before any launch.  tile_rows in {32, 64} and k_groups in {1} (any K) or
  * {3, 9} (K >= 27) are the CALLER'S choice here (u3d_spconv_plan[_bf16a] give the measured ones); ws = k_groups * n_dst * Cd * 4 bytes
  * when k_groups > 1 -- the main kernel then writes partials as always and the epilogue runs in the reduce.  addend is [n_dst][Cd].
- * Outputs must not overlap each other or the inputs.  Added entry point: U3D_ABI_VERSION is unchanged. */
+ * Outputs must not overlap each other or the inputs.  Added entry point: U3D_ABI_VERSION is unchanged.
+ * relu[j] is a FLAG WORD: U3D_EP_RELU = the ReLU follows; U3D_EP_BF16_ROWS = act[j] is a bf16-ROW buffer, the shadow u3d_bn_apply writes
+ * (y_bf16) and u3d_spconv_gmm_bf16a / fmt 3 gather: the same value rounded to nearest even, each 32-channel group in fragment order (the
+ * 8-byte piece of channels 4q..4q+3 of 16-channel half h at piece 2q + h), one 8-byte store per four channels.  For such an output act_ld[j]
+ * and act_col[j] count bf16 ELEMENTS and, like Cd, must be multiples of 32 (else U3D_EINVAL); scale / shift stay fp32, indexed by the
+ * output's own column.  No fp32 copy is written: a norm that is wanted in both forms takes two slots with the same scale / shift.  Any other
+ * bit: U3D_EUNSUPPORTED.  u3d_spconv_gmm_ep_formats() (host only) tells what the library writes -- bit 0: fp32 activated outputs, bit 1:
+ * bf16-row ones; a caller must see bit 1 before it sets U3D_EP_BF16_ROWS (a library from before the flag reads any non-zero word as "ReLU"
+ * and would write fp32 into the bf16 buffer; it lacks this symbol). */
+#define U3D_EP_RELU 1
+#define U3D_EP_BF16_ROWS 2
 typedef struct u3d_conv_epilogue {
     float* raw;
     int64_t raw_ld, raw_col;
@@ -239,6 +249,7 @@ int u3d_spconv_gmm_ep(int fmt, const void* src, int64_t n_src, const void* w_row
                       const int32_t* tile_starts, int K, int64_t cap, int Cs, int Cd, int64_t n_dst, int tile_rows,
                       int k_groups, const float* addend, void* ws, float* bn_partial, const u3d_conv_epilogue* ep, double flops_hint,
                       u3d_stream_t stream);
+int u3d_spconv_gmm_ep_formats(void);
 /* all packs of a model in one launch: desc = device array of n_desc records of eight int64
  * {src pointer, dst pointer, Cd, K, Cs, transposed, format (0 fp32, 1 bf16, 2 x3), first block}; record i owns blocks
  * [first_i, first_{i+1}) of 256 threads: one 16-byte output vector per thread in the fp32 (Cd*K*Cs/4 threads) and bf16 (Cd*K*Cs/8)

@@ -20,7 +20,7 @@ _u64 = C.c_uint64
 
 class ConvEpilogue(C.Structure):
     """u3d_conv_epilogue (include/u3d.h): where the rows of a forward convolution go -- raw into a column block, up to two
-    batch norm (+ ReLU) outputs."""
+    batch norm (+ ReLU) outputs.  ``relu[j]`` is a flag word: EP_RELU, EP_BF16_ROWS (``act[j]`` is a bf16-row buffer)."""
     _fields_ = [('raw', _vp), ('raw_ld', _i64), ('raw_col', _i64), ('n_act', _i32), ('act', _vp * 2), ('scale', _vp * 2), ('shift', _vp * 2),
                 ('act_ld', _i64 * 2), ('act_col', _i64 * 2), ('relu', _i32 * 2)]
 
@@ -64,6 +64,7 @@ PROTOTYPES = {
     'u3d_spconv_gmm_x3': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp]),
     'u3d_spconv_gmm_ep': (_i32, [_i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(ConvEpilogue),
                                  _f64, _vp]),
+    'u3d_spconv_gmm_ep_formats': (_i32, []),
     'u3d_weight_pack_x3': (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'u3d_spconv_rs_x3': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f64, _vp]),
     'u3d_spconv_rs_bf16a': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f64, _vp]),
@@ -190,6 +191,7 @@ PROTOTYPES = {
 }
 
 ABI_VERSION = 117         # include/u3d.h U3D_ABI_VERSION this table was written against
+EP_RELU, EP_BF16_ROWS = 1, 2      # include/u3d.h U3D_EP_*: the flag word of an activated output of u3d_conv_epilogue
 
 K_CONV_FWD, K_CONV_WGRAD, K_BN, K_POOL, K_ATTN_FWD, K_ATTN_BWD, K_RULEBOOK, K_VOXELIZE, K_GEMM = range(9)
 

@@ -212,10 +212,7 @@ __global__ void bn_finalize_k(const double* __restrict__ sums, double count, con
 // 16 + 4q .. 16 + 4q + 3 -- the eight reduction elements lane group q of v_mfma_f32_16x16x32_bf16 takes in the fp32-row kernels
 // (spconv.hip: k = 8q + e <-> channel 16 (e >> 2) + 4q + (e & 3)), so both kinds of kernel multiply the same operands in the same
 // k slots, share the packed weights, and return identical bits.
-__device__ __forceinline__ void store_shadow(__bf16* dst, int64_t row, int c4, int C4, const float4& o) {
-    const int g32 = c4 >> 3, half = (c4 >> 2) & 1, q = c4 & 3;          // channels 4 c4 .. 4 c4 + 3 = group g32, 16-channel half, quad q
-    reinterpret_cast<bf16x4*>(dst)[row * C4 + g32 * 8 + q * 2 + half] = bf16x4{(__bf16)o.x, (__bf16)o.y, (__bf16)o.z, (__bf16)o.w};
-}
+// (the store itself: u3d_common.h store_shadow, shared with the convolution epilogue)
 
 __global__ __launch_bounds__(256) void bn_apply_k(const float* __restrict__ x, const float* __restrict__ scale,
                                                   const float* __restrict__ shift, int relu, int64_t n4, int C4, float* y, __bf16* yb) {
@@ -226,7 +223,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const float* __restrict__ x, c
         const float4 sf = reinterpret_cast<const float4*>(shift)[c4];
         const float4 o = bn_affine_relu(v, sc, sf, relu);
         reinterpret_cast<float4*>(y)[i] = o;
-        if (yb) store_shadow(yb, i / C4, c4, C4, o);
+        if (yb) store_shadow(yb, i / C4, C4, 0, c4, o);
     }
 }
 
@@ -273,7 +270,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const float* __restrict__ 
             o.x += e.x; o.y += e.y; o.z += e.z; o.w += e.w;
         }
         reinterpret_cast<float4*>(dx)[i] = o;
-        if (dxb) store_shadow(dxb, i / C4, c4, C4, o);
+        if (dxb) store_shadow(dxb, i / C4, C4, 0, c4, o);
     }
 }
 

@@ -1102,14 +1102,21 @@ static int spconv_gmm_impl(const float* src, int64_t n_src, const float* w_rows,
         ge.raw = ep->raw; ge.raw_ld = (int)ep->raw_ld; ge.raw_col = (int)ep->raw_col;
         for (int j = 0; j < ep->n_act; ++j) {
             if (!ep->act[j] || !ep->scale[j] || !ep->shift[j]) { set_error("spconv_gmm_ep: activated output %d: NULL act / scale / shift", j); return U3D_EINVAL; }
-            if (ep->act_ld[j] < Cd || ep->act_col[j] < 0 || ep->act_col[j] + Cd > ep->act_ld[j] || ep->act_ld[j] % 4 || ep->act_col[j] % 4 || ep->act_ld[j] > (1 << 20)) {
-                set_error("spconv_gmm_ep: activated output %d ld=%lld col=%lld: ld >= col + Cd (Cd=%d), both multiples of 4 floats", j,
-                          (long long)ep->act_ld[j], (long long)ep->act_col[j], Cd);
+            if (ep->relu[j] & ~(U3D_EP_RELU | U3D_EP_BF16_ROWS)) {
+                set_error("spconv_gmm_ep: activated output %d: flag word %d (U3D_EP_RELU | U3D_EP_BF16_ROWS are defined)", j, ep->relu[j]);
+                return U3D_EUNSUPPORTED;
+            }
+            const bool b16 = (ep->relu[j] & U3D_EP_BF16_ROWS) != 0;      // bf16 rows: whole 32-channel groups, counted in bf16 elements
+            const int unit = b16 ? 32 : 4;
+            if (ep->act_ld[j] < Cd || ep->act_col[j] < 0 || ep->act_col[j] + Cd > ep->act_ld[j] || ep->act_ld[j] % unit || ep->act_col[j] % unit ||
+                ep->act_ld[j] > (1 << 20) || (b16 && Cd % 32)) {
+                set_error("spconv_gmm_ep: activated output %d ld=%lld col=%lld: ld >= col + Cd (Cd=%d), %s", j, (long long)ep->act_ld[j],
+                          (long long)ep->act_col[j], Cd, b16 ? "all three multiples of 32 bf16 elements (bf16 rows)" : "both multiples of 4 floats");
                 return U3D_EINVAL;
             }
             any = true;
             ge.act[j] = ep->act[j]; ge.scale[j] = ep->scale[j]; ge.shift[j] = ep->shift[j];
-            ge.act_ld[j] = (int)ep->act_ld[j]; ge.act_col[j] = (int)ep->act_col[j]; ge.relu[j] = ep->relu[j] ? 1 : 0;
+            ge.act_ld[j] = (int)ep->act_ld[j]; ge.act_col[j] = (int)ep->act_col[j]; ge.relu[j] = ep->relu[j];
         }
         if (!any) { set_error("spconv_gmm_ep: no output (raw NULL and no activated output)"); return U3D_EINVAL; }
         ge.n_act = ep->n_act;
@@ -1216,6 +1223,8 @@ int u3d_spconv_gmm_ep(int fmt, const void* src, int64_t n_src, const void* w_row
     return spconv_gmm_impl((const float*)src, n_src, (const float*)w_rows, gather, scatter, tile_starts, K, cap, Cs, Cd, n_dst, tile_rows,
                            k_groups, addend, nullptr, ws, bn_partial, flops_hint, stream, fmt, ep);
 }
+
+int u3d_spconv_gmm_ep_formats(void) { return 1 | 2; }      // bit 0: fp32 activated outputs, bit 1: bf16-row ones (U3D_EP_BF16_ROWS)
 
 static int weight_pack_impl(int format, const float* w, void* wp, int Cd, int K, int Cs, int transposed, u3d_stream_t stream) {
     static const char* const label[] = {"weight_pack", "weight_pack_bf16", "weight_pack_x3"};

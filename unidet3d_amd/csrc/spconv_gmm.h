@@ -11,6 +11,10 @@ namespace u3d {
 //   act[j], j < n_act <= 2: x * scale[j][c] + shift[j][c] (+ ReLU), c = the column of act[j] the value lands in (act_col[j] + dst column):
 //   a norm over a wider tensor (the U-Net's concat) is applied to its column blocks by the convolutions that produce them.
 // All leading dimensions and column offsets are multiples of 4 floats: every store is a 16-byte vector store.
+// relu[j] is the flag word of the C ABI: U3D_EP_RELU (1) = ReLU follows, U3D_EP_BF16_ROWS (2) = act[j] is a bf16-row buffer -- the shadow
+// u3d_bn_apply writes (u3d_common.h store_shadow: same rounding, same fragment order), act_ld / act_col then count bf16 elements in
+// multiples of 32: one 8-byte store per 16-byte fp32 piece.  (The two halves c4 / c4 + 4 of a 16-byte shadow quad sit on lanes l and
+// l + 4 of the write-out loops: pairing them would cost a cross-lane move per piece, so they stay two stores.)
 struct GmmEpilogue {
     float* raw;
     float* act[2];
@@ -29,7 +33,9 @@ __device__ __forceinline__ void gmm_write_out(const GmmEpilogue& ep, int64_t row
         if (j < ep.n_act) {
             const int c = ep.act_col[j] + col;
             const float4 sc = *reinterpret_cast<const float4*>(ep.scale[j] + c), sf = *reinterpret_cast<const float4*>(ep.shift[j] + c);
-            *reinterpret_cast<float4*>(ep.act[j] + row * ep.act_ld[j] + c) = bn_affine_relu(v, sc, sf, ep.relu[j]);
+            const float4 o = bn_affine_relu(v, sc, sf, ep.relu[j] & U3D_EP_RELU);
+            if (ep.relu[j] & U3D_EP_BF16_ROWS) store_shadow(reinterpret_cast<__bf16*>(ep.act[j]), row, ep.act_ld[j] >> 2, ep.act_col[j] >> 2, col >> 2, o);
+            else *reinterpret_cast<float4*>(ep.act[j] + row * ep.act_ld[j] + c) = o;
         }
     }
 }

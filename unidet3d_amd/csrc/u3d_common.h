@@ -105,6 +105,16 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return __builtin_bit_cast(unsigned, bf16x2{(__bf16)lo, (__bf16)hi}); }
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
 
+// Four channels of a row into its bf16 SHADOW (bn.hip: the rows the bf16-row convolution kernels gather): rounded to nearest even, each
+// 32-channel group in MFMA fragment order -- the 8-byte piece of channels 4 c4 .. 4 c4 + 3 sits at piece g32 * 8 + q * 2 + half.  THE
+// store of bn_apply_k / bn_bwd_apply_k and of the convolution epilogue (spconv_gmm.h gmm_write_out), like bn_affine_relu above: one
+// definition, one layout, one rounding.  dst is a buffer of ld4 pieces per row whose block starts at piece col4 (both multiples of 8: whole
+// 32-channel groups); c4 counts from the block's first column.
+__device__ __forceinline__ void store_shadow(__bf16* dst, int64_t row, int ld4, int col4, int c4, const float4& o) {
+    const int g32 = c4 >> 3, half = (c4 >> 2) & 1, q = c4 & 3;          // channels 4 c4 .. 4 c4 + 3 = group g32, 16-channel half, quad q
+    reinterpret_cast<bf16x4*>(dst)[row * ld4 + col4 + g32 * 8 + q * 2 + half] = bf16x4{(__bf16)o.x, (__bf16)o.y, (__bf16)o.z, (__bf16)o.w};
+}
+
 // LDS transpose read (ds_read_b64_tr_b16) of two [4 rows][16 cols] bf16 blocks: each 16-lane group hands in the 8-byte addresses
 // of its block (p0, p1: this lane's 4 halves) and lane t receives column t over the four rows of either block -- one MFMA operand.
 __device__ __forceinline__ bf16x8 tr16_pair(const __bf16* p0, const __bf16* p1) {

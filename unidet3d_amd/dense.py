@@ -391,6 +391,8 @@ class _LinearFn(torch.autograd.Function):
 def linear(x: torch.Tensor, weight: torch.Tensor, bias=None, out_bf16: bool = False) -> torch.Tensor:
     """y = x W^T + b for 2-D x [M, K] (K % 16 == 0).  ``out_bf16``: under precision.bf16_act() the result is a bf16 tensor (for a
     consumer that reads one: the attention kernels); ignored otherwise."""
+    if not x.shape[0] and getattr(x, '_u3d_rows_only', None) is not None:      # sparse.rows_only: a zero-row placeholder, not a matrix to multiply
+        raise L.U3DError('linear: this tensor exists as bf16 rows only (fused inference wrote it for a sparse convolution): no fp32 values to read')
     return _LinearFn.apply(_flow(x, x.shape[1]), x, weight, bias, out_bf16)
 
 

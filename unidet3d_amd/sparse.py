@@ -294,7 +294,30 @@ def attach_shadow(t: torch.Tensor, shadow: torch.Tensor):
     t._u3d_shadow = (shadow, t._version)
 
 
+def rows_only(shadow: torch.Tensor) -> torch.Tensor:
+    """A tensor that exists as bf16 rows ONLY (fused inference under ``precision.bf16_rows``: the convolution epilogue wrote a norm's result
+    in the one form its reader gathers): a zero-row fp32 placeholder of the same width that carries the rows as its shadow.  It has no
+    values to read by accident; ``shadow_of`` hands the rows to a pair-list convolution, every other reader refuses it (``refuse_rows_only``)."""
+    t = torch.empty(0, shadow.shape[1], dtype=torch.float32, device=shadow.device)
+    t._u3d_rows_only = shadow
+    return t
+
+
+def rows_only_of(t):
+    return getattr(t, '_u3d_rows_only', None)
+
+
+def refuse_rows_only(t, reader: str):
+    if not t.shape[0] and getattr(t, '_u3d_rows_only', None) is not None:      # (the placeholder has no rows: everything else leaves at the first test)
+        raise L.U3DError(f'{reader}: this tensor exists as bf16 rows only (fused inference wrote it for a sparse convolution that gathers '
+                         f'bf16 rows): it has no fp32 values to read')
+
+
 def shadow_of(t: torch.Tensor):
+    e = getattr(t, '_u3d_rows_only', None)
+    if e is not None:
+        SHADOW_STATS['hit'] += 1
+        return e
     e = getattr(t, '_u3d_shadow', None)
     if e is not None and e[1] == t._version and e[0].shape == t.shape and e[0].device == t.device:
         SHADOW_STATS['hit'] += 1
@@ -463,9 +486,10 @@ set_conv_rs, conv_rs = _flag_toggle('_CONV_RS')
 set_conv_rs_bf16, conv_rs_bf16 = _flag_toggle('_CONV_RS_BF16')
 # Fused inference: in eval mode under torch.no_grad() the pair-list convolutions write the batch norm + ReLU of the
 # norm(s) that read their result on the way out of the LDS tile (u3d_spconv_gmm_ep), and the U-Net's concat buffer directly.  Same bits
-# as the unfused path.  Three states: None (the default) = on, except under ``precision.bf16_rows`` -- there inference keeps gathering the
-# bf16 shadows u3d_bn_apply writes (the epilogue writes none; tests/test_gpu_bf16.py pins that data flow); True = on everywhere (under
-# bf16_rows the fused launches gather fp32 rows and round them: same bits, measured faster); False = off.
+# as the unfused path.  Under ``precision.bf16_rows`` the epilogue writes every norm result whose only reader is a planned convolution as
+# bf16 rows, the shadow u3d_bn_apply writes, and nothing else (``rows_only``): the reader gathers them with the bf16-row kernel, as on the
+# unfused path.  Three states: None (the default) = on, except under ``precision.bf16_rows`` -- there the default stays
+# the unfused sequence (tests/test_fused_inference_cpu.py pins it; the measurements are in DESIGN.md 4.28); True = on everywhere; False = off.
 # U3D_FUSED_INFERENCE=1 / 0, set_fused_inference(True / False / None).
 _FUSED_INFERENCE = {'1': True, '0': False}.get(os.environ.get('U3D_FUSED_INFERENCE', ''))
 
@@ -689,6 +713,7 @@ def sparse_conv(src, weight, rb, mode='fwd', addend=None, want_stats=False):
     """``want_stats``: a batch norm in training mode reads the result: what the launch wrote for it (``_gmm``) rides on the returned
     tensor (``stats_of``)."""
     st = {} if want_stats else None
+    refuse_rows_only(src, 'sparse_conv')
     dst = _SparseConvFn.apply(src, weight, rb, mode, addend, st)
     if st:
         attach_stats(dst, st['partial'], st['n_tiles'])
@@ -697,43 +722,60 @@ def sparse_conv(src, weight, rb, mode='fwd', addend=None, want_stats=False):
     return dst
 
 
+_EP_FORMATS = None
+
+
+def _ep_writes_rows() -> bool:
+    """u3d_spconv_gmm_ep_formats() bit 1, asked once: only a library that reports it is handed U3D_EP_BF16_ROWS (one from before the flag
+    would read it as "ReLU" and write fp32 into the bf16 buffer)"""
+    global _EP_FORMATS
+    if _EP_FORMATS is None:
+        _EP_FORMATS = int(L.lib().u3d_spconv_gmm_ep_formats())
+    return bool(_EP_FORMATS & 2)
+
+
 def sparse_conv_fused(src, weight, rb, mode, addend, raw, acts):
     """Forward convolution of the fused inference path (no autograd): u3d_spconv_gmm_ep.
     ``raw``: (fp32 buffer [n_dst, ld], first column) that receives dst, or None for no raw output; ``acts``: up to two
     (buffer [n_dst, ld], first column, scale, shift, relu) that receive relu(dst * scale + shift) -- scale / shift indexed by the buffer's
-    own columns.  Same kernel, operand format and offset groups as ``_gmm`` takes for this shape, so dst has the bits ``sparse_conv``
-    returns.  Under ``precision.bf16_rows`` a source without a bf16 shadow that a fused launch activated (``_u3d_fused_act``) is gathered
-    as fp32 rows and rounded as the operand is formed, under the plan of the bf16-row kernel the unfused path would have run on its
-    shadow: same values, same offset groups, same sums."""
+    own columns; a bfloat16 buffer receives bf16 rows (``to_shadow``'s layout, U3D_EP_BF16_ROWS), an fp32 one the values.  Same kernel,
+    operand format and offset groups as ``_gmm`` takes for this shape, so dst has the bits ``sparse_conv`` returns.  A ``rows_only`` source
+    is gathered as bf16 rows (fmt 3) under the bf16-row kernel's own plan, or refused where the launch would gather anything else."""
     cout, cin = weight.shape[0], weight.shape[-1]
     w = weight.reshape(cout, rb.K, cin).contiguous()
+    only = rows_only_of(src)
     src = src.contiguous()
     g, s, role, n_dst = _roles(rb, mode)
     if not n_dst:
         return
     flops = 2.0 * rb.total_pairs * cin * cout if _PROFILE_FLOPS else 0.0
     bf = P.conv_format()
-    shadow = shadow_of(src) if bf == P.FMT_BF16 and P.bf16_rows() and cin % 32 == 0 else None
+    shadow = shadow_of(src) if (bf == P.FMT_BF16 and P.bf16_rows() and cin % 32 == 0) or only is not None else None
+    n_src = src.shape[0] if only is None else only.shape[0]
     route, fmt, plan = _conv_route(cin, cout, n_dst, rb, bf, shadow is not None, False)
     if route != 'pairs':
         raise L.U3DError(f'fused inference: the {route!r} kernel has no output epilogue')
     R, G, rows = plan
-    if (fmt == P.FMT_BF16 and not rows and P.bf16_rows() and getattr(src, '_u3d_fused_act', False)
-            and L.lib().u3d_spconv_gmm_bf16a_supported(cin, cout)):
-        R, G = _plan(cin, cout, rb.K, n_dst, True)
+    if not rows:
+        refuse_rows_only(src, f'sparse_conv_fused ({cin} -> {cout} channels, operand format {fmt})')
     if _PROFILE_FLOPS:
-        account.add('conv_gmm', flops, 4.0 * (src.shape[0] * cin + n_dst * cout) + 8.0 * rb.total_pairs + 4.0 * rb.K * cin * cout)
+        account.add('conv_gmm', flops, 4.0 * (n_src * cin + n_dst * cout) + 8.0 * rb.total_pairs + 4.0 * rb.K * cin * cout)
     wp = _packed_weight(w, False, fmt, cout, rb.K, cin, src.device)
     ep = L.ConvEpilogue()
     if raw is not None:
         ep.raw, ep.raw_ld, ep.raw_col = raw[0].data_ptr(), raw[0].shape[1], raw[1]
     ep.n_act = len(acts)
     for j, (buf, col, scale, shift, relu) in enumerate(acts):
+        flags = L.EP_RELU if relu else 0
+        if buf.dtype == torch.bfloat16:
+            if not _ep_writes_rows():
+                raise L.U3DError('fused inference: this kernel library writes no bf16-row activated outputs: rebuild it')
+            flags |= L.EP_BF16_ROWS
         ep.act[j], ep.act_ld[j], ep.act_col[j] = buf.data_ptr(), buf.shape[1], col
-        ep.scale[j], ep.shift[j], ep.relu[j] = L.ptr(scale), L.ptr(shift), int(relu)
+        ep.scale[j], ep.shift[j], ep.relu[j] = L.ptr(scale), L.ptr(shift), flags
     ws = torch.empty(G * n_dst * cout, dtype=torch.float32, device=src.device) if G > 1 else None
     tiles = rb.tile_starts(role, R)
-    L.call('u3d_spconv_gmm_ep', 3 if rows else fmt, L.ptr(shadow if rows else src), src.shape[0], L.ptr(wp), L.ptr(g), L.ptr(s), L.ptr(tiles),
+    L.call('u3d_spconv_gmm_ep', 3 if rows else fmt, L.ptr(shadow if rows else src), n_src, L.ptr(wp), L.ptr(g), L.ptr(s), L.ptr(tiles),
            rb.K, rb.cap, cin, cout, n_dst, R, G, L.ptr(None if addend is None else addend.contiguous()), L.ptr(ws), None, ctypes.byref(ep),
            float(flops), L.stream())
 
@@ -750,12 +792,26 @@ class FusionRun:
         self.plan = plan
         self.cats: Dict = {}
         self.used = False                  # set when the planned U-Net starts its forward: a pass's buffers are never handed out twice
+        self._rows: Dict = {}
+
+    def rows(self, norm) -> bool:
+        """``norm``'s result is written as bf16 rows and as nothing else: bf16 operands with ``precision.bf16_rows``, the only reader a
+        planned convolution (``FusionPlan.rows_capable``) of a shape the bf16-row kernel has -- that launch then gathers fmt 3 under
+        the bf16-row plan, exactly what the unfused path runs on the shadow u3d_bn_apply wrote.  In every other mode: never."""
+        hit = self._rows.get(norm)
+        if hit is None:
+            hit = self._rows[norm] = bool(
+                P.conv_format() == P.FMT_BF16 and P.bf16_rows() and self.plan.rows_capable(norm)
+                and L.lib().u3d_spconv_gmm_bf16a_supported(norm.num_features, self.plan.norms[norm].reader.out_channels))
+        return hit
 
     def cat(self, owner, n: int, device):
-        """(raw, activated) [n, 2c] buffers of U-Net level ``owner``: the concatenation its tail blocks read, and the first tail norm of it"""
+        """(raw, activated) [n, 2c] buffers of U-Net level ``owner``: the concatenation its tail blocks read, and the first tail norm of it
+        (bf16 rows where ``rows`` says so)"""
         if owner not in self.cats:
-            width = self.plan.cats[owner].width
-            self.cats[owner] = tuple(torch.empty(n, width, dtype=torch.float32, device=device) for _ in range(2))
+            c = self.plan.cats[owner]
+            self.cats[owner] = (torch.empty(n, c.width, dtype=torch.float32, device=device),
+                                torch.empty(n, c.width, dtype=torch.bfloat16 if self.rows(c.norm) else torch.float32, device=device))
         return self.cats[owner]
 
     def conv(self, layer, cp, x: 'SparseConvTensor', rb: Rulebook, mode: str, addend=None) -> torch.Tensor:
@@ -774,10 +830,10 @@ class FusionRun:
         for norm, relu, where in cp.acts:
             scale, shift = norm.eval_affine()
             if where is None:
-                y = torch.empty(n_dst, Cd, dtype=torch.float32, device=dev)
-                y._u3d_fused_act = True
+                rows = self.rows(norm)
+                y = torch.empty(n_dst, Cd, dtype=torch.bfloat16 if rows else torch.float32, device=dev)
                 acts.append((y, 0, scale, shift, relu))
-                own.append((norm, y, relu))
+                own.append((norm, rows_only(y) if rows else y, relu))
             else:
                 acts.append((self.cat(where[0], n_dst, dev)[1], where[1], scale, shift, relu))
         sparse_conv_fused(src, weight, rb, mode, addend, raw, acts)
@@ -789,8 +845,7 @@ class FusionRun:
         """The concatenation of level ``owner`` after both producers ran, with its first tail norm's result attached"""
         buf, act = self.cat(owner, n, device)
         c = self.plan.cats[owner]
-        act._u3d_fused_act = True
-        attach_activated(buf, c.norm, act, c.relu)
+        attach_activated(buf, c.norm, rows_only(act) if act.dtype == torch.bfloat16 else act, c.relu)
         return buf
 
 
@@ -964,6 +1019,7 @@ class SparseBatchNorm(nn.Module):
         are used where there are any: the statistics then cost no pass over x."""
         # bf16 operands with bf16 rows in HBM (precision.bf16_rows): y (when a ReLU follows -- the input of a sparse convolution -- and
         # the channel count suits the bf16 kernels) and the gradient handed back to a producing convolution get a bf16 shadow
+        refuse_rows_only(x, 'SparseBatchNorm')
         if self.training and self._affine_cache is not None:
             self._affine_cache = None       # the running statistics (and, by the optimizer, weight and bias) move without a ``_version`` bump
         if not self.training and not torch.is_grad_enabled():

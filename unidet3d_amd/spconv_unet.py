@@ -74,8 +74,9 @@ class ResidualBlock(SparseModule):
 # ----------------------------------------------------------------------------------------
 class FusionPlan:
     """Successor plan of a pre-activation U-Net for the fused inference path.  Pure bookkeeping (no tensors):
-      ``norms``  SparseBatchNorm -> (name, relu, producers [(convolution, first column, end column)], fused); no producers = unfused:
-                 that norm runs u3d_bn_apply as always;
+      ``norms``  SparseBatchNorm -> (name, relu, producers [(convolution, first column, end column)], fused, reader); no producers =
+                 unfused: that norm runs u3d_bn_apply as always; reader = the planned convolution that is the ONLY reader of the norm's
+                 result (None: somebody else reads it, or nobody the plan knows) -- ``rows_capable``;
       ``convs``  convolution -> (raw, acts): raw = 'own' (a tensor of its own), None (nobody reads the raw result) or (level, first
                  column) of that U-Net level's concat buffer; acts = up to two (norm, relu, None | (level, first column)): the activated
                  tensor of its own, or a column block of the level's activated concat buffer;
@@ -95,7 +96,17 @@ class FusionPlan:
 
     def norm(self, m, relu, producers):
         assert m not in self.norms
-        self.norms[m] = SimpleNamespace(relu=bool(relu), producers=list(producers), fused=bool(producers))
+        self.norms[m] = SimpleNamespace(relu=bool(relu), producers=list(producers), fused=bool(producers), reader=None)
+
+    def read_by(self, norm, conv):
+        """``conv`` (3x3x3 or strided: a pair-list launch) is the only reader of ``norm``'s result"""
+        self.norms[norm].reader = conv
+
+    def rows_capable(self, norm) -> bool:
+        """The producers of ``norm`` may write its result as bf16 rows ONLY (``sparse.FusionRun``, precision.bf16_rows): every column of
+        it comes from an epilogue, and the one reader is a planned convolution, which gathers rows."""
+        e = self.norms.get(norm)
+        return e is not None and e.fused and e.reader is not None
 
     def feed(self, conv, norm, relu, lo, hi, where=None):
         """``conv`` writes columns [lo, hi) of ``norm``'s result"""
@@ -156,8 +167,10 @@ def _plan_level(plan, u, feed, sink):
                 plan.norm(n1, True, [])       # nobody known to produce its input: unfused
             else:
                 plan.feed(prod, n1, True, 0, width)
+            plan.read_by(n1, conv1)           # (the identity branch next to n1 reads the norm's INPUT)
             plan.conv(conv1).raw = None       # only norm 2 reads conv 1
             plan.feed(conv1, n2, True, 0, conv1.out_channels)
+            plan.read_by(n2, conv2)
             plan.conv(conv2)
             prod, width = conv2, conv2.out_channels
         return True, prod
@@ -179,9 +192,11 @@ def _plan_level(plan, u, feed, sink):
         # norm's columns [0, c)
         plan.conv(prod).raw = (u, 0)
         plan.feed(prod, down[0], True, 0, c)
+        plan.read_by(down[0], down[1])
         plan.feed(prod, tnorm, True, 0, c, (u, 0))
         if not _plan_level(plan, u.u, down[1], (up[0], True)):
             return False
+        plan.read_by(up[0], up[1])            # the inner level's sink; the outermost one (``last_consumer``) has no planned reader
         # the inverse convolution: raw and the first tail norm, columns [c, 2c)
         plan.conv(up[1]).raw = (u, c)
         plan.feed(up[1], tnorm, True, c, 2 * c, (u, c))
