@@ -165,6 +165,33 @@ int u3d_down_rulebook(const int32_t* coords, int64_t n, const uint64_t* bitmap2,
                       void* ws, u3d_stream_t stream);
 int64_t u3d_down_rulebook_ws_bytes(int64_t n);
 
+/* =====================================================================================
+ * R3g  General convolution geometry: kernel extents 1..3 per axis, any stride, padding, dilation (spconv's SparseConv3d / SubMConv3d
+ *      outside the two shapes above).  geom = int32 [12] on the HOST: kernel[3], stride[3], padding[3], dilation[3], axes in the order
+ *      of coords[:, 1:4].  Per axis out_dim = floor((in_dim + 2 p - d (k - 1) - 1) / s) + 1; output cell o is active iff an active input
+ *      i and a tap t in [0, k) satisfy i + p = o s + t d on all three axes with 0 <= o < out_dim.  Offset index = (t0 k1 + t1) k2 + t2
+ *      (the weight layout [C_out, k0, k1, k2, C_in]); K = k0 k1 k2 <= 27.  (k=2, s=2, p=0) gives R3's lists, SubM k=3 (p=1) R2's.
+ *   u3d_conv_out_shape (host only): out_shape int32 [3] for input extents (X, Y, Z); an extent that comes out <= 0 is reported as 0.
+ *   u3d_conv_mark: the output occupancy of the n input rows `coords`, in one of two forms -- bitmap_out (zeroed, sized by
+ *     u3d_index_words(B, out_shape); u3d_index_rank follows) or cells_out int64 [K n] (cell ids, INT64_MAX = none, for
+ *     u3d_hash_index_build); exactly one of the two is non-NULL.  The output level's rows are the index's canonical order.
+ *   u3d_conv_rulebook: output-stationary pairs.  out_coords int32 [n_out,4] = the output level's rows; (bitmap_in, word_rank_in,
+ *     hash_slots, B, X, Y, Z) = the INPUT level's index (n_in rows).  pair_in / pair_out int32 [K, cap], counts int32 [K]; cap >=
+ *     min(n_in, n_out) -- enough, because for a fixed offset the map output cell -> input cell is injective and monotone in canonical
+ *     order; for the same reason BOTH columns ascend inside an offset and no row repeats, which is what the convolution kernels need.
+ *     ws: u3d_conv_rulebook_ws_bytes(n_out, K).
+ *   Errors, before any launch and with a u3d_last_error text: U3D_EUNSUPPORTED for a kernel extent outside 1..3, for extent + 2 padding
+ *   + 2 dilation beyond 32-bit coordinates and for an output grid the index form refuses; U3D_EINVAL for stride / dilation < 1, padding
+ *   < 0, an empty output level, NULL pointers, n <= 0 and a cap below min(n_in, n_out).  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+int u3d_conv_out_shape(const int32_t* geom, int X, int Y, int Z, int32_t* out_shape);
+int u3d_conv_mark(const int32_t* coords, int64_t n, const int32_t* geom, int B, int X, int Y, int Z, uint64_t* bitmap_out,
+                  int64_t* cells_out, u3d_stream_t stream);
+int u3d_conv_rulebook(const int32_t* out_coords, int64_t n_out, int64_t n_in, const uint64_t* bitmap_in, const int32_t* word_rank_in,
+                      int64_t hash_slots, int B, int X, int Y, int Z, const int32_t* geom, int64_t cap, int32_t* pair_in,
+                      int32_t* pair_out, int32_t* counts, void* ws, u3d_stream_t stream);
+int64_t u3d_conv_rulebook_ws_bytes(int64_t n_out, int K);
+
 /* tile_starts int32 [K, n_tiles+1]: lower bound of t*tile_rows in the (ascending) list rows[k][0..counts[k]). */
 int u3d_tile_starts(const int32_t* rows, const int32_t* counts, int K, int64_t cap, int tile_rows,
                     int64_t n_tiles, int32_t* tile_starts, u3d_stream_t stream);

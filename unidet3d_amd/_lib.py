@@ -55,6 +55,11 @@ PROTOTYPES = {
     'u3d_index_mark': (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     'u3d_down_rulebook': (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     'u3d_down_rulebook_ws_bytes': (_i64, [_i64]),
+    # general convolution geometry (added entry points, same ABI version); geom = host int32 [12]
+    'u3d_conv_out_shape': (_i32, [C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32)]),
+    'u3d_conv_mark': (_i32, [_vp, _i64, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'u3d_conv_rulebook': (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i64, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_conv_rulebook_ws_bytes': (_i64, [_i64, _i32]),
     'u3d_tile_starts': (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp]),
     'u3d_spconv_gmm': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp]),
     'u3d_spconv_gmm_bf16': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp]),

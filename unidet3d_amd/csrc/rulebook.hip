@@ -1,6 +1,7 @@
 // R2 / R3 rulebooks on gfx950.
 // Replaces spconv's indice-pair generation for SubMConv3d(k=3) and SparseConv3d(k=2,s=2)
-// (reference call sites unidet3d/spconv_unet.py:43-56,148-154,178-183; unidet3d/unidet3d.py:97-103).
+// (reference call sites unidet3d/spconv_unet.py:43-56,148-154,178-183; unidet3d/unidet3d.py:97-103), and, for every other layer
+// shape with kernel extents up to 3 (stride, padding, dilation), the general builder further down (conv_mark_k / conv_count_k / conv_write_k).
 // Neighbour lookup goes through the occupancy bitmap + popcount rank (u3d_common.h) --
 // the key -> row map is a direct-address table, so rows come out in canonical (sorted-key)
 // order by construction and the pair lists are bit-exact against the CPU oracle.
@@ -135,6 +136,122 @@ __global__ __launch_bounds__(RB_T) void subm_write_k(const int32_t* __restrict__
     }
 }
 
+// ---- general convolution geometry: kernel extents 1..3 per axis, any stride / padding / dilation ------------------------------
+// spconv's rule, per axis: out_dim = floor((in_dim + 2 p - d (k - 1) - 1) / s) + 1, and output cell o is active iff an active input i and
+// a tap t in [0, k) satisfy i + p = o s + t d on all three axes with 0 <= o < out_dim.  Offset index = (t0 k1 + t1) k2 + t2, the order of
+// the weight layout [C_out, k0, k1, k2, C_in].  SparseConv3d(k=2, s=2) (out = in >> 1, edge drop) and SubMConv3d(k=3) (p = 1, output set
+// = input set) are special cases and come out of these kernels with the same lists as down_nbr_k / subm_lookup above.
+//
+// The rulebook pass is output-stationary like the SubM builder: thread = output row r, grid.y = offset, value = the row of the input cell
+// o s - p + t d in the INPUT level's index, looked up again in the count and in the write pass (same traffic argument as above).
+// Both columns of an offset's list ascend and no row repeats: for a fixed tap the map o -> o s - p + t d is, axis by axis, strictly
+// increasing, so it is injective and keeps the lexicographic order of (b, x, y, z), which is the canonical order of either level.  Walking
+// the output rows in order therefore emits the input rows in order, and an offset has at most min(n_in, n_out) pairs.
+struct ConvGeom {
+    int k[3], s[3], p[3], d[3];
+    int out[3];                 // output extents
+    int K;                      // k[0] k[1] k[2]
+};
+
+__device__ __forceinline__ void conv_taps(const ConvGeom& g, int k, int t[3]) {
+    t[2] = k % g.k[2];
+    t[1] = (k / g.k[2]) % g.k[1];
+    t[0] = k / (g.k[2] * g.k[1]);
+}
+
+// output cell of input cell `c` under tap `t` on one axis, or -1
+__device__ __forceinline__ int conv_out_of_in(int c, int t, int s, int p, int d, int out_dim) {
+    const int v = c + p - t * d;
+    if (v < 0) return -1;
+    // the stride is uniform over the launch: strides 1 and 2 (nearly every layer) take no integer division, one scalar branch instead
+    const int o = s == 1 ? v : (s == 2 ? v >> 1 : v / s);
+    return (o * s == v && o < out_dim) ? o : -1;
+}
+
+// grid (nblk, K): marks the output cell of (input row, tap) where there is one.  bitmap != nullptr: sets its bit (bitmap zeroed by the
+// caller); else cells[k n + i] = the cell id, CELL_NONE for none (the hashed index sorts and uniques them)
+__global__ __launch_bounds__(RB_T) void conv_mark_k(const int32_t* __restrict__ coords, int64_t n, ConvGeom g, int B, int Zw, unsigned long long* bitmap,
+                                                    int64_t* __restrict__ cells) {
+    const int64_t i = (int64_t)blockIdx.x * RB_T + threadIdx.x;
+    if (i >= n) return;
+    const int k = blockIdx.y;
+    int t[3];
+    conv_taps(g, k, t);
+    const int4 c = *reinterpret_cast<const int4*>(coords + i * 4);
+    const int x = conv_out_of_in(c.y, t[0], g.s[0], g.p[0], g.d[0], g.out[0]);
+    const int y = conv_out_of_in(c.z, t[1], g.s[1], g.p[1], g.d[1], g.out[1]);
+    const int z = conv_out_of_in(c.w, t[2], g.s[2], g.p[2], g.d[2], g.out[2]);
+    const bool ok = (x | y | z) >= 0 && (unsigned)c.x < (unsigned)B;
+    const int64_t w = (((int64_t)c.x * g.out[0] + x) * g.out[1] + y) * Zw + (z >> 6);
+    if (bitmap) {
+        if (ok) atomicOr(&bitmap[w], 1ull << (z & 63));
+    } else {
+        cells[(int64_t)k * n + i] = ok ? w * 64 + (z & 63) : 0x7fffffffffffffffLL;
+    }
+}
+
+__device__ __forceinline__ int conv_lookup(const int32_t* __restrict__ out_coords, int64_t r, int k, const ConvGeom& g, const Index& ix) {
+    int t[3];
+    conv_taps(g, k, t);
+    const int4 c = *reinterpret_cast<const int4*>(out_coords + r * 4);
+    return index_lookup(ix, c.x, c.y * g.s[0] - g.p[0] + t[0] * g.d[0], c.z * g.s[1] - g.p[1] + t[1] * g.d[1], c.w * g.s[2] - g.p[2] + t[2] * g.d[2]);
+}
+
+// grid (nblk, K)
+__global__ __launch_bounds__(RB_T) void conv_count_k(const int32_t* __restrict__ out_coords, int64_t n, ConvGeom g, Index ix, int nblk,
+                                                     int32_t* block_cnt) {
+    const int64_t r = (int64_t)blockIdx.x * RB_T + threadIdx.x;
+    const int k = blockIdx.y;
+    const bool ok = r < n && conv_lookup(out_coords, r, k, g, ix) >= 0;
+    const int c = __syncthreads_count(ok);
+    if (threadIdx.x == 0) block_cnt[(int64_t)k * nblk + blockIdx.x] = c;
+}
+
+// stable compaction, as subm_write_k: list_row[k][pos] = output row, list_val[k][pos] = its input row    grid (nblk, K)
+__global__ __launch_bounds__(RB_T) void conv_write_k(const int32_t* __restrict__ out_coords, int64_t n, ConvGeom g, Index ix, int nblk,
+                                                     const int32_t* __restrict__ block_base, int64_t cap, int32_t* list_row, int32_t* list_val) {
+    __shared__ int s_w[RB_T / 64];
+    const int64_t r = (int64_t)blockIdx.x * RB_T + threadIdx.x;
+    const int k = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int v = r < n ? conv_lookup(out_coords, r, k, g, ix) : -1;
+    const bool ok = v >= 0;
+    const unsigned long long m = __ballot(ok);
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_w[wave] = __popcll(m);
+    __syncthreads();
+    int woff = 0;
+#pragma unroll
+    for (int w = 0; w < RB_T / 64; ++w) if (w < wave) woff += s_w[w];
+    const int64_t at = (int64_t)block_base[(int64_t)k * nblk + blockIdx.x] + woff + rank;
+    if (ok && at < cap) {       // (at < cap always holds for cap >= min(n_in, n_out), which the entry point checks)
+        list_row[(int64_t)k * cap + at] = (int)r;
+        list_val[(int64_t)k * cap + at] = v;
+    }
+}
+
+// geom = kernel[3], stride[3], padding[3], dilation[3] (host) -> ConvGeom for input extents (X, Y, Z); U3D_OK, or the code with the text set.
+// Output extents may come out <= 0 (an input smaller than the kernel's reach): they are reported as 0, an empty level.
+static int conv_geom(const int32_t* geom, int X, int Y, int Z, ConvGeom* g) {
+    if (!geom || X <= 0 || Y <= 0 || Z <= 0) { set_error("conv geometry: null geometry or non-positive extent %d x %d x %d", X, Y, Z); return U3D_EINVAL; }
+    const int in[3] = {X, Y, Z};
+    g->K = 1;
+    for (int a = 0; a < 3; ++a) {
+        const int k = geom[a], s = geom[3 + a], p = geom[6 + a], d = geom[9 + a];
+        if (k < 1 || k > 3) { set_error("conv geometry: kernel extent %d on axis %d is outside 1..3", k, a); return U3D_EUNSUPPORTED; }
+        if (s < 1 || d < 1 || p < 0) { set_error("conv geometry: stride %d / dilation %d must be >= 1 and padding %d >= 0 (axis %d)", s, d, p, a); return U3D_EINVAL; }
+        // every coordinate the kernels form lies in [-(p + 2 d), in + 2 p + 2 d]: keep that inside int32
+        if ((int64_t)in[a] + 2 * (int64_t)p + 2 * (int64_t)d >= 0x7fffffffLL) {
+            set_error("conv geometry: extent %d + 2 * padding %d + 2 * dilation %d overflows 32-bit coordinates (axis %d)", in[a], p, d, a);
+            return U3D_EUNSUPPORTED;
+        }
+        const int64_t span = (int64_t)in[a] + 2 * (int64_t)p - (int64_t)d * (k - 1) - 1;
+        g->k[a] = k; g->s[a] = s; g->p[a] = p; g->d[a] = d;
+        g->out[a] = span < 0 ? 0 : (int)(span / s) + 1;
+        g->K *= k;
+    }
+    return U3D_OK;
+}
+
 // tile_starts[k][t] = lower_bound(rows[k][0..counts[k]), t*T)
 __global__ __launch_bounds__(256) void tile_starts_k(const int32_t* __restrict__ rows, const int32_t* __restrict__ counts, int64_t cap,
                                                      int T, int64_t n_tiles, int32_t* out) {
@@ -212,6 +329,69 @@ int u3d_down_rulebook(const int32_t* coords, int64_t n, const uint64_t* bitmap2,
     hipLaunchKernelGGL(down_nbr_k, dim3(nblk), dim3(RB_T), 0, s, coords, n, ix, val);
     // rows = input (child) voxel, value = output (parent) row
     return compact(val, n, 8, n, pair_in, pair_out, counts, bc, bb, s);
+}
+
+int u3d_conv_out_shape(const int32_t* geom, int X, int Y, int Z, int32_t* out_shape) {
+    ConvGeom g;
+    if (!out_shape) return U3D_EINVAL;
+    const int rc = conv_geom(geom, X, Y, Z, &g);
+    if (rc != U3D_OK) return rc;
+    for (int a = 0; a < 3; ++a) out_shape[a] = g.out[a];
+    return U3D_OK;
+}
+
+int u3d_conv_mark(const int32_t* coords, int64_t n, const int32_t* geom, int B, int X, int Y, int Z, uint64_t* bitmap_out, int64_t* cells_out,
+                  u3d_stream_t stream) {
+    ConvGeom g;
+    const int rc = conv_geom(geom, X, Y, Z, &g);
+    if (rc != U3D_OK) return rc;
+    if (!coords || n <= 0 || B <= 0 || (bitmap_out != nullptr) == (cells_out != nullptr)) {
+        set_error("conv_mark: needs rows, a batch size and exactly one of bitmap_out / cells_out");
+        return U3D_EINVAL;
+    }
+    if (g.out[0] <= 0 || g.out[1] <= 0 || g.out[2] <= 0) { set_error("conv_mark: the output level is empty (%d x %d x %d)", g.out[0], g.out[1], g.out[2]); return U3D_EINVAL; }
+    const int64_t zw = (g.out[2] + 63) / 64;
+    const long double words = (long double)B * g.out[0] * g.out[1] * zw;
+    if (bitmap_out ? words > (long double)U3D_INDEX_MAX_WORDS : words * 64 >= 4.0e18L) {
+        set_error("conv_mark: output grid %d x %d x %d x %d is too large for the %s index", B, g.out[0], g.out[1], g.out[2], bitmap_out ? "direct-address" : "hashed");
+        return U3D_EUNSUPPORTED;
+    }
+    if (n >= 0x7fffffffLL / g.K) { set_error("conv_mark: %lld rows x %d offsets exceed 32-bit counts", (long long)n, g.K); return U3D_EUNSUPPORTED; }
+    hipLaunchKernelGGL(conv_mark_k, dim3((unsigned)ceil_div(n, RB_T), g.K), dim3(RB_T), 0, (hipStream_t)stream, coords, n, g, B, (int)zw,
+                       (unsigned long long*)bitmap_out, cells_out);
+    return check_launch("conv_mark");
+}
+
+int64_t u3d_conv_rulebook_ws_bytes(int64_t n_out, int K) {
+    if (n_out <= 0 || K <= 0 || K > 27) return 0;
+    return (2 * K * ceil_div(n_out, RB_T) + 64) * 4;      // block counts + bases
+}
+
+int u3d_conv_rulebook(const int32_t* out_coords, int64_t n_out, int64_t n_in, const uint64_t* bitmap_in, const int32_t* word_rank_in,
+                      int64_t hash_slots, int B, int X, int Y, int Z, const int32_t* geom, int64_t cap, int32_t* pair_in, int32_t* pair_out,
+                      int32_t* counts, void* ws, u3d_stream_t stream) {
+    ConvGeom g;
+    const int rc = conv_geom(geom, X, Y, Z, &g);
+    if (rc != U3D_OK) return rc;
+    if (!out_coords || !bitmap_in || !word_rank_in || !pair_in || !pair_out || !counts || !ws || n_out <= 0 || n_in <= 0 || B <= 0 || hash_slots < 0) {
+        set_error("conv_rulebook: null argument or non-positive row count");
+        return U3D_EINVAL;
+    }
+    if (cap < (n_in < n_out ? n_in : n_out)) {
+        set_error("conv_rulebook: cap %lld is below min(n_in %lld, n_out %lld)", (long long)cap, (long long)n_in, (long long)n_out);
+        return U3D_EINVAL;
+    }
+    if (n_out >= 0x7fffffffLL || n_in >= 0x7fffffffLL) { set_error("conv_rulebook: row counts exceed int32"); return U3D_EUNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(U3D_K_RULEBOOK, s, 0.0);
+    const Index ix = make_index(bitmap_in, word_rank_in, B, X, Y, Z, hash_slots);
+    const int nblk = (int)ceil_div(n_out, RB_T);
+    int32_t* bc = (int32_t*)ws;
+    int32_t* bb = bc + (int64_t)g.K * nblk;
+    hipLaunchKernelGGL(conv_count_k, dim3(nblk, g.K), dim3(RB_T), 0, s, out_coords, n_out, g, ix, nblk, bc);
+    hipLaunchKernelGGL(rb_scan_k, dim3(g.K), dim3(RB_T), 0, s, (const int32_t*)bc, nblk, bb, counts);
+    hipLaunchKernelGGL(conv_write_k, dim3(nblk, g.K), dim3(RB_T), 0, s, out_coords, n_out, g, ix, nblk, (const int32_t*)bb, cap, pair_out, pair_in);
+    return check_launch("conv rulebook");
 }
 
 int u3d_tile_starts(const int32_t* rows, const int32_t* counts, int K, int64_t cap, int tile_rows, int64_t n_tiles,

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import operator
 import os
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -150,7 +151,8 @@ class Rulebook:
         self._tiles: Dict = {}
         self._total = None
         self.tag = None             # set by the layer that caches it (indice_key): lets the tile lists follow last step's use
-        self.coords = self.index = None      # SubM rulebooks: the level's voxels and occupancy index (tile-stationary kernel's tables)
+        self.coords = self.index = None      # SubM k=3 / dilation 1 rulebooks ONLY: the level's voxels and occupancy index (tile-stationary kernel's tables)
+        self.geom = None            # set by the layer that caches it: the layer geometry it was built for (a shared indice_key must agree)
         self._halo: Dict = {}
 
     def _tile_starts(self, role: str, T: int) -> torch.Tensor:
@@ -217,9 +219,10 @@ class Rulebook:
     @property
     def total_pairs(self) -> int:
         """Number of rulebook pairs (flops accounting).  Host read-back, cached by geometry so a bench
-        that replays the same scenes does not synchronise inside its timed region."""
+        that replays the same scenes does not synchronise inside its timed region.  The layer geometry is part of the key: two
+        rulebooks of one level (SubM k=3 with dilation 1 and 2) share K and both row counts, not their pairs."""
         if self._total is None:
-            key = (self.K, self.n_in, self.n_out)
+            key = (self.K, self.n_in, self.n_out, self.geom)
             if key not in _PAIR_CACHE:
                 _PAIR_CACHE[key] = int(self.counts.sum().item())
             self._total = _PAIR_CACHE[key]
@@ -261,6 +264,94 @@ def build_down_rulebook(coords: torch.Tensor, B: int, shape):
     L.call('u3d_down_rulebook', L.ptr(coords), n, *ix2.table(), B, *oshape,
            L.ptr(pin), L.ptr(pout), L.ptr(cnt), L.ptr(w), L.stream())
     return oc, oshape, ix2, Rulebook(pin, pout, cnt, 8, n, n2)
+
+
+def _triple(v, what: str):
+    """an integer or a 3-sequence of integers (anything with ``__index__``: Python ints, numpy integer scalars; no bools, no floats)
+    -> (a, b, c) of Python ints"""
+    def as_int(a):
+        if isinstance(a, bool):
+            raise TypeError
+        return operator.index(a)
+    try:
+        try:
+            a = as_int(v)
+            return (a, a, a)
+        except TypeError:
+            t = tuple(as_int(a) for a in v)
+    except TypeError:
+        t = ()
+    if len(t) != 3:
+        raise L.U3DError(f'sparse conv: {what} must be an int or a sequence of three ints, got {v!r}')
+    return t
+
+
+def conv_geometry(kernel_size, stride=1, padding=0, dilation=1):
+    """(k0, k1, k2, s0, s1, s2, p0, p1, p2, d0, d1, d2) of a layer, refused where the geometry kernels (csrc/rulebook.hip) have no form
+    for it: 1 <= kernel extent <= 3, stride >= 1, padding >= 0, dilation >= 1 on every axis."""
+    k, s, p, d = _triple(kernel_size, 'kernel_size'), _triple(stride, 'stride'), _triple(padding, 'padding'), _triple(dilation, 'dilation')
+    if not all(1 <= a <= 3 for a in k):
+        raise L.U3DError(f'sparse conv: kernel_size {k}: every kernel extent must satisfy 1 <= extent <= 3 (K = 27 offsets at most)')
+    if not all(a >= 1 for a in s):
+        raise L.U3DError(f'sparse conv: stride {s}: every stride must be >= 1')
+    if not all(a >= 0 for a in p):
+        raise L.U3DError(f'sparse conv: padding {p}: every padding must be >= 0')
+    if not all(a >= 1 for a in d):
+        raise L.U3DError(f'sparse conv: dilation {d}: every dilation must be >= 1')
+    return (*k, *s, *p, *d)
+
+
+def _geom_array(geom):
+    return (ctypes.c_int * 12)(*geom)
+
+
+def conv_out_shape(geom, shape):
+    """per axis floor((in + 2 p - d (k - 1) - 1) / s) + 1, 0 where that is not positive (u3d_conv_out_shape, host only)"""
+    out = (ctypes.c_int * 3)()
+    L.call('u3d_conv_out_shape', _geom_array(geom), *[int(s) for s in shape], out)
+    return [int(v) for v in out]
+
+
+def build_conv_rulebook(coords: torch.Tensor, index: OccupancyIndex, B: int, shape, geom, subm: bool = False):
+    """General geometry (csrc/rulebook.hip, conv_mark_k / conv_count_k / conv_write_k): kernel extents 1..3, any stride / padding /
+    dilation, spconv's rule.  ``index``: the occupancy index of the INPUT level ``coords``.  ``subm``: the output set is the input set
+    (``geom`` then carries stride 1 and the padding d (k - 1) / 2).  Returns (out_coords, out_shape, out_index, Rulebook).
+    The rulebook's lists are [K, cap] with cap = min(n_in, n_out) (at least 1): for a fixed offset the pairs are a monotone partial
+    bijection between the two levels, so both columns ascend and neither side has more pairs than rows.  It leaves ``Rulebook.coords`` /
+    ``index`` unset: those mean "SubM k=3, dilation 1" to the tile-stationary kernels (``_conv_route``)."""
+    n, dev = coords.shape[0], coords.device
+    shape = [int(s) for s in shape]
+    K = geom[0] * geom[1] * geom[2]
+    g = _geom_array(geom)
+    if subm:
+        oc, oshape, ix_out, n2 = coords, shape, index, n
+    else:
+        oshape = conv_out_shape(geom, shape)
+        if min(oshape) <= 0:
+            raise L.U3DError(f'sparse conv: spatial shape {shape} is smaller than the reach of kernel {tuple(geom[:3])} with dilation '
+                             f'{tuple(geom[9:])} and padding {tuple(geom[6:9])}: the output level would have extent {oshape}')
+        if OccupancyIndex.wants_hash(B, oshape):
+            cells = torch.empty(K * n, dtype=torch.int64, device=dev)
+            if n:
+                L.call('u3d_conv_mark', L.ptr(coords), n, g, B, *shape, None, L.ptr(cells), L.stream())
+            ix_out = OccupancyIndex.from_cells(cells, B, oshape)
+        else:
+            ix_out = OccupancyIndex.alloc(B, oshape, dev)
+            if n:
+                L.call('u3d_conv_mark', L.ptr(coords), n, g, B, *shape, L.ptr(ix_out.bitmap), None, L.stream())
+            ix_out.build_rank()
+        n2 = ix_out.count()
+        oc = ix_out.coords(n2)
+    cap = max(1, min(n, n2))
+    pin = torch.empty(K, cap, dtype=torch.int32, device=dev)
+    pout = torch.empty(K, cap, dtype=torch.int32, device=dev)
+    if n and n2:
+        cnt = torch.empty(K, dtype=torch.int32, device=dev)
+        w = L.ws(L.lib().u3d_conv_rulebook_ws_bytes(n2, K), dev)
+        L.call('u3d_conv_rulebook', L.ptr(oc), n2, n, *index.table(), B, *shape, g, cap, L.ptr(pin), L.ptr(pout), L.ptr(cnt), L.ptr(w), L.stream())
+    else:               # an empty level on either side: no pairs (the C entry points take n > 0 only)
+        cnt = torch.zeros(K, dtype=torch.int32, device=dev)
+    return oc, oshape, ix_out, Rulebook(pin, pout, cnt, K, n, n2)
 
 
 # ----------------------------------------------------------------------------------------
@@ -425,7 +516,7 @@ class WeightPacks:
             self.bufs = {}
             for m in self.convs:
                 w = m.weight
-                K = m.kernel_size ** 3
+                K = m.K
                 for transposed, (Cd, Cs) in ((0, (m.out_channels, m.in_channels)), (1, (m.in_channels, m.out_channels))):
                     if Cd % 32 or Cs % 16:
                         continue
@@ -536,7 +627,9 @@ def _conv_route(Cs, Cd, n_dst, rb, bf, has_rows, want_stats):
       'pairs'  the pair-list kernels (_GMM_ENTRY, or u3d_spconv_gmm_bf16a on bf16 rows); plan = (R, G, gathers bf16 rows).  Source
                channel counts that are not a multiple of 32 (the 6 -> 32 input convolution, padded to 16) stay on the fp32 kernel.
     The first three are SubM-only experiments behind their toggles, tried in that order; only the pair kernels' epilogue can write the
-    batch-norm statistics, so 'rs' / 'ts' step aside when those are wanted (``want_stats`` under _EPILOGUE_STATS)."""
+    batch-norm statistics, so 'rs' / 'ts' step aside when those are wanted (``want_stats`` under _EPILOGUE_STATS).
+    They read ``rb.coords`` / ``rb.index`` as "the 27 neighbours of SubM k=3, dilation 1" (u3d_subm_halo): a general or dilated rulebook
+    (``build_conv_rulebook``) must never set them -- it would get that layer's neighbours, not its own -- and so always lands on 'pairs'."""
     bf = int(bf)
     subm32 = rb.coords is not None and Cs % 32 == 0
     rs_shape = subm32 and Cd % 32 == 0 and n_dst >= _RS_MIN_ROWS and (Cs // 32) * (Cd // 32) <= _RS_MAX_BLOCKS
@@ -580,6 +673,8 @@ def _gmm(src, weight, transposed, rb, gather, scatter, role, n_dst, addend, flop
     dst = torch.empty(n_dst, Cd, dtype=torch.float32, device=src.device)
     if not n_dst:
         return dst
+    if not src.shape[0]:        # an empty source level (a strided convolution without output rows, read back by its inverse / input gradient): no pairs
+        return dst.zero_() if addend is None else dst.copy_(addend)
     route, fmt, plan = _conv_route(Cs, Cd, n_dst, rb, bf, src_rows_bf16 is not None, stats is not None)
     if _PROFILE_FLOPS:      # N(Cs+Cd)s + 2P*idx + K*Cs*Cd*s  (s = 4 B, idx = 4 B)
         account.add('conv_gmm', flops, 4.0 * (src.shape[0] * Cs + n_dst * Cd) + 8.0 * rb.total_pairs + 4.0 * rb.K * Cs * Cd)
@@ -669,7 +764,9 @@ class _SparseConvFn(torch.autograd.Function):
         flops = 2.0 * rb.total_pairs * cin * cout if _PROFILE_FLOPS else 0.0
         side = None
         dout_shadow = shadow_of(dout) if ctx.bf == P.FMT_BF16 and P.bf16_rows() and cout % 32 == 0 else None
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and not (dout.shape[0] and src.shape[0]):
+            dw = torch.zeros_like(weight)        # an empty level on either side: no pairs, no launch
+        elif ctx.needs_input_grad[1]:
             dw = torch.empty_like(weight)
             rx, rg, role, n_dy = _roles(rb, mode)
             if _PROFILE_FLOPS:
@@ -1135,14 +1232,27 @@ def _pad16(f):
 
 
 class _ConvBase(SparseModule):
-    def __init__(self, in_channels, out_channels, kernel_size, bias=False, indice_key=None):
+    """Weight [C_out, k0, k1, k2, C_in] and the layer geometry (``conv_geometry``: each of kernel_size / stride / padding / dilation an int
+    or a 3-sequence).  ``kernel_size`` keeps the int of a cubic kernel (a tuple otherwise); ``K`` is the number of offsets."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, bias=False, indice_key=None, stride=1, padding=0, dilation=1):
         super().__init__()
         if bias:
             raise L.U3DError('bias=True is not used by the reference configs and not built')
-        k = kernel_size
-        self.in_channels, self.out_channels, self.kernel_size, self.indice_key = in_channels, out_channels, k, indice_key
-        self.weight = nn.Parameter(torch.empty(out_channels, k, k, k, in_channels))
+        self.geom = conv_geometry(kernel_size, stride, padding, dilation)
+        k = self.geom[:3]
+        self.in_channels, self.out_channels, self.indice_key = in_channels, out_channels, indice_key
+        self.kernel_size = k[0] if k[0] == k[1] == k[2] else k
+        self.stride, self.padding, self.dilation = self.geom[3:6], self.geom[6:9], self.geom[9:]
+        self.K = k[0] * k[1] * k[2]
+        self.weight = nn.Parameter(torch.empty(out_channels, *k, in_channels))
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
+
+    def _agree(self, rb: Rulebook, mine):
+        """a rulebook found under this layer's ``indice_key`` must have been built for this layer's geometry"""
+        if rb.geom is not None and rb.geom != mine:
+            raise L.U3DError(f'{type(self).__name__}: indice_key {self.indice_key!r} holds a rulebook built for geometry {rb.geom}, this layer '
+                             f'has {mine}: layers that share an indice_key must share kernel_size, stride, padding and dilation')
 
     def _w16(self):
         c = self.in_channels
@@ -1160,12 +1270,22 @@ class _ConvBase(SparseModule):
 
 
 class SubMConv3d(_ConvBase):
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None):
-        super().__init__(in_channels, out_channels, kernel_size, bias, indice_key)
-        assert kernel_size in (1, 3)
+    """Submanifold convolution: the output set is the input set.  Kernel extents 1 or 3 per axis (odd, as in spconv), any dilation;
+    ``stride`` / ``padding`` are accepted and, as in spconv, without effect: the effective padding is d (k - 1) / 2.
+    k = 3 with dilation 1 builds the hard-coded 27-neighbour rulebook (``build_subm_rulebook``), the all-ones kernel is a dense GEMM,
+    everything else goes through the general builder."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=False, indice_key=None):
+        super().__init__(in_channels, out_channels, kernel_size, bias, indice_key, stride, padding, dilation)
+        k, d = self.geom[:3], self.geom[9:]
+        if not all(a in (1, 3) for a in k):
+            raise L.U3DError(f'SubMConv3d: kernel_size {k}: every kernel extent must be 1 or 3 (odd extents only, as in spconv)')
+        self.general = not (k == (3, 3, 3) and d == (1, 1, 1))
+        self._rb_geom = ('subm', k, d)
+        self._subm_geom = (*k, 1, 1, 1, *[d[a] * (k[a] - 1) // 2 for a in range(3)], *d)
 
     def forward(self, x: SparseConvTensor, addend: Optional[torch.Tensor] = None) -> SparseConvTensor:
-        if self.kernel_size == 1:
+        if self.K == 1:
             # 1x1 skip convolution = [N, Cin] x [Cin, Cout] GEMM, no rulebook (K5): the decoder's fp32 MFMA GEMM kernels (the
             # library picked a 0.6 ms kernel for the level-1 weight gradient, a [64 x 356k] x [356k x 32] product)
             y = dense.linear(x.features, self.weight.view(self.out_channels, self.in_channels))
@@ -1176,39 +1296,69 @@ class SubMConv3d(_ConvBase):
         key = self.indice_key if self.indice_key is not None else ('__subm__', id(self))
         rb = x.indice_dict.get(key)
         if rb is None:
-            rb = build_subm_rulebook(x.indices, x.index)
+            if self.general:
+                rb = build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, self._subm_geom, subm=True)[3]
+            else:
+                rb = build_subm_rulebook(x.indices, x.index)
+            rb.geom = self._rb_geom
             rb.tag = ('subm', key) if isinstance(key, str) else None
             x.indice_dict[key] = rb
+        elif not isinstance(rb, Rulebook):
+            raise L.U3DError(f'SubMConv3d: indice_key {self.indice_key!r} is taken by a strided convolution')
+        else:
+            self._agree(rb, self._rb_geom)
         return rb
 
 
 class SparseConv3d(_ConvBase):
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False, indice_key=None):
-        super().__init__(in_channels, out_channels, kernel_size, bias, indice_key)
-        assert kernel_size == 2 and stride == 2 and padding == 0, 'only k=2,s=2 is on the hot path'
+    """Regular sparse convolution: kernel extents 1..3, any stride / padding / dilation.  k = 2, s = 2, p = 0 (the U-Net's) builds the
+    hard-coded parity rulebook (``build_down_rulebook``), everything else goes through the general builder."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=False, indice_key=None):
+        super().__init__(in_channels, out_channels, kernel_size, bias, indice_key, stride, padding, dilation)
+        self.general = self.geom != (2, 2, 2, 2, 2, 2, 0, 0, 0, 1, 1, 1)
+        self._rb_geom = ('conv', *self.geom)
 
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
         oc, oshape, ix2, rb = self.geometry(x)
         return SparseConvTensor(self._conv(x, rb, 'fwd'), oc, oshape, x.batch_size, x.indice_dict, ix2)
 
     def geometry(self, x: SparseConvTensor):
-        """Coarser level + rulebook for this conv; cached in ``indice_dict`` (the inverse conv reads the
-        same entry), so it can be built ahead of the feature pass (``prepare_geometry``)."""
-        key = ('__down__', self.indice_key)
+        """Output level + rulebook for this conv; cached in ``indice_dict`` (the inverse conv reads the
+        same entry), so it can be built ahead of the feature pass (``prepare_geometry``).  A layer without an ``indice_key`` caches under
+        its own identity: nothing else can pick its rulebook up."""
+        name = self.indice_key if self.indice_key is not None or not self.general else ('__anon__', id(self))
+        key = ('__down__', name)
         if key not in x.indice_dict:
-            oc, oshape, ix2, rb = build_down_rulebook(x.indices, x.batch_size, x.spatial_shape)
-            rb.tag = key
+            if self.general:
+                oc, oshape, ix2, rb = build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, self.geom)
+            else:
+                oc, oshape, ix2, rb = build_down_rulebook(x.indices, x.batch_size, x.spatial_shape)
+            rb.geom = self._rb_geom
+            rb.tag = key if not isinstance(name, tuple) else None
             x.indice_dict[key] = (oc, oshape, ix2, rb)
-            x.indice_dict[self.indice_key] = (rb, x.indices, x.spatial_shape, x._index)
+            if not isinstance(name, tuple):
+                x.indice_dict[name] = (rb, x.indices, x.spatial_shape, x._index)
+        else:
+            self._agree(x.indice_dict[key][3], self._rb_geom)
         return x.indice_dict[key]
 
 
 class SparseInverseConv3d(_ConvBase):
+    """Undoes the ``SparseConv3d`` found under its ``indice_key``, whatever that layer's geometry: the saved pairs with the roles
+    swapped (mode 'inv'), output on the strided convolution's input level.  ``kernel_size`` must be that layer's."""
+
     def __init__(self, in_channels, out_channels, kernel_size, indice_key=None, bias=False):
         super().__init__(in_channels, out_channels, kernel_size, bias, indice_key)
 
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
-        if self.indice_key not in x.indice_dict:
+        entry = x.indice_dict.get(self.indice_key)
+        if entry is None:
             raise L.U3DError(f'SparseInverseConv3d: no rulebook saved under {self.indice_key!r}')
-        rb, idx, shape, index = x.indice_dict[self.indice_key]
+        if isinstance(entry, Rulebook):
+            raise L.U3DError(f'SparseInverseConv3d: indice_key {self.indice_key!r} belongs to a SubMConv3d, not to a SparseConv3d')
+        rb, idx, shape, index = entry
+        if rb.geom is not None and tuple(rb.geom[1:4]) != self.geom[:3]:
+            raise L.U3DError(f'SparseInverseConv3d: kernel_size {self.geom[:3]} differs from kernel_size {tuple(rb.geom[1:4])} of the '
+                             f'SparseConv3d saved under {self.indice_key!r}')
         return SparseConvTensor(self._conv(x, rb, 'inv'), idx, shape, x.batch_size, x.indice_dict, index)

@@ -233,7 +233,8 @@ def fusion_plan(unet, first_producer=None, last_consumer=None) -> FusionPlan:
         plan.names[sink[0]] = '<last_consumer>'
     for name, m in unet.named_modules():
         plan.names[m] = name or '<unet>'
-    if not _plan_level(plan, unet, feed, sink):
+    # (a layer of the general geometry -- any kernel / stride / padding / dilation but the U-Net's own -- runs unfused: the whole plan steps aside)
+    if not _plan_level(plan, unet, feed, sink) or any(getattr(c, 'general', False) for c in plan.convs):
         plan = FusionPlan(unet)
     for conv, e in plan.convs.items():          # at most two activated outputs per launch
         for norm, _, _ in e.acts[2:]:
