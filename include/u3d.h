@@ -439,6 +439,38 @@ int u3d_segment_minmax_xyz(const float* points, int pt_ld, const int64_t* ids, i
                            u3d_stream_t stream);
 
 /* =====================================================================================
+ * P1  Sparse max / average pooling over a convolution rulebook (spconv's SparseMaxPool3d / SparseAvgPool3d; csrc/sparse_pool.hip).
+ *     Geometry: R3g's, offsets in the order (t0 k1 + t1) k2 + t2; every output row has at least one pair.
+ *   u3d_pair_table: the destination-major view of K pair lists.  pair_key / pair_val int32 [K, cap], counts int32 [K]; table int32
+ *     [n, K] receives table[pair_key[k][i]][k] = pair_val[k][i] for i < counts[k] and -1 everywhere else (every entry is written;
+ *     4 K n bytes).  Race-free because for a fixed offset no row repeats (u3d_conv_rulebook).  With (key, val) = (pair_out, pair_in),
+ *     n = n_out it gives each output row its inputs, with (pair_in, pair_out), n = n_in each input row its outputs.
+ *   u3d_sparse_pool_fwd (x [n_in, C], table_out [n_out, K]):
+ *     max: y[j, c] = the maximum over the inputs PRESENT in the window of j -- an absent cell is not a zero.  Selection: walk the offsets
+ *       in ascending index; take the first value; replace the held value only if the new one is > it, or if the new one is NaN and the
+ *       held one is not.  So the first maximal element wins a tie, +0.0 and -0.0 do not replace each other, a NaN in the window gives NaN.
+ *       y holds the BITS of the selected element, arg uint8 [n_out, C] its offset index.  count is not touched.
+ *     avg: y[j, c] = (sum of the present inputs in ascending offset order) / count[j]; count int32 [n_out] receives the number of pairs of
+ *       each row.  arg is not touched.
+ *   u3d_sparse_pool_bwd (dy [n_out, C], table_in [n_in, K]), every dx element written once (an input row without outputs gets 0):
+ *     max: dx[i, c] = sum over the offsets k, ascending, of dy[j_k, c] for the outputs j_k = table_in[i][k] with arg[j_k, c] == k: a tie
+ *       sends the gradient to the one selected element (torch's dense rule).
+ *     avg: dx[i, c] = sum over k, ascending, of dy[j_k, c] * (1 / count[j_k]).
+ *   No floating-point atomics, one summation order: results are bit-reproducible.  The unused one of arg / count may be NULL.
+ *   Contract: C % 4 == 0, 4 <= C <= 512, 1 <= K <= 27, mode U3D_POOL_MAX or U3D_POOL_AVG; rows past n are not touched.  Errors, before
+ *   any HIP call and with a u3d_last_error text: U3D_EINVAL for NULL pointers, n <= 0, cap <= 0 and an unknown mode; U3D_EUNSUPPORTED
+ *   for other widths or offset counts and for n max(C, K) >= 2^31.  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+#define U3D_POOL_MAX 0
+#define U3D_POOL_AVG 1
+int u3d_pair_table(const int32_t* pair_key, const int32_t* pair_val, const int32_t* counts, int K, int64_t cap, int64_t n, int32_t* table,
+                   u3d_stream_t stream);
+int u3d_sparse_pool_fwd(const float* x, const int32_t* table_out, int64_t n_out, int K, int C, int mode, float* y,
+                        uint8_t* arg /* max only */, int32_t* count /* avg only */, u3d_stream_t stream);
+int u3d_sparse_pool_bwd(const float* dy, const int32_t* table_in, int64_t n_in, int K, int C, int mode, const uint8_t* arg /* max only */,
+                        const int32_t* count /* avg only */, float* dx, u3d_stream_t stream);
+
+/* =====================================================================================
  * K13  self-attention core of nn.MultiheadAttention(256, 8, batch_first) per scene
  *     (unidet3d/encoder.py:19-20,36-37): softmax(Q K^T / sqrt(hd)) V over packed variable
  *     length scenes.  qkv [n_total, 3*H*hd] (the in_proj output), cu_seqlens int32 [B+1],

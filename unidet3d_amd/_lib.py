@@ -114,6 +114,10 @@ PROTOTYPES = {
     'u3d_csr_build': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'u3d_csr_build_ws_bytes': (_i64, [_i64, _i64]),
     'u3d_gather_i64_to_i32': (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    # sparse pooling over a rulebook (csrc/sparse_pool.hip; added entry points, same ABI version)
+    'u3d_pair_table': (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp]),
+    'u3d_sparse_pool_fwd': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'u3d_sparse_pool_bwd': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'u3d_segment_gather_sum': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     'u3d_segment_mean_xyz': (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'u3d_segment_minmax_xyz': (_i32, [_vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
@@ -197,6 +201,7 @@ PROTOTYPES = {
 
 ABI_VERSION = 117         # include/u3d.h U3D_ABI_VERSION this table was written against
 EP_RELU, EP_BF16_ROWS = 1, 2      # include/u3d.h U3D_EP_*: the flag word of an activated output of u3d_conv_epilogue
+POOL_MAX, POOL_AVG = 0, 1         # include/u3d.h U3D_POOL_*: the mode of u3d_sparse_pool_fwd / _bwd
 
 K_CONV_FWD, K_CONV_WGRAD, K_BN, K_POOL, K_ATTN_FWD, K_ATTN_BWD, K_RULEBOOK, K_VOXELIZE, K_GEMM = range(9)
 

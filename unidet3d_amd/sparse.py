@@ -6,7 +6,8 @@ Mirrors the subset of ``spconv.pytorch`` the reference uses
 replace_feature / per-forward ``indice_dict`` rulebook cache keyed by
 ``indice_key``), ``SparseSequential``, ``SubMConv3d``, ``SparseConv3d``,
 ``SparseInverseConv3d``; plus the BatchNorm the reference takes from torch
-(``nn.SyncBatchNorm`` / ``nn.BatchNorm1d``).  Same constructor arguments,
+(``nn.SyncBatchNorm`` / ``nn.BatchNorm1d``), and spconv's ``SparseMaxPool3d`` /
+``SparseAvgPool3d`` on the strided convolution's geometry.  Same constructor arguments,
 same parameter names and weight layout ``[C_out, k, k, k, C_in]``.
 
 Every compute step is a call through the C ABI (include/u3d.h); there is no
@@ -154,6 +155,28 @@ class Rulebook:
         self.coords = self.index = None      # SubM k=3 / dilation 1 rulebooks ONLY: the level's voxels and occupancy index (tile-stationary kernel's tables)
         self.geom = None            # set by the layer that caches it: the layer geometry it was built for (a shared indice_key must agree)
         self._halo: Dict = {}
+        self._nbr: Dict = {}
+
+    def neighbours(self, role: str) -> torch.Tensor:
+        """The destination-major view of the pair lists (u3d_pair_table) the pooling kernels walk: int32 [n, K], entry [r, k] = the row
+        paired with r at offset k, or -1.  role 'out': n = n_out, each output row's inputs; 'in': n = n_in, each input row's outputs.
+        Built once per rulebook and role (4 K n bytes); remembered like the tile lists so that the next step's rulebook builds it ahead."""
+        if role not in ('out', 'in'):
+            raise L.U3DError(f"Rulebook.neighbours: role must be 'out' or 'in', got {role!r}")
+        if self.tag is not None:
+            _TILE_HISTORY.setdefault(self.tag, set()).add(('nbr', role))
+        return self._neighbours(role)
+
+    def _neighbours(self, role: str) -> torch.Tensor:
+        if role not in self._nbr:
+            key, val, n, m = (self.pair_out, self.pair_in, self.n_out, self.n_in) if role == 'out' else (self.pair_in, self.pair_out, self.n_in, self.n_out)
+            if n and m:
+                t = torch.empty(n, self.K, dtype=torch.int32, device=key.device)
+                L.call('u3d_pair_table', L.ptr(key), L.ptr(val), L.ptr(self.counts), self.K, self.cap, n, L.ptr(t), L.stream())
+            else:           # an empty level on either side: no pairs (the C entry points take n > 0 only)
+                t = torch.full((n, self.K), -1, dtype=torch.int32, device=key.device)
+            self._nbr[role] = t
+        return self._nbr[role]
 
     def _tile_starts(self, role: str, T: int) -> torch.Tensor:
         key = (role, T)
@@ -208,6 +231,8 @@ class Rulebook:
             if key[0] == 'halo':
                 if self.coords is not None and self.n_out > 0:
                     self._halo_tables(key[1], key[2])
+            elif key[0] == 'nbr':
+                self._neighbours(key[1])
             elif len(key) == 2:
                 self._tile_starts(*key)
             else:
@@ -947,6 +972,83 @@ class FusionRun:
 
 
 # ----------------------------------------------------------------------------------------
+# pooling over a rulebook (csrc/sparse_pool.hip, include/u3d.h section P1)
+# ----------------------------------------------------------------------------------------
+_POOL_MODES = {'max': L.POOL_MAX, 'avg': L.POOL_AVG}
+
+
+def _pool_check(x: torch.Tensor, mode: str):
+    if mode not in _POOL_MODES:
+        raise L.U3DError(f"sparse_pool: mode must be 'max' or 'avg', got {mode!r}")
+    if not x.is_cuda:
+        raise L.U3DError('sparse_pool: u3d kernels need CUDA (HIP) tensors: the product path has no CPU fallback')
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise L.U3DError(f'sparse_pool: features must be fp32 [n, C], got {x.dtype} {tuple(x.shape)}')
+    _pool_width(x.shape[1])
+
+
+def _pool_width(C: int):
+    if C % 4 or not 4 <= C <= 512:
+        raise L.U3DError(f'sparse_pool: {C} channels: the gfx950 kernels take a multiple of 4 in 4..512')
+
+
+def sparse_pool_forward(x: torch.Tensor, rb: Rulebook, mode: str):
+    """(y [n_out, C], aux) without autograd: aux is ``arg`` (uint8 [n_out, C], the selected offset of every element) for 'max' and
+    ``count`` (int32 [n_out], the pairs of every row) for 'avg' -- what the backward reads instead of x and y."""
+    _pool_check(x, mode)
+    x = x.contiguous()
+    if x.shape[0] != rb.n_in:
+        raise L.U3DError(f'sparse_pool: {x.shape[0]} feature rows, the rulebook has {rb.n_in} input rows')
+    C, dev = x.shape[1], x.device
+    y = torch.empty(rb.n_out, C, dtype=torch.float32, device=dev)
+    arg = torch.empty(rb.n_out, C, dtype=torch.uint8, device=dev) if mode == 'max' else None
+    count = torch.empty(rb.n_out, dtype=torch.int32, device=dev) if mode == 'avg' else None
+    if rb.n_out:           # (an output row has at least one pair: n_in > 0 as well)
+        L.call('u3d_sparse_pool_fwd', L.ptr(x), L.ptr(rb.neighbours('out')), rb.n_out, rb.K, C, _POOL_MODES[mode], L.ptr(y), L.ptr(arg),
+               L.ptr(count), L.stream())
+    return y, (arg if mode == 'max' else count)
+
+
+def sparse_pool_backward(dy: torch.Tensor, rb: Rulebook, mode: str, aux: torch.Tensor) -> torch.Tensor:
+    """dx [n_in, C] from dy [n_out, C] and the forward's ``aux``; every element is written by the kernel, an empty level launches nothing"""
+    _pool_check(dy, mode)
+    dy = dy.contiguous()
+    C, dev = dy.shape[1], dy.device
+    if not (rb.n_in and rb.n_out):
+        return torch.zeros(rb.n_in, C, dtype=torch.float32, device=dev)
+    dx = torch.empty(rb.n_in, C, dtype=torch.float32, device=dev)
+    arg, count = (aux, None) if mode == 'max' else (None, aux)
+    L.call('u3d_sparse_pool_bwd', L.ptr(dy), L.ptr(rb.neighbours('in')), rb.n_in, rb.K, C, _POOL_MODES[mode], L.ptr(arg), L.ptr(count),
+           L.ptr(dx), L.stream())
+    return dx
+
+
+class _SparsePoolFn(torch.autograd.Function):
+    """Saves the selected offsets (max) or the pair counts (avg), and neither x nor y."""
+
+    @staticmethod
+    def forward(ctx, x, rb: Rulebook, mode: str):
+        y, aux = sparse_pool_forward(x, rb, mode)
+        ctx.save_for_backward(aux)
+        ctx.rb, ctx.mode = rb, mode
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (aux,) = ctx.saved_tensors
+        return sparse_pool_backward(dy, ctx.rb, ctx.mode, aux), None, None
+
+
+def sparse_pool(x: torch.Tensor, rb: Rulebook, mode: str) -> torch.Tensor:
+    """Max / average pooling of the rows x [n_in, C] over the windows of ``rb`` (a strided convolution's rulebook) -> [n_out, C].
+    'max': over the inputs present in a window, first maximal element on a tie, NaN if the window holds one; the gradient goes to the
+    selected element alone.  'avg': sum / number of present inputs.  Fixed summation order, no atomics: bit-reproducible."""
+    _pool_check(x, mode)
+    refuse_rows_only(x, 'sparse_pool')
+    return _SparsePoolFn.apply(x, rb, mode)
+
+
+# ----------------------------------------------------------------------------------------
 # batch norm (+ReLU)
 # ----------------------------------------------------------------------------------------
 def _dist_on():
@@ -1231,6 +1333,40 @@ def _pad16(f):
     return f if c % 16 == 0 else F.pad(f, (0, 16 - c % 16))
 
 
+_DOWN_K2S2 = (2, 2, 2, 2, 2, 2, 0, 0, 0, 1, 1, 1)      # the U-Net's strided layer: the hard-coded parity rulebook (``build_down_rulebook``)
+
+
+def _agree(layer, rb: Rulebook, mine):
+    """a rulebook found under a layer's ``indice_key`` must have been built for that layer's geometry"""
+    if rb.geom is not None and rb.geom != mine:
+        raise L.U3DError(f'{type(layer).__name__}: indice_key {layer.indice_key!r} holds a rulebook built for geometry {rb.geom}, this layer '
+                         f'has {mine}: layers that share an indice_key must share kernel_size, stride, padding and dilation')
+
+
+def strided_geometry(layer, x: 'SparseConvTensor'):
+    """(out_coords, out_shape, out_index, Rulebook) of a layer that moves to a new level -- ``SparseConv3d`` and the pooling layers, which
+    consume exactly the same geometry: ``layer.geom`` (the 12 integers of ``conv_geometry``) and ``layer.indice_key``.  Cached in
+    ``indice_dict`` (the inverse conv reads the same entry), so it can be built ahead of the feature pass (``prepare_geometry``), and a
+    pool and a convolution that share a key and a geometry share one rulebook.  A layer without an ``indice_key`` caches under its own
+    identity: nothing else can pick its rulebook up."""
+    general, mine = layer.geom != _DOWN_K2S2, ('conv', *layer.geom)
+    name = layer.indice_key if layer.indice_key is not None or not general else ('__anon__', id(layer))
+    key = ('__down__', name)
+    if key not in x.indice_dict:
+        if general:
+            oc, oshape, ix2, rb = build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, layer.geom)
+        else:
+            oc, oshape, ix2, rb = build_down_rulebook(x.indices, x.batch_size, x.spatial_shape)
+        rb.geom = mine
+        rb.tag = key if not isinstance(name, tuple) else None
+        x.indice_dict[key] = (oc, oshape, ix2, rb)
+        if not isinstance(name, tuple):
+            x.indice_dict[name] = (rb, x.indices, x.spatial_shape, x._index)
+    else:
+        _agree(layer, x.indice_dict[key][3], mine)
+    return x.indice_dict[key]
+
+
 class _ConvBase(SparseModule):
     """Weight [C_out, k0, k1, k2, C_in] and the layer geometry (``conv_geometry``: each of kernel_size / stride / padding / dilation an int
     or a 3-sequence).  ``kernel_size`` keeps the int of a cubic kernel (a tuple otherwise); ``K`` is the number of offsets."""
@@ -1249,10 +1385,7 @@ class _ConvBase(SparseModule):
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
 
     def _agree(self, rb: Rulebook, mine):
-        """a rulebook found under this layer's ``indice_key`` must have been built for this layer's geometry"""
-        if rb.geom is not None and rb.geom != mine:
-            raise L.U3DError(f'{type(self).__name__}: indice_key {self.indice_key!r} holds a rulebook built for geometry {rb.geom}, this layer '
-                             f'has {mine}: layers that share an indice_key must share kernel_size, stride, padding and dilation')
+        _agree(self, rb, mine)
 
     def _w16(self):
         c = self.in_channels
@@ -1316,7 +1449,7 @@ class SparseConv3d(_ConvBase):
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=False, indice_key=None):
         super().__init__(in_channels, out_channels, kernel_size, bias, indice_key, stride, padding, dilation)
-        self.general = self.geom != (2, 2, 2, 2, 2, 2, 0, 0, 0, 1, 1, 1)
+        self.general = self.geom != _DOWN_K2S2
         self._rb_geom = ('conv', *self.geom)
 
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
@@ -1324,24 +1457,43 @@ class SparseConv3d(_ConvBase):
         return SparseConvTensor(self._conv(x, rb, 'fwd'), oc, oshape, x.batch_size, x.indice_dict, ix2)
 
     def geometry(self, x: SparseConvTensor):
-        """Output level + rulebook for this conv; cached in ``indice_dict`` (the inverse conv reads the
-        same entry), so it can be built ahead of the feature pass (``prepare_geometry``).  A layer without an ``indice_key`` caches under
-        its own identity: nothing else can pick its rulebook up."""
-        name = self.indice_key if self.indice_key is not None or not self.general else ('__anon__', id(self))
-        key = ('__down__', name)
-        if key not in x.indice_dict:
-            if self.general:
-                oc, oshape, ix2, rb = build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, self.geom)
-            else:
-                oc, oshape, ix2, rb = build_down_rulebook(x.indices, x.batch_size, x.spatial_shape)
-            rb.geom = self._rb_geom
-            rb.tag = key if not isinstance(name, tuple) else None
-            x.indice_dict[key] = (oc, oshape, ix2, rb)
-            if not isinstance(name, tuple):
-                x.indice_dict[name] = (rb, x.indices, x.spatial_shape, x._index)
-        else:
-            self._agree(x.indice_dict[key][3], self._rb_geom)
-        return x.indice_dict[key]
+        """Output level + rulebook for this conv (``strided_geometry``)"""
+        return strided_geometry(self, x)
+
+
+class _PoolBase(SparseModule):
+    """spconv's SparseMaxPool3d / SparseAvgPool3d: the geometry of a ``SparseConv3d`` with the same kernel_size / stride / padding /
+    dilation (``strided_geometry``: same cache entries, so a convolution or a ``SparseInverseConv3d`` under the same ``indice_key``
+    finds this layer's rulebook), ``stride=None`` meaning stride = kernel_size.  No parameters."""
+    mode = None
+
+    def __init__(self, kernel_size, stride=None, padding=0, dilation=1, indice_key=None, subm=False):
+        super().__init__()
+        if subm:
+            raise L.U3DError(f'{type(self).__name__}: subm=True is not built')
+        self.geom = conv_geometry(kernel_size, kernel_size if stride is None else stride, padding, dilation)
+        k = self.geom[:3]
+        self.kernel_size = k[0] if k[0] == k[1] == k[2] else k
+        self.stride, self.padding, self.dilation = self.geom[3:6], self.geom[6:9], self.geom[9:]
+        self.K, self.indice_key = k[0] * k[1] * k[2], indice_key
+
+    def geometry(self, x: SparseConvTensor):
+        return strided_geometry(self, x)
+
+    def forward(self, x: SparseConvTensor) -> SparseConvTensor:
+        _pool_width(x.features.shape[1])
+        oc, oshape, ix2, rb = self.geometry(x)
+        return SparseConvTensor(sparse_pool(x.features, rb, self.mode), oc, oshape, x.batch_size, x.indice_dict, ix2)
+
+
+class SparseMaxPool3d(_PoolBase):
+    """Maximum over the inputs present in each window (an absent cell is not a zero); the gradient goes to the first maximal element."""
+    mode = 'max'
+
+
+class SparseAvgPool3d(_PoolBase):
+    """Sum over the inputs present in each window divided by their number."""
+    mode = 'avg'
 
 
 class SparseInverseConv3d(_ConvBase):
