@@ -192,6 +192,26 @@ int u3d_conv_rulebook(const int32_t* out_coords, int64_t n_out, int64_t n_in, co
                       int32_t* pair_out, int32_t* counts, void* ws, u3d_stream_t stream);
 int64_t u3d_conv_rulebook_ws_bytes(int64_t n_out, int K);
 
+/* =====================================================================================
+ * R3t  Transposed convolution geometry (spconv's SparseConvTranspose3d): R3g's geom [12] plus outpad = int32 [3] on the HOST, the output
+ *      padding.  Per axis out_dim = (in_dim - 1) s - 2 p + d (k - 1) + q + 1 (torch's rule); output cell o is active iff an active input
+ *      i and a tap t in [0, k) give o = i s - p + t d on all three axes with 0 <= o < out_dim.  Offsets and weight layout as in R3g, taps
+ *      not flipped.  (X, Y, Z) are the layer's INPUT extents.
+ *   u3d_convt_out_shape (host only): out_shape int32 [3].
+ *   u3d_convt_mark: the output occupancy of the n input rows, in u3d_conv_mark's two forms (bitmap_out sized by u3d_index_words(B,
+ *     out_shape), or cells_out int64 [K n]); exactly one is non-NULL.
+ *   The pair lists need no entry point of their own: o = i s - p + t d is R3g's relation with the two levels swapped, so
+ *     u3d_conv_rulebook(out_coords = the layer's INPUT rows, the NEW level's index and extents, the same geom) returns them --
+ *     pair_out = layer-input rows, pair_in = new-level rows, both ascending, at most min(n_in, n_out) pairs per offset.
+ *   Errors, before any HIP call and with a u3d_last_error text: everything R3g's validation of k / s / p / d refuses; U3D_EINVAL for
+ *   q < 0 or q >= max(s, d), for an empty output grid (an extent <= 0), NULL pointers and n <= 0; U3D_EUNSUPPORTED for an output extent
+ *   (+ 2 padding + 2 dilation) beyond 32-bit coordinates, for an output grid the chosen index form cannot hold and for n K >= 2^31.
+ *   Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+int u3d_convt_out_shape(const int32_t* geom, const int32_t* outpad, int X, int Y, int Z, int32_t* out_shape);
+int u3d_convt_mark(const int32_t* coords, int64_t n, const int32_t* geom, const int32_t* outpad, int B, int X, int Y, int Z,
+                   uint64_t* bitmap_out, int64_t* cells_out, u3d_stream_t stream);
+
 /* tile_starts int32 [K, n_tiles+1]: lower bound of t*tile_rows in the (ascending) list rows[k][0..counts[k]). */
 int u3d_tile_starts(const int32_t* rows, const int32_t* counts, int K, int64_t cap, int tile_rows,
                     int64_t n_tiles, int32_t* tile_starts, u3d_stream_t stream);
@@ -469,6 +489,23 @@ int u3d_sparse_pool_fwd(const float* x, const int32_t* table_out, int64_t n_out,
                         uint8_t* arg /* max only */, int32_t* count /* avg only */, u3d_stream_t stream);
 int u3d_sparse_pool_bwd(const float* dy, const int32_t* table_in, int64_t n_in, int K, int C, int mode, const uint8_t* arg /* max only */,
                         const int32_t* count /* avg only */, float* dx, u3d_stream_t stream);
+
+/* =====================================================================================
+ * B1  Bias of the sparse convolution layers (bias=True; csrc/sparse_bias.hip).  y, dy fp32 [n, C]; bias, db fp32 [C].
+ *   u3d_bias_add: y[r, c] += bias[c] in place over every row: one fp32 addition per element, the bits of y + b.
+ *   u3d_bias_grad: db[c] = sum over the rows of dy[r, c].  Two passes: workgroup b sums the fixed row range [b R, (b + 1) R),
+ *     R = U3D_BIAS_GRAD_ROWS, in fp64 into ws; then the partials of a channel are added in fp64 -- lane l of a wave takes l, l + S, ...
+ *     (S = U3D_BIAS_GRAD_STEP) in ascending order, a fixed tree adds the lanes -- and the sum is rounded once to fp32.  No atomics, one
+ *     summation order: bit-identical from run to run.  ws: u3d_bias_grad_ws_bytes(n, C) = ceil(n / R) C doubles.
+ *   Contract: C % 32 == 0, 32 <= C <= 512 (the convolution's destination widths), 1 <= n < 2^31; rows past n are not touched.  Errors,
+ *   before any HIP call and with a u3d_last_error text: U3D_EINVAL for NULL pointers and n <= 0, U3D_EUNSUPPORTED for other widths and
+ *   row counts.  n == 0 is the caller's business (no launch; db = 0).  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+#define U3D_BIAS_GRAD_ROWS 512
+#define U3D_BIAS_GRAD_STEP 64
+int u3d_bias_add(float* y, const float* bias, int64_t n, int C, u3d_stream_t stream);
+int u3d_bias_grad(const float* dy, int64_t n, int C, float* db, void* ws, u3d_stream_t stream);
+int64_t u3d_bias_grad_ws_bytes(int64_t n, int C);
 
 /* =====================================================================================
  * K13  self-attention core of nn.MultiheadAttention(256, 8, batch_first) per scene

@@ -60,6 +60,9 @@ PROTOTYPES = {
     'u3d_conv_mark': (_i32, [_vp, _i64, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     'u3d_conv_rulebook': (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i64, _vp, _vp, _vp, _vp, _vp]),
     'u3d_conv_rulebook_ws_bytes': (_i64, [_i64, _i32]),
+    # transposed convolution geometry (csrc/rulebook.hip; added entry points, same ABI version); outpad = host int32 [3]
+    'u3d_convt_out_shape': (_i32, [C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32)]),
+    'u3d_convt_mark': (_i32, [_vp, _i64, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     'u3d_tile_starts': (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp]),
     'u3d_spconv_gmm': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp]),
     'u3d_spconv_gmm_bf16': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp]),
@@ -118,6 +121,10 @@ PROTOTYPES = {
     'u3d_pair_table': (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp]),
     'u3d_sparse_pool_fwd': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'u3d_sparse_pool_bwd': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # bias of the sparse convolution layers (csrc/sparse_bias.hip; added entry points, same ABI version)
+    'u3d_bias_add': (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    'u3d_bias_grad': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    'u3d_bias_grad_ws_bytes': (_i64, [_i64, _i32]),
     'u3d_segment_gather_sum': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     'u3d_segment_mean_xyz': (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'u3d_segment_minmax_xyz': (_i32, [_vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
@@ -202,6 +209,7 @@ PROTOTYPES = {
 ABI_VERSION = 117         # include/u3d.h U3D_ABI_VERSION this table was written against
 EP_RELU, EP_BF16_ROWS = 1, 2      # include/u3d.h U3D_EP_*: the flag word of an activated output of u3d_conv_epilogue
 POOL_MAX, POOL_AVG = 0, 1         # include/u3d.h U3D_POOL_*: the mode of u3d_sparse_pool_fwd / _bwd
+BIAS_GRAD_ROWS, BIAS_GRAD_STEP = 512, 64      # include/u3d.h U3D_BIAS_GRAD_*: rows per first-pass workgroup, partials per second-pass step
 
 K_CONV_FWD, K_CONV_WGRAD, K_BN, K_POOL, K_ATTN_FWD, K_ATTN_BWD, K_RULEBOOK, K_VOXELIZE, K_GEMM = range(9)
 

@@ -190,6 +190,34 @@ __global__ __launch_bounds__(RB_T) void conv_mark_k(const int32_t* __restrict__ 
     }
 }
 
+// Transposed convolution (SparseConvTranspose3d): the output cell of (input row, tap) is o = i s - p + t d -- no division, no stride
+// branch, only the range test against the output extent (g.out holds the TRANSPOSED layer's output extents here, convt_geom).  Same
+// launch shape and the same two output forms as conv_mark_k.  The relation is conv_lookup's o' s - p + t d = i' with the two levels
+// swapped, so the pair lists come from conv_count_k / conv_write_k run over the layer's INPUT rows against the new level's index, and
+// the ascending-columns argument above holds read from the other side: for a fixed tap i -> i s - p + t d is strictly increasing on
+// every axis, hence injective and order-preserving from the layer's input level into the new level; walking the input rows in
+// canonical order emits the new level's rows in canonical order, no row repeats, and an offset has at most min(n_in, n_out) pairs.
+__global__ __launch_bounds__(RB_T) void convt_mark_k(const int32_t* __restrict__ coords, int64_t n, ConvGeom g, int B, int Zw, unsigned long long* bitmap,
+                                                     int64_t* __restrict__ cells) {
+    const int64_t i = (int64_t)blockIdx.x * RB_T + threadIdx.x;
+    if (i >= n) return;
+    const int k = blockIdx.y;
+    int t[3];
+    conv_taps(g, k, t);
+    const int4 c = *reinterpret_cast<const int4*>(coords + i * 4);
+    const int x = c.y * g.s[0] - g.p[0] + t[0] * g.d[0];
+    const int y = c.z * g.s[1] - g.p[1] + t[1] * g.d[1];
+    const int z = c.w * g.s[2] - g.p[2] + t[2] * g.d[2];
+    const bool ok = (unsigned)x < (unsigned)g.out[0] && (unsigned)y < (unsigned)g.out[1] && (unsigned)z < (unsigned)g.out[2] &&
+                    (unsigned)c.x < (unsigned)B;
+    const int64_t w = (((int64_t)c.x * g.out[0] + x) * g.out[1] + y) * Zw + (z >> 6);
+    if (bitmap) {
+        if (ok) atomicOr(&bitmap[w], 1ull << (z & 63));
+    } else {
+        cells[(int64_t)k * n + i] = ok ? w * 64 + (z & 63) : 0x7fffffffffffffffLL;
+    }
+}
+
 __device__ __forceinline__ int conv_lookup(const int32_t* __restrict__ out_coords, int64_t r, int k, const ConvGeom& g, const Index& ix) {
     int t[3];
     conv_taps(g, k, t);
@@ -248,6 +276,35 @@ static int conv_geom(const int32_t* geom, int X, int Y, int Z, ConvGeom* g) {
         g->k[a] = k; g->s[a] = s; g->p[a] = p; g->d[a] = d;
         g->out[a] = span < 0 ? 0 : (int)(span / s) + 1;
         g->K *= k;
+    }
+    return U3D_OK;
+}
+
+// The transposed layer of `geom` with output padding outpad[3] on INPUT extents (X, Y, Z): conv_geom's validation of k / s / p / d, then
+// torch's rule per axis, out = (in - 1) s - 2 p + d (k - 1) + q + 1, formed in int64; g->out receives it.  U3D_OK, or the code with
+// the text set -- all before any HIP call.
+static int convt_geom(const int32_t* geom, const int32_t* outpad, int X, int Y, int Z, ConvGeom* g) {
+    const int rc = conv_geom(geom, X, Y, Z, g);
+    if (rc != U3D_OK) return rc;
+    if (!outpad) { set_error("conv transpose geometry: null output padding"); return U3D_EINVAL; }
+    const int in[3] = {X, Y, Z};
+    for (int a = 0; a < 3; ++a) {
+        const int q = outpad[a], lim = g->s[a] > g->d[a] ? g->s[a] : g->d[a];
+        if (q < 0 || q >= lim) {
+            set_error("conv transpose geometry: output padding %d must be >= 0 and smaller than max(stride %d, dilation %d) (axis %d)", q, g->s[a], g->d[a], a);
+            return U3D_EINVAL;
+        }
+        const int64_t out = ((int64_t)in[a] - 1) * g->s[a] - 2 * (int64_t)g->p[a] + (int64_t)g->d[a] * (g->k[a] - 1) + q + 1;
+        if (out <= 0) {
+            set_error("conv transpose geometry: the output grid is empty: extent %lld on axis %d (input %d, padding %d beyond the reach)", (long long)out, a, in[a], g->p[a]);
+            return U3D_EINVAL;
+        }
+        // every coordinate the kernels form lies in [-p, out + 2 p): keep that, and what conv_geom asks of the new level, inside int32
+        if (out + 2 * (int64_t)g->p[a] + 2 * (int64_t)g->d[a] >= 0x7fffffffLL) {
+            set_error("conv transpose geometry: output extent %lld + 2 * padding %d + 2 * dilation %d overflows 32-bit coordinates (axis %d)", (long long)out, g->p[a], g->d[a], a);
+            return U3D_EUNSUPPORTED;
+        }
+        g->out[a] = (int)out;
     }
     return U3D_OK;
 }
@@ -360,6 +417,36 @@ int u3d_conv_mark(const int32_t* coords, int64_t n, const int32_t* geom, int B, 
     hipLaunchKernelGGL(conv_mark_k, dim3((unsigned)ceil_div(n, RB_T), g.K), dim3(RB_T), 0, (hipStream_t)stream, coords, n, g, B, (int)zw,
                        (unsigned long long*)bitmap_out, cells_out);
     return check_launch("conv_mark");
+}
+
+int u3d_convt_out_shape(const int32_t* geom, const int32_t* outpad, int X, int Y, int Z, int32_t* out_shape) {
+    ConvGeom g;
+    if (!out_shape) { set_error("convt_out_shape: null out_shape"); return U3D_EINVAL; }
+    const int rc = convt_geom(geom, outpad, X, Y, Z, &g);
+    if (rc != U3D_OK) return rc;
+    for (int a = 0; a < 3; ++a) out_shape[a] = g.out[a];
+    return U3D_OK;
+}
+
+int u3d_convt_mark(const int32_t* coords, int64_t n, const int32_t* geom, const int32_t* outpad, int B, int X, int Y, int Z, uint64_t* bitmap_out,
+                   int64_t* cells_out, u3d_stream_t stream) {
+    ConvGeom g;
+    const int rc = convt_geom(geom, outpad, X, Y, Z, &g);
+    if (rc != U3D_OK) return rc;
+    if (!coords || n <= 0 || B <= 0 || (bitmap_out != nullptr) == (cells_out != nullptr)) {
+        set_error("convt_mark: needs rows, a batch size and exactly one of bitmap_out / cells_out");
+        return U3D_EINVAL;
+    }
+    const int64_t zw = (g.out[2] + 63) / 64;
+    const long double words = (long double)B * g.out[0] * g.out[1] * zw;
+    if (bitmap_out ? words > (long double)U3D_INDEX_MAX_WORDS : words * 64 >= 4.0e18L) {
+        set_error("convt_mark: output grid %d x %d x %d x %d is too large for the %s index", B, g.out[0], g.out[1], g.out[2], bitmap_out ? "direct-address" : "hashed");
+        return U3D_EUNSUPPORTED;
+    }
+    if (n >= 0x7fffffffLL / g.K) { set_error("convt_mark: %lld rows x %d offsets exceed 32-bit counts", (long long)n, g.K); return U3D_EUNSUPPORTED; }
+    hipLaunchKernelGGL(convt_mark_k, dim3((unsigned)ceil_div(n, RB_T), g.K), dim3(RB_T), 0, (hipStream_t)stream, coords, n, g, B, (int)zw,
+                       (unsigned long long*)bitmap_out, cells_out);
+    return check_launch("convt_mark");
 }
 
 int64_t u3d_conv_rulebook_ws_bytes(int64_t n_out, int K) {

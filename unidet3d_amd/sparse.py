@@ -6,9 +6,10 @@ Mirrors the subset of ``spconv.pytorch`` the reference uses
 replace_feature / per-forward ``indice_dict`` rulebook cache keyed by
 ``indice_key``), ``SparseSequential``, ``SubMConv3d``, ``SparseConv3d``,
 ``SparseInverseConv3d``; plus the BatchNorm the reference takes from torch
-(``nn.SyncBatchNorm`` / ``nn.BatchNorm1d``), and spconv's ``SparseMaxPool3d`` /
-``SparseAvgPool3d`` on the strided convolution's geometry.  Same constructor arguments,
-same parameter names and weight layout ``[C_out, k, k, k, C_in]``.
+(``nn.SyncBatchNorm`` / ``nn.BatchNorm1d``), spconv's ``SparseMaxPool3d`` /
+``SparseAvgPool3d`` on the strided convolution's geometry, and ``SparseConvTranspose3d``
+(with ``output_padding``).  Same constructor arguments, same parameter names (``weight``,
+``bias`` with ``bias=True``) and weight layout ``[C_out, k, k, k, C_in]``.
 
 Every compute step is a call through the C ABI (include/u3d.h); there is no
 PyTorch fallback.  Rows must be in canonical order (ascending
@@ -377,6 +378,65 @@ def build_conv_rulebook(coords: torch.Tensor, index: OccupancyIndex, B: int, sha
     else:               # an empty level on either side: no pairs (the C entry points take n > 0 only)
         cnt = torch.zeros(K, dtype=torch.int32, device=dev)
     return oc, oshape, ix_out, Rulebook(pin, pout, cnt, K, n, n2)
+
+
+def output_padding_of(output_padding, geom):
+    """(q0, q1, q2) of a transposed layer, under ``_triple``'s rules; refused where torch refuses it: 0 <= q < max(stride, dilation)"""
+    q = _triple(output_padding, 'output_padding')
+    s, d = geom[3:6], geom[9:]
+    if not all(0 <= q[a] < max(s[a], d[a]) for a in range(3)):
+        raise L.U3DError(f'sparse conv: output_padding {q}: every output padding must be >= 0 and smaller than max(stride, dilation) = '
+                         f'{tuple(max(s[a], d[a]) for a in range(3))}')
+    return q
+
+
+def convt_out_shape(geom, outpad, shape):
+    """per axis (in - 1) s - 2 p + d (k - 1) + q + 1, torch's rule (u3d_convt_out_shape, host only); an empty grid is refused there"""
+    out = (ctypes.c_int * 3)()
+    L.call('u3d_convt_out_shape', _geom_array(geom), (ctypes.c_int * 3)(*outpad), *[int(s) for s in shape], out)
+    return [int(v) for v in out]
+
+
+def build_convt_rulebook(coords: torch.Tensor, B: int, shape, geom, outpad):
+    """Transposed convolution (csrc/rulebook.hip convt_mark_k, then the general builder's count / write passes): input cell i pairs with
+    output cell o = i s - p + t d.  That is ``build_conv_rulebook``'s relation o' s - p + t d = i' with the two levels swapped, so the
+    pair lists are those of "the SparseConv3d of this geometry from the NEW level, restricted to these rows": u3d_conv_rulebook with the
+    layer's input rows on its stationary side and the new level's index on its looked-up side.  Returns (out_coords, out_shape,
+    out_index, Rulebook) with pair_in = new-level rows, pair_out = layer-input rows (n_in = n_new, n_out = n): the layer runs
+    ``sparse_conv(..., mode='inv')``, the path ``SparseInverseConv3d`` takes over a general rulebook.  Both columns ascend inside an offset
+    (the same monotone map, read from the other side), cap = min(n_in, n_out) (at least 1); one host read, ``count()``.  It leaves
+    ``Rulebook.coords`` / ``index`` unset (``_conv_route``)."""
+    n, dev = coords.shape[0], coords.device
+    shape = [int(s) for s in shape]
+    K = geom[0] * geom[1] * geom[2]
+    g, q = _geom_array(geom), (ctypes.c_int * 3)(*outpad)
+    try:
+        oshape = convt_out_shape(geom, outpad, shape)
+    except L.U3DError as e:
+        raise L.U3DError(f'sparse conv transpose: spatial shape {shape} with kernel {tuple(geom[:3])}, stride {tuple(geom[3:6])}, padding '
+                         f'{tuple(geom[6:9])}, dilation {tuple(geom[9:])} and output padding {tuple(outpad)} has no output level: {e}') from None
+    if OccupancyIndex.wants_hash(B, oshape):
+        cells = torch.empty(K * n, dtype=torch.int64, device=dev)
+        if n:
+            L.call('u3d_convt_mark', L.ptr(coords), n, g, q, B, *shape, None, L.ptr(cells), L.stream())
+        ix_out = OccupancyIndex.from_cells(cells, B, oshape)
+    else:
+        ix_out = OccupancyIndex.alloc(B, oshape, dev)
+        if n:
+            L.call('u3d_convt_mark', L.ptr(coords), n, g, q, B, *shape, L.ptr(ix_out.bitmap), None, L.stream())
+        ix_out.build_rank()
+    n2 = ix_out.count()
+    oc = ix_out.coords(n2)
+    cap = max(1, min(n, n2))
+    pin = torch.empty(K, cap, dtype=torch.int32, device=dev)
+    pout = torch.empty(K, cap, dtype=torch.int32, device=dev)
+    if n and n2:
+        cnt = torch.empty(K, dtype=torch.int32, device=dev)
+        w = L.ws(L.lib().u3d_conv_rulebook_ws_bytes(n, K), dev)
+        L.call('u3d_conv_rulebook', L.ptr(coords), n, n2, *ix_out.table(), B, *oshape, g, cap, L.ptr(pin), L.ptr(pout), L.ptr(cnt), L.ptr(w), L.stream())
+    else:               # no input rows, or none whose taps reach the output grid: no pairs (the C entry points take n > 0 only)
+        cnt = torch.zeros(K, dtype=torch.int32, device=dev)
+    return oc, oshape, ix_out, Rulebook(pin, pout, cnt, K, n2, n)
 
 
 # ----------------------------------------------------------------------------------------
@@ -842,6 +902,64 @@ def sparse_conv(src, weight, rb, mode='fwd', addend=None, want_stats=False):
     if P.bf16_rows():
         dst._u3d_from_conv = True      # the batch norm behind this output hands its gradient back with a bf16 shadow (bf16_rows)
     return dst
+
+
+# ---- bias of a convolution layer (csrc/sparse_bias.hip) --------------------------------------------------------------------------
+def _bias_check(t: torch.Tensor, what: str, bias=None):
+    refuse_rows_only(t, what)
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise L.U3DError(f'{what}: rows must be fp32 [n, C], got {t.dtype} {tuple(t.shape)}')
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (t.shape[1],) or bias.device != t.device):
+        raise L.U3DError(f'{what}: the bias must be fp32 [{t.shape[1]}] on {t.device}, got {bias.dtype} {tuple(bias.shape)} on {bias.device} '
+                         f'(the bias add stays fp32 under every operand format)')
+
+
+def bias_add_(y: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """y += bias over every row, in place (u3d_bias_add: the bits of the fp32 y + b); no rows, no launch"""
+    _bias_check(y, 'bias_add', bias)
+    if y.shape[0]:
+        L.call('u3d_bias_add', L.ptr(y), L.ptr(bias), y.shape[0], y.shape[1], L.stream())
+    return y
+
+
+def bias_grad(dy: torch.Tensor) -> torch.Tensor:
+    """column sums of dy [n, C] (u3d_bias_grad: fp64 partials in a fixed order, one rounding); no rows, no launch and zeros"""
+    _bias_check(dy, 'bias_grad')
+    dy = dy.contiguous()
+    n, C = dy.shape
+    if not n:
+        return torch.zeros(C, dtype=torch.float32, device=dy.device)
+    db = torch.empty(C, dtype=torch.float32, device=dy.device)
+    w = L.ws(L.lib().u3d_bias_grad_ws_bytes(n, C), dy.device)
+    L.call('u3d_bias_grad', L.ptr(dy), n, C, L.ptr(db), L.ptr(w), L.stream())
+    return db
+
+
+class _BiasFn(torch.autograd.Function):
+    """y + bias in place on a convolution's fresh result (nothing in ``_SparseConvFn`` saves its output).  The backward hands dy on
+    untouched and sums it only when the bias asks for a gradient -- then always, whatever the weight does."""
+
+    @staticmethod
+    def forward(ctx, y, bias):
+        ctx.mark_dirty(y)
+        return bias_add_(y, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, (bias_grad(dy) if ctx.needs_input_grad[1] else None)
+
+
+def sparse_bias(y: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """(conv [+ addend]) + bias, fp32 under every operand format.  The result carries nothing for the layer behind it: no epilogue
+    statistics (they would be those of the value before the bias; the layer asks for none), no bf16 shadow and no ``_u3d_from_conv``
+    mark -- its reader takes the path of any tensor without one."""
+    if not y.is_contiguous():
+        raise L.U3DError('sparse_bias: non-contiguous convolution result')
+    out = _BiasFn.apply(y, bias)
+    for attr in ('_u3d_from_conv', '_u3d_stats', '_u3d_shadow'):
+        if hasattr(out, attr):
+            delattr(out, attr)
+    return out
 
 
 _EP_FORMATS = None
@@ -1343,6 +1461,11 @@ def _agree(layer, rb: Rulebook, mine):
                          f'has {mine}: layers that share an indice_key must share kernel_size, stride, padding and dilation')
 
 
+class UpLevel(tuple):
+    """(out_coords, out_shape, out_index, Rulebook) of a ``SparseConvTranspose3d``: its ``indice_dict`` entry, under ('__up__', name) and
+    under the plain ``indice_key``, where the other layer kinds recognise it by its type"""
+
+
 def strided_geometry(layer, x: 'SparseConvTensor'):
     """(out_coords, out_shape, out_index, Rulebook) of a layer that moves to a new level -- ``SparseConv3d`` and the pooling layers, which
     consume exactly the same geometry: ``layer.geom`` (the 12 integers of ``conv_geometry``) and ``layer.indice_key``.  Cached in
@@ -1353,6 +1476,8 @@ def strided_geometry(layer, x: 'SparseConvTensor'):
     name = layer.indice_key if layer.indice_key is not None or not general else ('__anon__', id(layer))
     key = ('__down__', name)
     if key not in x.indice_dict:
+        if isinstance(x.indice_dict.get(name), UpLevel):
+            raise L.U3DError(f'{type(layer).__name__}: indice_key {name!r} is taken by a SparseConvTranspose3d')
         if general:
             oc, oshape, ix2, rb = build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, layer.geom)
         else:
@@ -1369,12 +1494,17 @@ def strided_geometry(layer, x: 'SparseConvTensor'):
 
 class _ConvBase(SparseModule):
     """Weight [C_out, k0, k1, k2, C_in] and the layer geometry (``conv_geometry``: each of kernel_size / stride / padding / dilation an int
-    or a 3-sequence).  ``kernel_size`` keeps the int of a cubic kernel (a tuple otherwise); ``K`` is the number of offsets."""
+    or a 3-sequence).  ``kernel_size`` keeps the int of a cubic kernel (a tuple otherwise); ``K`` is the number of offsets.
+    ``bias=True`` (an fp32 ``bias`` [C_out], added to every output row after the convolution, ``sparse_bias``) is taken by the layer
+    kinds that set ``_takes_bias``: ``SparseInverseConv3d`` and ``SparseConvTranspose3d``.  ``SubMConv3d`` and ``SparseConv3d`` refuse it as
+    they always did."""
+    _takes_bias = False
 
     def __init__(self, in_channels, out_channels, kernel_size, bias=False, indice_key=None, stride=1, padding=0, dilation=1):
         super().__init__()
-        if bias:
-            raise L.U3DError('bias=True is not used by the reference configs and not built')
+        if bias and not self._takes_bias:
+            raise L.U3DError(f'{type(self).__name__}: bias=True is not built for this layer kind (SparseInverseConv3d and '
+                             f'SparseConvTranspose3d take one)')
         self.geom = conv_geometry(kernel_size, stride, padding, dilation)
         k = self.geom[:3]
         self.in_channels, self.out_channels, self.indice_key = in_channels, out_channels, indice_key
@@ -1383,9 +1513,19 @@ class _ConvBase(SparseModule):
         self.K = k[0] * k[1] * k[2]
         self.weight = nn.Parameter(torch.empty(out_channels, *k, in_channels))
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
+        if bias:                # fp32 [C_out], uniform in +-1 / sqrt(K C_in) (the fan-in of the weight above)
+            self.bias = nn.Parameter(torch.empty(out_channels))
+            bound = 1.0 / (self.K * in_channels) ** 0.5
+            nn.init.uniform_(self.bias, -bound, bound)
+        else:
+            self.register_parameter('bias', None)
 
     def _agree(self, rb: Rulebook, mine):
         _agree(self, rb, mine)
+
+    def _biased(self, y: torch.Tensor) -> torch.Tensor:
+        """y + bias on every row of the layer's result, rows without a pair included (``sparse_bias``); y itself without a bias"""
+        return y if self.bias is None else sparse_bias(y, self.bias)
 
     def _w16(self):
         c = self.in_channels
@@ -1394,12 +1534,16 @@ class _ConvBase(SparseModule):
     def _conv(self, x: 'SparseConvTensor', rb: Rulebook, mode: str, addend=None) -> torch.Tensor:
         """pad -> sparse_conv -> result features; in training mode with the statistics for a norm behind this layer asked for.
         On the fused inference path (a ``FusionRun`` in the tensor's ``indice_dict`` that plans this layer, ``fusion_active``) the
-        launch writes the result of the norm(s) behind this layer as well, and the result itself where the plan says."""
+        launch writes the result of the norm(s) behind this layer as well, and the result itself where the plan says.
+        With a bias the result is (conv + addend) + bias, two fp32 roundings in that order; such a layer asks the launch for no
+        statistics (the epilogue's would be those of the value before the bias) and is in no fusion plan (``spconv_unet.fusion_plan``)."""
         run = x.indice_dict.get(FUSE_KEY)
         cp = run.plan.convs.get(self) if run is not None else None
         if cp is not None and fusion_active(self, *(a[0] for a in cp.acts)):
+            if self.bias is not None:
+                raise L.U3DError(f'{type(self).__name__}: a layer with a bias has no fused-inference epilogue')
             return run.conv(self, cp, x, rb, mode, addend)
-        return sparse_conv(_pad16(x.features), self._w16(), rb, mode, addend, self.training)
+        return self._biased(sparse_conv(_pad16(x.features), self._w16(), rb, mode, addend, self.training and self.bias is None))
 
 
 class SubMConv3d(_ConvBase):
@@ -1437,7 +1581,8 @@ class SubMConv3d(_ConvBase):
             rb.tag = ('subm', key) if isinstance(key, str) else None
             x.indice_dict[key] = rb
         elif not isinstance(rb, Rulebook):
-            raise L.U3DError(f'SubMConv3d: indice_key {self.indice_key!r} is taken by a strided convolution')
+            taker = 'SparseConvTranspose3d' if isinstance(rb, UpLevel) else 'strided convolution'
+            raise L.U3DError(f'SubMConv3d: indice_key {self.indice_key!r} is taken by a {taker}')
         else:
             self._agree(rb, self._rb_geom)
         return rb
@@ -1498,7 +1643,9 @@ class SparseAvgPool3d(_PoolBase):
 
 class SparseInverseConv3d(_ConvBase):
     """Undoes the ``SparseConv3d`` found under its ``indice_key``, whatever that layer's geometry: the saved pairs with the roles
-    swapped (mode 'inv'), output on the strided convolution's input level.  ``kernel_size`` must be that layer's."""
+    swapped (mode 'inv'), output on the strided convolution's input level.  ``kernel_size`` must be that layer's.  With ``bias=True`` the
+    bias reaches every row of that level, a row without a pair included (a voxel beyond the last full window of a p = 0 layer)."""
+    _takes_bias = True
 
     def __init__(self, in_channels, out_channels, kernel_size, indice_key=None, bias=False):
         super().__init__(in_channels, out_channels, kernel_size, bias, indice_key)
@@ -1509,8 +1656,54 @@ class SparseInverseConv3d(_ConvBase):
             raise L.U3DError(f'SparseInverseConv3d: no rulebook saved under {self.indice_key!r}')
         if isinstance(entry, Rulebook):
             raise L.U3DError(f'SparseInverseConv3d: indice_key {self.indice_key!r} belongs to a SubMConv3d, not to a SparseConv3d')
+        if isinstance(entry, UpLevel):
+            raise L.U3DError(f'SparseInverseConv3d: indice_key {self.indice_key!r} belongs to a SparseConvTranspose3d: inverting a '
+                             f'transposed layer is not built')
         rb, idx, shape, index = entry
         if rb.geom is not None and tuple(rb.geom[1:4]) != self.geom[:3]:
             raise L.U3DError(f'SparseInverseConv3d: kernel_size {self.geom[:3]} differs from kernel_size {tuple(rb.geom[1:4])} of the '
                              f'SparseConv3d saved under {self.indice_key!r}')
         return SparseConvTensor(self._conv(x, rb, 'inv'), idx, shape, x.batch_size, x.indice_dict, index)
+
+
+class SparseConvTranspose3d(_ConvBase):
+    """Transposed sparse convolution: learned up-sampling into NEW voxels.  Input cell i and tap t reach output cell o = i s - p + t d
+    (per axis, taps not flipped); the output set is every cell so reached inside the output grid, in canonical order, and
+    y[o] = sum over the pairs (i, t) of W[:, t, :] x[i] -- ``F.conv_transpose3d(x, W.permute(4, 0, 1, 2, 3), stride=s, padding=p,
+    output_padding=q, dilation=d)`` sampled at the active rows (the dense result is zero everywhere else).  Kernel extents 1..3.
+    Output extent per axis: (in - 1) s - 2 p + d (k - 1) + q + 1, torch's rule.  spconv's own rule for this layer leaves the dilation out
+    ((in - 1) s - 2 p + k + q); the two agree at dilation 1.  ``output_padding`` must be smaller than max(stride, dilation), as in torch.
+    An input row whose taps all fall outside the grid (padding beyond the reach) contributes nothing; an empty output level gives an
+    empty tensor.  The rulebook is cached under ('__up__', indice_key) -- the layer's own identity without a key; two transposed layers
+    that share a key must share the geometry, output padding included.  Geometry and launch path: ``build_convt_rulebook``."""
+    _takes_bias = True
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, output_padding=0, dilation=1, bias=False, indice_key=None):
+        super().__init__(in_channels, out_channels, kernel_size, bias, indice_key, stride, padding, dilation)
+        self.output_padding = output_padding_of(output_padding, self.geom)
+        self.general = True                 # not the U-Net's own layer shapes: a fusion plan that meets it steps aside
+        self._rb_geom = ('convt', *self.geom, *self.output_padding)
+
+    def geometry(self, x: SparseConvTensor) -> UpLevel:
+        """Output level + rulebook of this layer: (out_coords, out_shape, out_index, Rulebook), cached in ``indice_dict``"""
+        name = self.indice_key if self.indice_key is not None else ('__anon__', id(self))
+        key = ('__up__', name)
+        hit = x.indice_dict.get(key)
+        if hit is None:
+            named = not isinstance(name, tuple)
+            if named and (name in x.indice_dict or ('__down__', name) in x.indice_dict):
+                taker = 'SubMConv3d' if isinstance(x.indice_dict.get(name), Rulebook) else 'strided convolution or pooling layer'
+                raise L.U3DError(f'SparseConvTranspose3d: indice_key {name!r} is taken by a {taker}')
+            oc, oshape, ix, rb = build_convt_rulebook(x.indices, x.batch_size, x.spatial_shape, self.geom, self.output_padding)
+            rb.geom = self._rb_geom
+            rb.tag = key if named else None
+            hit = x.indice_dict[key] = UpLevel((oc, oshape, ix, rb))
+            if named:
+                x.indice_dict[name] = hit
+        else:
+            self._agree(hit[3], self._rb_geom)
+        return hit
+
+    def forward(self, x: SparseConvTensor) -> SparseConvTensor:
+        oc, oshape, ix, rb = self.geometry(x)
+        return SparseConvTensor(self._conv(x, rb, 'inv'), oc, oshape, x.batch_size, x.indice_dict, ix)

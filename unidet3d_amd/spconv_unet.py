@@ -234,7 +234,10 @@ def fusion_plan(unet, first_producer=None, last_consumer=None) -> FusionPlan:
     for name, m in unet.named_modules():
         plan.names[m] = name or '<unet>'
     # (a layer of the general geometry -- any kernel / stride / padding / dilation but the U-Net's own -- runs unfused: the whole plan steps aside)
-    if not _plan_level(plan, unet, feed, sink) or any(getattr(c, 'general', False) for c in plan.convs):
+    # (so does a layer with a bias and a transposed layer, planned or anywhere in the U-Net: no fused epilogue knows about either)
+    held = [m for m in unet.modules() if isinstance(m, S._ConvBase)] + ([feed] if feed is not None else [])
+    aside = any(m.bias is not None or isinstance(m, S.SparseConvTranspose3d) for m in held)
+    if aside or not _plan_level(plan, unet, feed, sink) or any(getattr(c, 'general', False) for c in plan.convs):
         plan = FusionPlan(unet)
     for conv, e in plan.convs.items():          # at most two activated outputs per launch
         for norm, _, _ in e.acts[2:]:
