@@ -302,3 +302,43 @@ def test_geometry_entry_points_validate_on_the_host():
     assert lib.u3d_conv_mark(8, 10, S._geom_array(S.conv_geometry(3, 2, 0, 1)), 1, 2, 8, 8, 8, None, None) == -1 and b'empty' in lib.u3d_last_error()
     assert lib.u3d_conv_rulebook(8, 10, 20, 8, 8, 0, 1, 8, 8, 8, g, 9, 8, 8, 8, 8, None) == -1 and b'below min' in lib.u3d_last_error()
     assert lib.u3d_conv_rulebook(8, 0, 20, 8, 8, 0, 1, 8, 8, 8, g, 9, 8, 8, 8, 8, None) == -1
+
+
+# ---------------------------------------------------------------------------------------------------------------- module boundaries
+_MOVED_PUBLIC = ['OccupancyIndex', 'Rulebook', 'UpLevel', 'build_subm_rulebook', 'build_down_rulebook', 'build_conv_rulebook',
+                 'build_convt_rulebook', 'conv_geometry', 'conv_out_shape', 'output_padding_of', 'convt_out_shape', 'strided_geometry',
+                 'cached_level']
+_MOVED_PRIVATE = ['_PAIR_CACHE', '_TILE_HISTORY', '_TILE_PRECOMPUTE', '_INDEX_MODE', '_HASH_ABOVE_BYTES', '_DOWN_K2S2', '_triple', '_geom_array',
+                  '_agree']
+_BOUNDARY_CHILD = '''
+import sys, types
+pkg = types.ModuleType('unidet3d_amd')          # the package without its __init__, which registers every model and so imports every module
+pkg.__path__ = [sys.argv[1]]
+sys.modules['unidet3d_amd'] = pkg
+import unidet3d_amd.geometry as geometry
+assert sorted(m for m in sys.modules if m.startswith('unidet3d_amd.')) == ['unidet3d_amd._lib', 'unidet3d_amd.geometry'], sorted(sys.modules)
+import unidet3d_amd.ops
+assert 'unidet3d_amd.sparse' not in sys.modules and 'unidet3d_amd.dense' not in sys.modules
+assert unidet3d_amd.ops.OccupancyIndex is geometry.OccupancyIndex
+import unidet3d_amd.sparse as sparse
+public, private = sys.argv[2].split(','), sys.argv[3].split(',')
+for name in public + ['_TILE_HISTORY']:
+    assert getattr(sparse, name) is getattr(geometry, name), name
+for name in private:
+    assert hasattr(geometry, name), name
+    assert not hasattr(sparse, name) or getattr(sparse, name) is getattr(geometry, name), name
+for name in ('_INDEX_MODE', '_HASH_ABOVE_BYTES', '_TILE_PRECOMPUTE'):          # read where they are owned: a copy here would be a dead switch
+    assert not hasattr(sparse, name), name
+print('boundaries ok')
+'''
+
+
+def test_geometry_module_stands_below_the_layers_and_the_voxeliser():
+    """In a fresh interpreter: ``geometry`` imports nothing of the package but ``_lib``; ``ops`` (the voxeliser) imports neither ``sparse``
+    nor ``dense``; and every moved name that ``sparse`` still shows is the object ``geometry`` owns, the three environment switches not
+    among them."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, '-c', _BOUNDARY_CHILD, os.path.join(ROOT, 'unidet3d_amd'), ','.join(_MOVED_PUBLIC), ','.join(_MOVED_PRIVATE)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and 'boundaries ok' in r.stdout, r.stderr[-3000:]

@@ -7,6 +7,9 @@ and inverse roles, ELEMENTWISE inside the derived bound of tests/_conv_geometry.
 allocations.  Modules: a small stack runs forward and backward with the predicted shapes and indices, bit-identical across runs; the
 U-Net's own two layer shapes still launch exactly the entry points they launched before the general builder existed.
 The largest err / bound per kernel selection goes to the parity log (_parity.log_errors, test 'conv_general')."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -76,22 +79,24 @@ def test_geometry_equals_the_brute_force_reference_bit_for_bit(cfg):
 
 @pytest.mark.parametrize('cfg', list(G.CONFIGS))
 def test_geometry_under_the_hashed_index(cfg, monkeypatch):
-    from unidet3d_amd import sparse
-    monkeypatch.setattr(sparse, '_INDEX_MODE', 'hash')
+    from unidet3d_amd import geometry
+    monkeypatch.setattr(geometry, '_INDEX_MODE', 'hash')
     for name in G.SCENES:
         assert _build(cfg, name)['index'].hashed
 
 
 @pytest.mark.parametrize('mode', ['bitmap', 'hash'])
 def test_general_builder_reproduces_the_two_hard_coded_rulebooks(mode, monkeypatch):
-    from unidet3d_amd import sparse
-    monkeypatch.setattr(sparse, '_INDEX_MODE', mode)
+    from unidet3d_amd import geometry, sparse
+    monkeypatch.setattr(geometry, '_INDEX_MODE', mode)
     for name in G.SCENES:
         _, B, shape, coords = G.scene(name)
         rows = coords.to(DEV)
         ix = sparse.OccupancyIndex.from_coords(rows, B, shape)
+        assert ix.hashed == (mode == 'hash')
         oc, oshape, ix2, rb = sparse.build_down_rulebook(rows, B, shape)
         goc, goshape, gix2, grb = sparse.build_conv_rulebook(rows, ix, B, shape, sparse.conv_geometry(2, 2, 0, 1))
+        assert ix2.hashed == gix2.hashed == (mode == 'hash')
         assert torch.equal(oc, goc) and list(oshape) == list(goshape) and torch.equal(rb.counts, grb.counts), name
         _same_lists(grb.lists(), rb.lists(), f'k2s2 on {name}')
         rb = sparse.build_subm_rulebook(rows, ix)
@@ -285,3 +290,66 @@ def test_unet_layer_shapes_launch_the_entry_points_they_always_did(monkeypatch):
         S.SparseConv3d(32, 64, 3, stride=2, padding=1, indice_key='g').to(DEV)(y)
         geo, conv = geometry_calls()
         assert geo == ['u3d_conv_out_shape', 'u3d_conv_mark', 'u3d_index_rank', 'u3d_index_coords', 'u3d_conv_rulebook'] and len(conv) == 1, (geo, conv)
+
+
+GOLDEN_STACK = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'general_stack_launch_names_before_geometry_module.json')
+
+
+def _cache_key_kind(key):
+    """an ``indice_dict`` key without what changes from run to run: the ``id()`` of a keyless layer, the address of the level's rows"""
+    if not isinstance(key, tuple):
+        return key
+    if key[0] == '__index__':
+        return ['__index__', list(key[1])]
+    return [a[0] if isinstance(a, tuple) else a for a in key if not isinstance(a, int)]
+
+
+def _general_stack_launches(monkeypatch):
+    """The ``L.call`` names, in order, and the ``indice_dict`` keys of one inference pass of every layer kind over one cache: a dilated
+    SubM layer, a general strided convolution, a max pool that shares its key, its inverse, a keyed and a keyless transposed layer, at
+    32 channels on 'block5_odd_extent' with an empty tile history.  Weight packs and tile lists are left out, as in
+    ``test_unet_layer_shapes_launch_the_entry_points_they_always_did``.  The recorded lists are this function run on the commit before
+    the geometry moved into its own module."""
+    from unidet3d_amd import _lib as L
+    from unidet3d_amd import sparse as S
+    torch.manual_seed(3)
+    subm = S.SubMConv3d(32, 32, 3, dilation=2, indice_key='s')
+    down = S.SparseConv3d(32, 32, 3, stride=2, padding=1, indice_key='d')
+    pool = S.SparseMaxPool3d(3, stride=2, padding=1, indice_key='d')
+    inv = S.SparseInverseConv3d(32, 32, 3, indice_key='d')
+    up = S.SparseConvTranspose3d(32, 32, 3, stride=2, padding=1, output_padding=1, indice_key='u')
+    anon = S.SparseConvTranspose3d(32, 32, 3, stride=2, padding=1, output_padding=1)
+    torch.nn.ModuleList([subm, down, pool, inv, up, anon]).to(DEV).eval()
+    _, B, shape, coords = G.scene('block5_odd_extent')
+    feats = torch.randn(len(coords), 32, generator=torch.Generator().manual_seed(2)).to(DEV)
+    names, real = [], L.call
+
+    def recorder(nm, *a):
+        names.append(nm)
+        return real(nm, *a)
+    S._TILE_HISTORY.clear()
+    monkeypatch.setattr(L, 'call', recorder)
+    with torch.no_grad(), _selection('bf16x3'), S.conv_ts(False), S.conv_rs(False):
+        x = S.SparseConvTensor(feats, coords.to(DEV), shape, B)
+        y = subm(x)
+        z = down(y)
+        p = pool(y)
+        w = inv(z)
+        t = anon(up(w))
+    torch.cuda.synchronize()
+    monkeypatch.setattr(L, 'call', real)
+    assert torch.equal(p.indices, z.indices) and torch.equal(w.indices, x.indices) and t.spatial_shape == [4 * s for s in shape]
+    assert all(bool(torch.isfinite(v.features).all()) for v in (p, w, t)) and float(t.features.abs().max()) > 0
+    keys = sorted((_cache_key_kind(k) for k in x.indice_dict), key=str)
+    return dict(names=[nm for nm in names if not nm.startswith(('u3d_weight_pack', 'u3d_tile_starts'))], keys=keys)
+
+
+@pytest.mark.parametrize('mode', ['bitmap', 'hash'])
+def test_mixed_stack_launches_and_caches_exactly_what_it_did_before(mode, monkeypatch):
+    from unidet3d_amd import geometry
+    monkeypatch.setattr(geometry, '_INDEX_MODE', mode)
+    before = json.load(open(GOLDEN_STACK))[mode]
+    got = _general_stack_launches(monkeypatch)
+    assert len(before['names']) > 20 and (mode == 'hash') == ('u3d_hash_index_build' in got['names']) == ('u3d_index_rank' not in got['names'])
+    assert got['names'] == before['names'], [(i, a, b) for i, (a, b) in enumerate(zip(got['names'], before['names'])) if a != b][:5]
+    assert got['keys'] == before['keys']

@@ -79,8 +79,8 @@ def test_geometry_equals_the_brute_force_reference_bit_for_bit(cfg):
 
 @pytest.mark.parametrize('cfg', GEOMETRY_CONFIGS, ids=str)
 def test_geometry_under_the_hashed_index(cfg, monkeypatch):
-    from unidet3d_amd import sparse
-    monkeypatch.setattr(sparse, '_INDEX_MODE', 'hash')
+    from unidet3d_amd import geometry
+    monkeypatch.setattr(geometry, '_INDEX_MODE', 'hash')
     for name in T.SCENES:
         assert _build(cfg, name)['index'].hashed
 

@@ -632,8 +632,8 @@ def test_hashed_index_is_bit_exact(monkeypatch):
     """The hashed form of the voxel index (radix sort -> unique -> open-addressing table; csrc/hashidx.hip) forced onto an ordinary
     batch: voxel coordinates, inverse map, voxel features and the rulebooks of all five levels equal the oracle's bit for bit --
     the same kernels as with the bitmap index, fed through the table."""
-    from unidet3d_amd import ops, sparse
-    monkeypatch.setattr(sparse, '_INDEX_MODE', 'hash')
+    from unidet3d_amd import geometry, ops, sparse
+    monkeypatch.setattr(geometry, '_INDEX_MODE', 'hash')
     scenes = _scene_points(3, 30_000, seed0=61)
     pts_cpu = [torch.from_numpy(s.points) for s in scenes]
     vb = ops.voxelize([p.to(_dev()) for p in pts_cpu], 0.02, 128)

@@ -15,7 +15,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib as L
-from .sparse import OccupancyIndex
+from .geometry import OccupancyIndex
 
 
 @dataclass
@@ -56,16 +56,12 @@ def voxelize(points: List[torch.Tensor], voxel_size: float, min_spatial_shape: i
            L.ptr(stats), L.ptr(gmax), L.ptr(w), L.stream())
     shape = [max(int(v) + 1, int(min_spatial_shape)) for v in gmax.tolist()]       # read-back #1
     pt_cell = torch.empty(n_pts, dtype=torch.int64, device=dev)
-    if OccupancyIndex.wants_hash(B, shape):
-        # large extent: cell ids only, then sort -> unique -> hash table (memory follows occupancy, csrc/hashidx.hip)
+
+    def mark(bitmap):           # bitmap None = hashed index (large extent): cell ids only, then sort -> unique -> hash table (csrc/hashidx.hip)
         L.call('u3d_vox_mark', L.ptr(pts), L.ptr(csrc), L.ptr(offs), B, max(sizes), L.ptr(stats), vs, div_mode,
-               *shape, None, L.ptr(pt_cell), L.stream())
-        index = OccupancyIndex.from_cells(pt_cell, B, shape)
-    else:
-        index = OccupancyIndex.alloc(B, shape, dev)
-        L.call('u3d_vox_mark', L.ptr(pts), L.ptr(csrc), L.ptr(offs), B, max(sizes), L.ptr(stats), vs, div_mode,
-               *shape, L.ptr(index.bitmap), L.ptr(pt_cell), L.stream())
-        index.build_rank()
+               *shape, L.ptr(bitmap), L.ptr(pt_cell), L.stream())
+        return pt_cell
+    index = OccupancyIndex.from_marks(B, shape, dev, mark)
     n_vox = index.count()                                                          # read-back #2
     coords = index.coords(n_vox)
     inverse = torch.empty(n_pts, dtype=torch.int64, device=dev)

@@ -20,12 +20,14 @@ What a layer leaves for the next one rides on the feature TENSOR (bf16 shadow, `
 convolution's epilogue, in inference the norm's whole result: ``shadow_of`` / ``stats_of`` / ``activated_of``); ``SparseConvTensor``
 carries geometry only (and, in its ``indice_dict``, the ``FusionRun`` of a forward on the fused inference path).  A norm on a sparse tensor is one
 call, ``SparseBatchNorm.on``; a convolution layer is: find the geometry, ``_ConvBase._conv``, build the output tensor.
+
+The geometry itself (``OccupancyIndex``, ``Rulebook``, the four rulebook builders, the layer-geometry helpers, the ``indice_dict`` level
+cache ``cached_level`` / ``strided_geometry``) moved to ``unidet3d_amd.geometry``; its public names are re-exported here.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes
-import operator
 import os
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -40,403 +42,10 @@ from . import dense
 from . import precision as P
 from . import account
 from . import wgrad_stream as WS
+from .geometry import (OccupancyIndex, Rulebook, UpLevel, build_subm_rulebook, build_conv_rulebook, build_convt_rulebook, conv_geometry,
+                       output_padding_of, strided_geometry, cached_level, layer_geometry, saved_under, tensor_index, _DOWN_K2S2)
+from .geometry import build_down_rulebook, conv_out_shape, convt_out_shape, _geom_array, _TILE_HISTORY      # noqa: F401  (re-exported)
 from .wgrad_stream import set_wgrad_overlap, async_dw_ok, join_wgrad_stream, end_of_backward, _ASYNC_DW_SEEN      # noqa: F401  (re-exported)
-
-
-# ----------------------------------------------------------------------------------------
-# geometry: occupancy index + rulebooks
-# ----------------------------------------------------------------------------------------
-# A grid whose direct-address table would exceed this many bytes (or that u3d_index_words refuses) gets the hashed index
-# (csrc/hashidx.hip: memory follows occupancy).  The six indoor configs stay far below (cfg2: 100 MB); U3D_INDEX=hash forces the
-# hashed form everywhere (tests), U3D_INDEX=bitmap forbids it.
-_INDEX_MODE = os.environ.get('U3D_INDEX', 'auto')
-_HASH_ABOVE_BYTES = int(float(os.environ.get('U3D_INDEX_HASH_ABOVE_MB', '4096')) * (1 << 20))
-
-
-class OccupancyIndex:
-    """Cell -> canonical row of one level: bitmap + popcount rank over the grid extent, or -- large extents -- a hash table over the
-    occupied cells.  ``table()`` gives the (pointer, pointer, hash_slots) triple every C entry point takes."""
-
-    def __init__(self, bitmap, rank, B, shape, slots=0, ukeys=None, n_dev=None):
-        self.bitmap, self.rank, self.B = bitmap, rank, B          # hashed form: table keys (int64 view of uint64) / table values
-        self.shape = [int(s) for s in shape]
-        self.slots, self.ukeys, self.n_dev = int(slots), ukeys, n_dev
-
-    @property
-    def hashed(self) -> bool:
-        return self.slots > 0
-
-    def table(self):
-        return L.ptr(self.bitmap), L.ptr(self.rank), self.slots
-
-    @staticmethod
-    def wants_hash(B, shape) -> bool:
-        if _INDEX_MODE == 'hash':
-            return True
-        nw = L.lib().u3d_index_words(B, *[int(s) for s in shape])
-        if _INDEX_MODE == 'bitmap':
-            return False
-        return nw < 0 or nw * 12 > _HASH_ABOVE_BYTES
-
-    @staticmethod
-    def alloc(B, shape, device):
-        nw = L.lib().u3d_index_words(B, *[int(s) for s in shape])
-        if nw < 0:
-            raise L.U3DError(f'occupancy index refused (code {nw}): {L.lib().u3d_last_error().decode()}')
-        bitmap = torch.zeros(nw, dtype=torch.int64, device=device)
-        rank = torch.empty(nw + 1, dtype=torch.int32, device=device)
-        return OccupancyIndex(bitmap, rank, B, shape)
-
-    @staticmethod
-    def from_cells(cells: torch.Tensor, B: int, shape) -> 'OccupancyIndex':
-        """Hashed index of the cells in ``cells`` (int64 cell ids, duplicates allowed, INT64_MAX = none)."""
-        n, dev = cells.shape[0], cells.device
-        slots = L.lib().u3d_hash_index_slots(n)
-        ukeys = torch.empty(n, dtype=torch.int64, device=dev)
-        n_dev = torch.empty(1, dtype=torch.int32, device=dev)
-        vals = torch.empty(slots, dtype=torch.int32, device=dev)
-        if n == 0:                 # an empty level / point set: a table of free slots, zero rows (the C entry points take n > 0 only)
-            keys = torch.full((slots,), -1, dtype=torch.int64, device=dev)
-            return OccupancyIndex(keys, vals, B, shape, slots, ukeys, n_dev.zero_())
-        keys = torch.empty(slots, dtype=torch.int64, device=dev)
-        w = L.ws(L.lib().u3d_hash_index_ws_bytes(n), dev)
-        n_cells = int(B) * int(shape[0]) * int(shape[1]) * ((int(shape[2]) + 63) // 64) * 64       # cell ids are < n_cells: bounds the sort's passes
-        L.call('u3d_hash_index_build', L.ptr(cells), n, n_cells if n_cells < (1 << 62) else 0, L.ptr(ukeys), L.ptr(n_dev), L.ptr(keys), L.ptr(vals),
-               slots, L.ptr(w), L.stream())
-        return OccupancyIndex(keys, vals, B, shape, slots, ukeys, n_dev)
-
-    def build_rank(self):
-        nw = self.bitmap.numel()
-        w = L.ws(L.lib().u3d_index_rank_ws_bytes(nw), self.bitmap.device)
-        L.call('u3d_index_rank', L.ptr(self.bitmap), nw, L.ptr(self.rank), L.ptr(w), L.stream())
-
-    def count(self) -> int:
-        return int((self.n_dev if self.hashed else self.rank[-1]).item())       # documented read-back (one host sync)
-
-    def coords(self, n: int) -> torch.Tensor:
-        c = torch.empty(n, 4, dtype=torch.int32, device=self.bitmap.device)
-        if n and self.hashed:
-            L.call('u3d_hash_index_coords', L.ptr(self.ukeys), n, *self.shape, L.ptr(c), L.stream())
-        elif n:
-            L.call('u3d_index_coords', L.ptr(self.bitmap), L.ptr(self.rank), self.B, *self.shape, L.ptr(c), L.stream())
-        return c
-
-    @staticmethod
-    def from_coords(coords: torch.Tensor, B: int, shape, shift: int = 0) -> 'OccupancyIndex':
-        shape = [int(s) for s in shape]
-        if OccupancyIndex.wants_hash(B, shape):
-            cells = torch.empty(coords.shape[0], dtype=torch.int64, device=coords.device)
-            if coords.shape[0] == 0:
-                return OccupancyIndex.from_cells(cells, B, shape)
-            L.call('u3d_cells_of_coords', L.ptr(coords), coords.shape[0], shift, B, *shape, L.ptr(cells), L.stream())
-            return OccupancyIndex.from_cells(cells, B, shape)
-        ix = OccupancyIndex.alloc(B, shape, coords.device)
-        L.call('u3d_index_mark', L.ptr(coords), coords.shape[0], shift, *ix.shape, L.ptr(ix.bitmap), L.stream())
-        ix.build_rank()
-        return ix
-
-
-_PAIR_CACHE: Dict = {}
-# rulebook tag (its indice_key) -> the (role, tile height) lists the convolutions asked of that rulebook in earlier steps:
-# ``Rulebook.precompute_tiles`` builds them with the rulebook (on the side stream of ``UniDet3D.prefetch``) instead of on first use
-# in the middle of the forward / backward pass (34 launches of ~6.6 us on the main stream per step otherwise)
-_TILE_HISTORY: Dict = {}
-_TILE_PRECOMPUTE = os.environ.get('U3D_TILE_PRECOMPUTE', '1') != '0'
-
-
-class Rulebook:
-    """pair_in / pair_out int32 [K, cap] grouped by offset, ascending inside an offset."""
-
-    def __init__(self, pair_in, pair_out, counts, K, n_in, n_out):
-        self.pair_in, self.pair_out, self.counts = pair_in, pair_out, counts
-        self.K, self.cap, self.n_in, self.n_out = K, pair_in.shape[1], n_in, n_out
-        self._tiles: Dict = {}
-        self._total = None
-        self.tag = None             # set by the layer that caches it (indice_key): lets the tile lists follow last step's use
-        self.coords = self.index = None      # SubM k=3 / dilation 1 rulebooks ONLY: the level's voxels and occupancy index (tile-stationary kernel's tables)
-        self.geom = None            # set by the layer that caches it: the layer geometry it was built for (a shared indice_key must agree)
-        self._halo: Dict = {}
-        self._nbr: Dict = {}
-
-    def neighbours(self, role: str) -> torch.Tensor:
-        """The destination-major view of the pair lists (u3d_pair_table) the pooling kernels walk: int32 [n, K], entry [r, k] = the row
-        paired with r at offset k, or -1.  role 'out': n = n_out, each output row's inputs; 'in': n = n_in, each input row's outputs.
-        Built once per rulebook and role (4 K n bytes); remembered like the tile lists so that the next step's rulebook builds it ahead."""
-        if role not in ('out', 'in'):
-            raise L.U3DError(f"Rulebook.neighbours: role must be 'out' or 'in', got {role!r}")
-        if self.tag is not None:
-            _TILE_HISTORY.setdefault(self.tag, set()).add(('nbr', role))
-        return self._neighbours(role)
-
-    def _neighbours(self, role: str) -> torch.Tensor:
-        if role not in self._nbr:
-            key, val, n, m = (self.pair_out, self.pair_in, self.n_out, self.n_in) if role == 'out' else (self.pair_in, self.pair_out, self.n_in, self.n_out)
-            if n and m:
-                t = torch.empty(n, self.K, dtype=torch.int32, device=key.device)
-                L.call('u3d_pair_table', L.ptr(key), L.ptr(val), L.ptr(self.counts), self.K, self.cap, n, L.ptr(t), L.stream())
-            else:           # an empty level on either side: no pairs (the C entry points take n > 0 only)
-                t = torch.full((n, self.K), -1, dtype=torch.int32, device=key.device)
-            self._nbr[role] = t
-        return self._nbr[role]
-
-    def _tile_starts(self, role: str, T: int) -> torch.Tensor:
-        key = (role, T)
-        if key not in self._tiles:
-            rows = self.pair_out if role == 'out' else self.pair_in
-            n_dst = self.n_out if role == 'out' else self.n_in
-            nt = (n_dst + T - 1) // T
-            ts = torch.empty(self.K, nt + 1, dtype=torch.int32, device=rows.device)
-            L.call('u3d_tile_starts', L.ptr(rows), L.ptr(self.counts), self.K, self.cap, T, nt, L.ptr(ts), L.stream())
-            self._tiles[key] = ts
-        return self._tiles[key]
-
-    def tile_starts(self, role: str, T: int, wgrad=None) -> torch.Tensor:
-        """``wgrad`` = (C_in, C_out) when T is a weight-gradient tile height: that height follows the row count (u3d_spconv_wgrad_tile_rows),
-        so the history remembers the layer shape and the next rulebook recomputes ITS height instead of replaying this one."""
-        if self.tag is not None:
-            _TILE_HISTORY.setdefault(self.tag, set()).add((role, T) if wgrad is None else (role, 'wgrad', int(wgrad[0]), int(wgrad[1])))
-        return self._tile_starts(role, T)
-
-    def halo(self, T: int, H: int):
-        """Tables of the tile-stationary SubM kernel (csrc/spconv_ts.hip, u3d_subm_halo) for tiles of T rows and passes of H halo
-        rows: (nhalo, halo, loc, pmask).  Built once per rulebook and (T, H); remembered like the tile lists so that the next step's
-        rulebook builds them on the side stream."""
-        if self.tag is not None:
-            _TILE_HISTORY.setdefault(self.tag, set()).add(('halo', int(T), int(H)))
-        return self._halo_tables(int(T), int(H))
-
-    def _halo_tables(self, T: int, H: int):
-        key = (T, H)
-        if key not in self._halo:
-            if self.coords is None:
-                raise L.U3DError('halo tables need a SubM rulebook built by build_subm_rulebook')
-            n, dev = self.n_out, self.coords.device
-            nt = (n + T - 1) // T
-            pmax = L.lib().u3d_subm_halo_pmax(T, H)
-            nhalo = torch.empty(nt, dtype=torch.int32, device=dev)
-            halo = torch.empty(nt, 27 * T, dtype=torch.int32, device=dev)
-            loc = torch.empty(nt, 27, T, dtype=torch.int16, device=dev)
-            pmask = torch.empty(nt, pmax, dtype=torch.int32, device=dev)
-            L.call('u3d_subm_halo', L.ptr(self.coords), n, *self.index.table(), self.index.B, *self.index.shape, T, H,
-                   L.ptr(nhalo), L.ptr(halo), L.ptr(loc), L.ptr(pmask), L.stream())
-            self._halo[key] = (nhalo, halo, loc, pmask)
-        return self._halo[key]
-
-    def precompute_tiles(self):
-        """Build the tile lists the PREVIOUS rulebook with this tag was asked for: fixed heights (the forward / input-gradient kernels'
-        32 / 64 rows) as they were, weight-gradient heights recomputed for THIS rulebook's row count.  Only this step's real requests
-        are remembered for the next."""
-        if self.tag is None or not _TILE_PRECOMPUTE:
-            return
-        for key in sorted(_TILE_HISTORY.pop(self.tag, ()), key=str):
-            if key[0] == 'halo':
-                if self.coords is not None and self.n_out > 0:
-                    self._halo_tables(key[1], key[2])
-            elif key[0] == 'nbr':
-                self._neighbours(key[1])
-            elif len(key) == 2:
-                self._tile_starts(*key)
-            else:
-                role, _, cin, cout = key
-                n_dy = self.n_out if role == 'out' else self.n_in
-                if n_dy > 0:
-                    self._tile_starts(role, int(L.lib().u3d_spconv_wgrad_tile_rows(self.K, n_dy, cin, cout)))
-
-    @property
-    def total_pairs(self) -> int:
-        """Number of rulebook pairs (flops accounting).  Host read-back, cached by geometry so a bench
-        that replays the same scenes does not synchronise inside its timed region.  The layer geometry is part of the key: two
-        rulebooks of one level (SubM k=3 with dilation 1 and 2) share K and both row counts, not their pairs."""
-        if self._total is None:
-            key = (self.K, self.n_in, self.n_out, self.geom)
-            if key not in _PAIR_CACHE:
-                _PAIR_CACHE[key] = int(self.counts.sum().item())
-            self._total = _PAIR_CACHE[key]
-        return self._total
-
-    def lists(self):
-        """Host copy as 27/8 (in_rows, out_rows) arrays -- the canonical rulebook (tests)."""
-        c = self.counts.cpu().tolist()
-        pi, po = self.pair_in.cpu(), self.pair_out.cpu()
-        return [(pi[k, :c[k]].numpy(), po[k, :c[k]].numpy()) for k in range(self.K)]
-
-
-def build_subm_rulebook(coords: torch.Tensor, index: OccupancyIndex) -> Rulebook:
-    n = coords.shape[0]
-    dev = coords.device
-    pin = torch.empty(27, n, dtype=torch.int32, device=dev)
-    pout = torch.empty(27, n, dtype=torch.int32, device=dev)
-    cnt = torch.empty(27, dtype=torch.int32, device=dev)
-    w = L.ws(L.lib().u3d_subm_rulebook_ws_bytes(n), dev)
-    L.call('u3d_subm_rulebook', L.ptr(coords), n, *index.table(), index.B, *index.shape,
-           L.ptr(pin), L.ptr(pout), L.ptr(cnt), L.ptr(w), L.stream())
-    rb = Rulebook(pin, pout, cnt, 27, n, n)
-    rb.coords, rb.index = coords, index
-    return rb
-
-
-def build_down_rulebook(coords: torch.Tensor, B: int, shape):
-    """Returns (out_coords, out_shape, out_index, Rulebook)."""
-    n = coords.shape[0]
-    dev = coords.device
-    oshape = [int(s) // 2 for s in shape]
-    ix2 = OccupancyIndex.from_coords(coords, B, oshape, shift=1)
-    n2 = ix2.count()
-    oc = ix2.coords(n2)
-    pin = torch.empty(8, n, dtype=torch.int32, device=dev)
-    pout = torch.empty(8, n, dtype=torch.int32, device=dev)
-    cnt = torch.empty(8, dtype=torch.int32, device=dev)
-    w = L.ws(L.lib().u3d_down_rulebook_ws_bytes(n), dev)
-    L.call('u3d_down_rulebook', L.ptr(coords), n, *ix2.table(), B, *oshape,
-           L.ptr(pin), L.ptr(pout), L.ptr(cnt), L.ptr(w), L.stream())
-    return oc, oshape, ix2, Rulebook(pin, pout, cnt, 8, n, n2)
-
-
-def _triple(v, what: str):
-    """an integer or a 3-sequence of integers (anything with ``__index__``: Python ints, numpy integer scalars; no bools, no floats)
-    -> (a, b, c) of Python ints"""
-    def as_int(a):
-        if isinstance(a, bool):
-            raise TypeError
-        return operator.index(a)
-    try:
-        try:
-            a = as_int(v)
-            return (a, a, a)
-        except TypeError:
-            t = tuple(as_int(a) for a in v)
-    except TypeError:
-        t = ()
-    if len(t) != 3:
-        raise L.U3DError(f'sparse conv: {what} must be an int or a sequence of three ints, got {v!r}')
-    return t
-
-
-def conv_geometry(kernel_size, stride=1, padding=0, dilation=1):
-    """(k0, k1, k2, s0, s1, s2, p0, p1, p2, d0, d1, d2) of a layer, refused where the geometry kernels (csrc/rulebook.hip) have no form
-    for it: 1 <= kernel extent <= 3, stride >= 1, padding >= 0, dilation >= 1 on every axis."""
-    k, s, p, d = _triple(kernel_size, 'kernel_size'), _triple(stride, 'stride'), _triple(padding, 'padding'), _triple(dilation, 'dilation')
-    if not all(1 <= a <= 3 for a in k):
-        raise L.U3DError(f'sparse conv: kernel_size {k}: every kernel extent must satisfy 1 <= extent <= 3 (K = 27 offsets at most)')
-    if not all(a >= 1 for a in s):
-        raise L.U3DError(f'sparse conv: stride {s}: every stride must be >= 1')
-    if not all(a >= 0 for a in p):
-        raise L.U3DError(f'sparse conv: padding {p}: every padding must be >= 0')
-    if not all(a >= 1 for a in d):
-        raise L.U3DError(f'sparse conv: dilation {d}: every dilation must be >= 1')
-    return (*k, *s, *p, *d)
-
-
-def _geom_array(geom):
-    return (ctypes.c_int * 12)(*geom)
-
-
-def conv_out_shape(geom, shape):
-    """per axis floor((in + 2 p - d (k - 1) - 1) / s) + 1, 0 where that is not positive (u3d_conv_out_shape, host only)"""
-    out = (ctypes.c_int * 3)()
-    L.call('u3d_conv_out_shape', _geom_array(geom), *[int(s) for s in shape], out)
-    return [int(v) for v in out]
-
-
-def build_conv_rulebook(coords: torch.Tensor, index: OccupancyIndex, B: int, shape, geom, subm: bool = False):
-    """General geometry (csrc/rulebook.hip, conv_mark_k / conv_count_k / conv_write_k): kernel extents 1..3, any stride / padding /
-    dilation, spconv's rule.  ``index``: the occupancy index of the INPUT level ``coords``.  ``subm``: the output set is the input set
-    (``geom`` then carries stride 1 and the padding d (k - 1) / 2).  Returns (out_coords, out_shape, out_index, Rulebook).
-    The rulebook's lists are [K, cap] with cap = min(n_in, n_out) (at least 1): for a fixed offset the pairs are a monotone partial
-    bijection between the two levels, so both columns ascend and neither side has more pairs than rows.  It leaves ``Rulebook.coords`` /
-    ``index`` unset: those mean "SubM k=3, dilation 1" to the tile-stationary kernels (``_conv_route``)."""
-    n, dev = coords.shape[0], coords.device
-    shape = [int(s) for s in shape]
-    K = geom[0] * geom[1] * geom[2]
-    g = _geom_array(geom)
-    if subm:
-        oc, oshape, ix_out, n2 = coords, shape, index, n
-    else:
-        oshape = conv_out_shape(geom, shape)
-        if min(oshape) <= 0:
-            raise L.U3DError(f'sparse conv: spatial shape {shape} is smaller than the reach of kernel {tuple(geom[:3])} with dilation '
-                             f'{tuple(geom[9:])} and padding {tuple(geom[6:9])}: the output level would have extent {oshape}')
-        if OccupancyIndex.wants_hash(B, oshape):
-            cells = torch.empty(K * n, dtype=torch.int64, device=dev)
-            if n:
-                L.call('u3d_conv_mark', L.ptr(coords), n, g, B, *shape, None, L.ptr(cells), L.stream())
-            ix_out = OccupancyIndex.from_cells(cells, B, oshape)
-        else:
-            ix_out = OccupancyIndex.alloc(B, oshape, dev)
-            if n:
-                L.call('u3d_conv_mark', L.ptr(coords), n, g, B, *shape, L.ptr(ix_out.bitmap), None, L.stream())
-            ix_out.build_rank()
-        n2 = ix_out.count()
-        oc = ix_out.coords(n2)
-    cap = max(1, min(n, n2))
-    pin = torch.empty(K, cap, dtype=torch.int32, device=dev)
-    pout = torch.empty(K, cap, dtype=torch.int32, device=dev)
-    if n and n2:
-        cnt = torch.empty(K, dtype=torch.int32, device=dev)
-        w = L.ws(L.lib().u3d_conv_rulebook_ws_bytes(n2, K), dev)
-        L.call('u3d_conv_rulebook', L.ptr(oc), n2, n, *index.table(), B, *shape, g, cap, L.ptr(pin), L.ptr(pout), L.ptr(cnt), L.ptr(w), L.stream())
-    else:               # an empty level on either side: no pairs (the C entry points take n > 0 only)
-        cnt = torch.zeros(K, dtype=torch.int32, device=dev)
-    return oc, oshape, ix_out, Rulebook(pin, pout, cnt, K, n, n2)
-
-
-def output_padding_of(output_padding, geom):
-    """(q0, q1, q2) of a transposed layer, under ``_triple``'s rules; refused where torch refuses it: 0 <= q < max(stride, dilation)"""
-    q = _triple(output_padding, 'output_padding')
-    s, d = geom[3:6], geom[9:]
-    if not all(0 <= q[a] < max(s[a], d[a]) for a in range(3)):
-        raise L.U3DError(f'sparse conv: output_padding {q}: every output padding must be >= 0 and smaller than max(stride, dilation) = '
-                         f'{tuple(max(s[a], d[a]) for a in range(3))}')
-    return q
-
-
-def convt_out_shape(geom, outpad, shape):
-    """per axis (in - 1) s - 2 p + d (k - 1) + q + 1, torch's rule (u3d_convt_out_shape, host only); an empty grid is refused there"""
-    out = (ctypes.c_int * 3)()
-    L.call('u3d_convt_out_shape', _geom_array(geom), (ctypes.c_int * 3)(*outpad), *[int(s) for s in shape], out)
-    return [int(v) for v in out]
-
-
-def build_convt_rulebook(coords: torch.Tensor, B: int, shape, geom, outpad):
-    """Transposed convolution (csrc/rulebook.hip convt_mark_k, then the general builder's count / write passes): input cell i pairs with
-    output cell o = i s - p + t d.  That is ``build_conv_rulebook``'s relation o' s - p + t d = i' with the two levels swapped, so the
-    pair lists are those of "the SparseConv3d of this geometry from the NEW level, restricted to these rows": u3d_conv_rulebook with the
-    layer's input rows on its stationary side and the new level's index on its looked-up side.  Returns (out_coords, out_shape,
-    out_index, Rulebook) with pair_in = new-level rows, pair_out = layer-input rows (n_in = n_new, n_out = n): the layer runs
-    ``sparse_conv(..., mode='inv')``, the path ``SparseInverseConv3d`` takes over a general rulebook.  Both columns ascend inside an offset
-    (the same monotone map, read from the other side), cap = min(n_in, n_out) (at least 1); one host read, ``count()``.  It leaves
-    ``Rulebook.coords`` / ``index`` unset (``_conv_route``)."""
-    n, dev = coords.shape[0], coords.device
-    shape = [int(s) for s in shape]
-    K = geom[0] * geom[1] * geom[2]
-    g, q = _geom_array(geom), (ctypes.c_int * 3)(*outpad)
-    try:
-        oshape = convt_out_shape(geom, outpad, shape)
-    except L.U3DError as e:
-        raise L.U3DError(f'sparse conv transpose: spatial shape {shape} with kernel {tuple(geom[:3])}, stride {tuple(geom[3:6])}, padding '
-                         f'{tuple(geom[6:9])}, dilation {tuple(geom[9:])} and output padding {tuple(outpad)} has no output level: {e}') from None
-    if OccupancyIndex.wants_hash(B, oshape):
-        cells = torch.empty(K * n, dtype=torch.int64, device=dev)
-        if n:
-            L.call('u3d_convt_mark', L.ptr(coords), n, g, q, B, *shape, None, L.ptr(cells), L.stream())
-        ix_out = OccupancyIndex.from_cells(cells, B, oshape)
-    else:
-        ix_out = OccupancyIndex.alloc(B, oshape, dev)
-        if n:
-            L.call('u3d_convt_mark', L.ptr(coords), n, g, q, B, *shape, L.ptr(ix_out.bitmap), None, L.stream())
-        ix_out.build_rank()
-    n2 = ix_out.count()
-    oc = ix_out.coords(n2)
-    cap = max(1, min(n, n2))
-    pin = torch.empty(K, cap, dtype=torch.int32, device=dev)
-    pout = torch.empty(K, cap, dtype=torch.int32, device=dev)
-    if n and n2:
-        cnt = torch.empty(K, dtype=torch.int32, device=dev)
-        w = L.ws(L.lib().u3d_conv_rulebook_ws_bytes(n, K), dev)
-        L.call('u3d_conv_rulebook', L.ptr(coords), n, n2, *ix_out.table(), B, *oshape, g, cap, L.ptr(pin), L.ptr(pout), L.ptr(cnt), L.ptr(w), L.stream())
-    else:               # no input rows, or none whose taps reach the output grid: no pairs (the C entry points take n > 0 only)
-        cnt = torch.zeros(K, dtype=torch.int32, device=dev)
-    return oc, oshape, ix_out, Rulebook(pin, pout, cnt, K, n2, n)
 
 
 # ----------------------------------------------------------------------------------------
@@ -1384,10 +993,7 @@ class SparseConvTensor:
     @property
     def index(self) -> OccupancyIndex:
         if self._index is None:
-            key = ('__index__', tuple(self.spatial_shape), self.indices.data_ptr())
-            if key not in self.indice_dict:
-                self.indice_dict[key] = OccupancyIndex.from_coords(self.indices, self.batch_size, self.spatial_shape)
-            self._index = self.indice_dict[key]
+            self._index = tensor_index(self.indice_dict, self.indices, self.batch_size, self.spatial_shape)
         return self._index
 
 
@@ -1451,47 +1057,6 @@ def _pad16(f):
     return f if c % 16 == 0 else F.pad(f, (0, 16 - c % 16))
 
 
-_DOWN_K2S2 = (2, 2, 2, 2, 2, 2, 0, 0, 0, 1, 1, 1)      # the U-Net's strided layer: the hard-coded parity rulebook (``build_down_rulebook``)
-
-
-def _agree(layer, rb: Rulebook, mine):
-    """a rulebook found under a layer's ``indice_key`` must have been built for that layer's geometry"""
-    if rb.geom is not None and rb.geom != mine:
-        raise L.U3DError(f'{type(layer).__name__}: indice_key {layer.indice_key!r} holds a rulebook built for geometry {rb.geom}, this layer '
-                         f'has {mine}: layers that share an indice_key must share kernel_size, stride, padding and dilation')
-
-
-class UpLevel(tuple):
-    """(out_coords, out_shape, out_index, Rulebook) of a ``SparseConvTranspose3d``: its ``indice_dict`` entry, under ('__up__', name) and
-    under the plain ``indice_key``, where the other layer kinds recognise it by its type"""
-
-
-def strided_geometry(layer, x: 'SparseConvTensor'):
-    """(out_coords, out_shape, out_index, Rulebook) of a layer that moves to a new level -- ``SparseConv3d`` and the pooling layers, which
-    consume exactly the same geometry: ``layer.geom`` (the 12 integers of ``conv_geometry``) and ``layer.indice_key``.  Cached in
-    ``indice_dict`` (the inverse conv reads the same entry), so it can be built ahead of the feature pass (``prepare_geometry``), and a
-    pool and a convolution that share a key and a geometry share one rulebook.  A layer without an ``indice_key`` caches under its own
-    identity: nothing else can pick its rulebook up."""
-    general, mine = layer.geom != _DOWN_K2S2, ('conv', *layer.geom)
-    name = layer.indice_key if layer.indice_key is not None or not general else ('__anon__', id(layer))
-    key = ('__down__', name)
-    if key not in x.indice_dict:
-        if isinstance(x.indice_dict.get(name), UpLevel):
-            raise L.U3DError(f'{type(layer).__name__}: indice_key {name!r} is taken by a SparseConvTranspose3d')
-        if general:
-            oc, oshape, ix2, rb = build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, layer.geom)
-        else:
-            oc, oshape, ix2, rb = build_down_rulebook(x.indices, x.batch_size, x.spatial_shape)
-        rb.geom = mine
-        rb.tag = key if not isinstance(name, tuple) else None
-        x.indice_dict[key] = (oc, oshape, ix2, rb)
-        if not isinstance(name, tuple):
-            x.indice_dict[name] = (rb, x.indices, x.spatial_shape, x._index)
-    else:
-        _agree(layer, x.indice_dict[key][3], mine)
-    return x.indice_dict[key]
-
-
 class _ConvBase(SparseModule):
     """Weight [C_out, k0, k1, k2, C_in] and the layer geometry (``conv_geometry``: each of kernel_size / stride / padding / dilation an int
     or a 3-sequence).  ``kernel_size`` keeps the int of a cubic kernel (a tuple otherwise); ``K`` is the number of offsets.
@@ -1505,12 +1070,8 @@ class _ConvBase(SparseModule):
         if bias and not self._takes_bias:
             raise L.U3DError(f'{type(self).__name__}: bias=True is not built for this layer kind (SparseInverseConv3d and '
                              f'SparseConvTranspose3d take one)')
-        self.geom = conv_geometry(kernel_size, stride, padding, dilation)
-        k = self.geom[:3]
+        k = layer_geometry(self, conv_geometry(kernel_size, stride, padding, dilation))
         self.in_channels, self.out_channels, self.indice_key = in_channels, out_channels, indice_key
-        self.kernel_size = k[0] if k[0] == k[1] == k[2] else k
-        self.stride, self.padding, self.dilation = self.geom[3:6], self.geom[6:9], self.geom[9:]
-        self.K = k[0] * k[1] * k[2]
         self.weight = nn.Parameter(torch.empty(out_channels, *k, in_channels))
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
         if bias:                # fp32 [C_out], uniform in +-1 / sqrt(K C_in) (the fan-in of the weight above)
@@ -1519,9 +1080,6 @@ class _ConvBase(SparseModule):
             nn.init.uniform_(self.bias, -bound, bound)
         else:
             self.register_parameter('bias', None)
-
-    def _agree(self, rb: Rulebook, mine):
-        _agree(self, rb, mine)
 
     def _biased(self, y: torch.Tensor) -> torch.Tensor:
         """y + bias on every row of the layer's result, rows without a pair included (``sparse_bias``); y itself without a bias"""
@@ -1570,22 +1128,11 @@ class SubMConv3d(_ConvBase):
         return x.replace_feature(self._conv(x, self.geometry(x), 'fwd', addend))
 
     def geometry(self, x: SparseConvTensor) -> Rulebook:
-        key = self.indice_key if self.indice_key is not None else ('__subm__', id(self))
-        rb = x.indice_dict.get(key)
-        if rb is None:
+        def build():
             if self.general:
-                rb = build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, self._subm_geom, subm=True)[3]
-            else:
-                rb = build_subm_rulebook(x.indices, x.index)
-            rb.geom = self._rb_geom
-            rb.tag = ('subm', key) if isinstance(key, str) else None
-            x.indice_dict[key] = rb
-        elif not isinstance(rb, Rulebook):
-            taker = 'SparseConvTranspose3d' if isinstance(rb, UpLevel) else 'strided convolution'
-            raise L.U3DError(f'SubMConv3d: indice_key {self.indice_key!r} is taken by a {taker}')
-        else:
-            self._agree(rb, self._rb_geom)
-        return rb
+                return build_conv_rulebook(x.indices, x.index, x.batch_size, x.spatial_shape, self._subm_geom, subm=True)[3]
+            return build_subm_rulebook(x.indices, x.index)
+        return cached_level(x, 'subm', self, self._rb_geom, build)
 
 
 class SparseConv3d(_ConvBase):
@@ -1616,11 +1163,8 @@ class _PoolBase(SparseModule):
         super().__init__()
         if subm:
             raise L.U3DError(f'{type(self).__name__}: subm=True is not built')
-        self.geom = conv_geometry(kernel_size, kernel_size if stride is None else stride, padding, dilation)
-        k = self.geom[:3]
-        self.kernel_size = k[0] if k[0] == k[1] == k[2] else k
-        self.stride, self.padding, self.dilation = self.geom[3:6], self.geom[6:9], self.geom[9:]
-        self.K, self.indice_key = k[0] * k[1] * k[2], indice_key
+        layer_geometry(self, conv_geometry(kernel_size, kernel_size if stride is None else stride, padding, dilation))
+        self.indice_key = indice_key
 
     def geometry(self, x: SparseConvTensor):
         return strided_geometry(self, x)
@@ -1651,12 +1195,12 @@ class SparseInverseConv3d(_ConvBase):
         super().__init__(in_channels, out_channels, kernel_size, bias, indice_key)
 
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
-        entry = x.indice_dict.get(self.indice_key)
-        if entry is None:
+        kind, entry = saved_under(x.indice_dict, self.indice_key)
+        if kind is None:
             raise L.U3DError(f'SparseInverseConv3d: no rulebook saved under {self.indice_key!r}')
-        if isinstance(entry, Rulebook):
+        if kind == 'subm':
             raise L.U3DError(f'SparseInverseConv3d: indice_key {self.indice_key!r} belongs to a SubMConv3d, not to a SparseConv3d')
-        if isinstance(entry, UpLevel):
+        if kind == 'up':
             raise L.U3DError(f'SparseInverseConv3d: indice_key {self.indice_key!r} belongs to a SparseConvTranspose3d: inverting a '
                              f'transposed layer is not built')
         rb, idx, shape, index = entry
@@ -1674,7 +1218,7 @@ class SparseConvTranspose3d(_ConvBase):
     Output extent per axis: (in - 1) s - 2 p + d (k - 1) + q + 1, torch's rule.  spconv's own rule for this layer leaves the dilation out
     ((in - 1) s - 2 p + k + q); the two agree at dilation 1.  ``output_padding`` must be smaller than max(stride, dilation), as in torch.
     An input row whose taps all fall outside the grid (padding beyond the reach) contributes nothing; an empty output level gives an
-    empty tensor.  The rulebook is cached under ('__up__', indice_key) -- the layer's own identity without a key; two transposed layers
+    empty tensor.  The rulebook is cached under the layer's indice_key (``geometry.cached_level``) -- its own identity without a key; two transposed layers
     that share a key must share the geometry, output padding included.  Geometry and launch path: ``build_convt_rulebook``."""
     _takes_bias = True
 
@@ -1686,23 +1230,8 @@ class SparseConvTranspose3d(_ConvBase):
 
     def geometry(self, x: SparseConvTensor) -> UpLevel:
         """Output level + rulebook of this layer: (out_coords, out_shape, out_index, Rulebook), cached in ``indice_dict``"""
-        name = self.indice_key if self.indice_key is not None else ('__anon__', id(self))
-        key = ('__up__', name)
-        hit = x.indice_dict.get(key)
-        if hit is None:
-            named = not isinstance(name, tuple)
-            if named and (name in x.indice_dict or ('__down__', name) in x.indice_dict):
-                taker = 'SubMConv3d' if isinstance(x.indice_dict.get(name), Rulebook) else 'strided convolution or pooling layer'
-                raise L.U3DError(f'SparseConvTranspose3d: indice_key {name!r} is taken by a {taker}')
-            oc, oshape, ix, rb = build_convt_rulebook(x.indices, x.batch_size, x.spatial_shape, self.geom, self.output_padding)
-            rb.geom = self._rb_geom
-            rb.tag = key if named else None
-            hit = x.indice_dict[key] = UpLevel((oc, oshape, ix, rb))
-            if named:
-                x.indice_dict[name] = hit
-        else:
-            self._agree(hit[3], self._rb_geom)
-        return hit
+        return cached_level(x, 'up', self, self._rb_geom,
+                            lambda: build_convt_rulebook(x.indices, x.batch_size, x.spatial_shape, self.geom, self.output_padding))
 
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
         oc, oshape, ix, rb = self.geometry(x)
