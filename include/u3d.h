@@ -508,6 +508,33 @@ int u3d_bias_grad(const float* dy, int64_t n, int C, float* db, void* ws, u3d_st
 int64_t u3d_bias_grad_ws_bytes(int64_t n, int C);
 
 /* =====================================================================================
+ * S1  Sparse tensors on different voxel sets: union add and pruning (csrc/sparse_sets.hip).  Rows fp32 [n, C]; row maps int32.
+ *   u3d_index_rows: rows_out[i] = the canonical row of coords[i] = (b, x, y, z) in the occupancy index (either form, as every entry
+ *     point takes it), or -1 for a cell that is absent, outside the grid or outside the batch [0, B).  Thread = row.
+ *   u3d_mask_compact: mask uint8 [n] (a torch.bool tensor's bytes; non-zero = keep).  kept int32 [n] receives the kept rows in ascending
+ *     order in its first n_kept entries (the rest is not touched), pos int32 [n] the position of every row in that list or -1 (every
+ *     entry written), n_kept int32 [1] the count.  Block counts, a scan of the block counts, a wave-64 ballot prefix inside each block:
+ *     stable, no atomics, one result.  ws: u3d_mask_compact_ws_bytes(n) = (2 ceil(n / 256) + 64) * 4 bytes; 0 for n <= 0.
+ *   u3d_rows_take: y[j] = x[rows[j]] for j < n_out, bit for bit; a row value outside [0, n_src) (unsigned compare: -1, n_src, anything)
+ *     gives a row of +0.0.  Serves a gather by the kept list, a scatter read through the position list, and int32 [n, 4] coordinate
+ *     rows viewed as C = 4 (16-byte moves: the bits are not touched).
+ *   u3d_rows_take2: y[j] = a[rows_a[j]] + b[rows_b[j]] in one pass: the fp32 sum (one rounding) where both rows are present, the BITS of
+ *     the present row where one is (-0.0 stays -0.0, a NaN keeps its payload), +0.0 where neither is.  Absent: as above, against n_a / n_b.
+ *   Every destination element is written exactly once: no atomics, no memset, results are bit-reproducible.  Rows past n_out are not
+ *   touched.  y must not overlap an input.
+ *   Contract: C % 4 == 0, 4 <= C <= 512, every count < 2^31.  Errors, before any HIP call and with a u3d_last_error text: U3D_EINVAL
+ *   for NULL pointers, n <= 0 / n_out <= 0, a negative source count and (u3d_index_rows) an empty grid; U3D_EUNSUPPORTED for other widths
+ *   and for counts >= 2^31.  Empty inputs are the caller's business (no launch).  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+int u3d_index_rows(const int32_t* coords, int64_t n, const uint64_t* bitmap, const int32_t* word_rank, int64_t hash_slots, int B, int X, int Y,
+                   int Z, int32_t* rows_out, u3d_stream_t stream);
+int u3d_mask_compact(const uint8_t* mask, int64_t n, int32_t* kept, int32_t* pos, int32_t* n_kept, void* ws, u3d_stream_t stream);
+int64_t u3d_mask_compact_ws_bytes(int64_t n);
+int u3d_rows_take(const float* x, const int32_t* rows, int64_t n_out, int64_t n_src, int C, float* y, u3d_stream_t stream);
+int u3d_rows_take2(const float* a, const int32_t* rows_a, int64_t n_a, const float* b, const int32_t* rows_b, int64_t n_b, int64_t n_out, int C,
+                   float* y, u3d_stream_t stream);
+
+/* =====================================================================================
  * K13  self-attention core of nn.MultiheadAttention(256, 8, batch_first) per scene
  *     (unidet3d/encoder.py:19-20,36-37): softmax(Q K^T / sqrt(hd)) V over packed variable
  *     length scenes.  qkv [n_total, 3*H*hd] (the in_proj output), cu_seqlens int32 [B+1],

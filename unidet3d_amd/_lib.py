@@ -125,6 +125,12 @@ PROTOTYPES = {
     'u3d_bias_add': (_i32, [_vp, _vp, _i64, _i32, _vp]),
     'u3d_bias_grad': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
     'u3d_bias_grad_ws_bytes': (_i64, [_i64, _i32]),
+    # sparse tensors on different voxel sets (csrc/sparse_sets.hip; added entry points, same ABI version)
+    'u3d_index_rows': (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'u3d_mask_compact': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_mask_compact_ws_bytes': (_i64, [_i64]),
+    'u3d_rows_take': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    'u3d_rows_take2': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'u3d_segment_gather_sum': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     'u3d_segment_mean_xyz': (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'u3d_segment_minmax_xyz': (_i32, [_vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),

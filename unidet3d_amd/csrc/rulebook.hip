@@ -7,11 +7,9 @@
 // order by construction and the pair lists are bit-exact against the CPU oracle.
 // Pair lists are produced by a two-pass stable compaction: per-block counts (ballot/popcount),
 // a per-offset scan of block counts, then a wave-64 ballot prefix inside each block.
-#include "u3d_common.h"
+#include "rb_compact.h"      // RB_T, rb_scan_k, rb_block_rank: shared with sparse_sets.hip
 
 namespace u3d {
-
-constexpr int RB_T = 256;
 
 // val[k*n + i] = parent row if offset(i) == k (and the parent is inside the halved grid) else -1
 __global__ __launch_bounds__(RB_T) void down_nbr_k(const int32_t* __restrict__ coords, int64_t n, Index ix2, int32_t* val) {
@@ -44,53 +42,17 @@ __global__ __launch_bounds__(RB_T) void rb_count_k(const int32_t* __restrict__ v
     if (threadIdx.x == 0) block_cnt[(int64_t)k * nblk + blockIdx.x] = c;
 }
 
-// one block per offset: exclusive scan of its block counts
-__global__ __launch_bounds__(RB_T) void rb_scan_k(const int32_t* __restrict__ block_cnt, int nblk, int32_t* block_base, int32_t* counts) {
-    __shared__ int s_w[RB_T / 64];
-    __shared__ int s_carry;
-    const int k = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblk; base += RB_T) {
-        const int i = base + threadIdx.x;
-        const int v = i < nblk ? block_cnt[(int64_t)k * nblk + i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            int t = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < RB_T / 64; ++w) { int t = s_w[w]; if (w < wave) woff += t; tot += t; }
-        const int carry = s_carry;
-        if (i < nblk) block_base[(int64_t)k * nblk + i] = carry + woff + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry = carry + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[k] = s_carry;
-}
-
 // stable compaction: list_row[k][pos] = r, list_val[k][pos] = val[k][r]   grid (nblk, K)
 __global__ __launch_bounds__(RB_T) void rb_write_k(const int32_t* __restrict__ val, int64_t n, int nblk, const int32_t* __restrict__ block_base,
                                                    int64_t cap, int32_t* list_row, int32_t* list_val) {
     __shared__ int s_w[RB_T / 64];
     const int64_t r = (int64_t)blockIdx.x * RB_T + threadIdx.x;
-    const int k = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = blockIdx.y;
     const int v = r < n ? val[(int64_t)k * n + r] : -1;
     const bool ok = v >= 0;
-    const unsigned long long m = __ballot(ok);
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[wave] = __popcll(m);
-    __syncthreads();
-    int woff = 0;
-#pragma unroll
-    for (int w = 0; w < RB_T / 64; ++w) if (w < wave) woff += s_w[w];
+    const int rank = rb_block_rank(ok, s_w);
     if (ok) {
-        const int64_t pos = (int64_t)k * cap + block_base[(int64_t)k * nblk + blockIdx.x] + woff + rank;
+        const int64_t pos = (int64_t)k * cap + block_base[(int64_t)k * nblk + blockIdx.x] + rank;
         list_row[pos] = (int)r;
         list_val[pos] = v;
     }
@@ -119,18 +81,12 @@ __global__ __launch_bounds__(RB_T) void subm_write_k(const int32_t* __restrict__
                                                      const int32_t* __restrict__ block_base, int64_t cap, int32_t* list_row, int32_t* list_val) {
     __shared__ int s_w[RB_T / 64];
     const int64_t r = (int64_t)blockIdx.x * RB_T + threadIdx.x;
-    const int k = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = blockIdx.y;
     const int v = r < n ? subm_lookup(coords, r, k, ix) : -1;
     const bool ok = v >= 0;
-    const unsigned long long m = __ballot(ok);
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[wave] = __popcll(m);
-    __syncthreads();
-    int woff = 0;
-#pragma unroll
-    for (int w = 0; w < RB_T / 64; ++w) if (w < wave) woff += s_w[w];
+    const int rank = rb_block_rank(ok, s_w);
     if (ok) {
-        const int64_t pos = (int64_t)k * cap + block_base[(int64_t)k * nblk + blockIdx.x] + woff + rank;
+        const int64_t pos = (int64_t)k * cap + block_base[(int64_t)k * nblk + blockIdx.x] + rank;
         list_row[pos] = (int)r;
         list_val[pos] = v;
     }
@@ -240,17 +196,10 @@ __global__ __launch_bounds__(RB_T) void conv_write_k(const int32_t* __restrict__
                                                      const int32_t* __restrict__ block_base, int64_t cap, int32_t* list_row, int32_t* list_val) {
     __shared__ int s_w[RB_T / 64];
     const int64_t r = (int64_t)blockIdx.x * RB_T + threadIdx.x;
-    const int k = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = blockIdx.y;
     const int v = r < n ? conv_lookup(out_coords, r, k, g, ix) : -1;
     const bool ok = v >= 0;
-    const unsigned long long m = __ballot(ok);
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[wave] = __popcll(m);
-    __syncthreads();
-    int woff = 0;
-#pragma unroll
-    for (int w = 0; w < RB_T / 64; ++w) if (w < wave) woff += s_w[w];
-    const int64_t at = (int64_t)block_base[(int64_t)k * nblk + blockIdx.x] + woff + rank;
+    const int64_t at = (int64_t)block_base[(int64_t)k * nblk + blockIdx.x] + rb_block_rank(ok, s_w);
     if (ok && at < cap) {       // (at < cap always holds for cap >= min(n_in, n_out), which the entry point checks)
         list_row[(int64_t)k * cap + at] = (int)r;
         list_val[(int64_t)k * cap + at] = v;

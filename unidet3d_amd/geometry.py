@@ -1,7 +1,8 @@
 """Sparse geometry (host side): the occupancy index of a level, the rulebooks over it, the per-forward level cache.  Integer kernels only:
 no features, no autograd, nothing of the package but the C ABI (``_lib``); ``unidet3d_amd.sparse`` re-exports the public names.
 Decided here and nowhere else: how an index is made (``OccupancyIndex.from_marks``), how a general layer's new level gets its pair lists
-(``_level_pairs``), what lives where in a ``SparseConvTensor.indice_dict`` (``cached_level``; readers ``saved_under`` / ``tensor_index``)."""
+(``_level_pairs``), what lives where in a ``SparseConvTensor.indice_dict`` (``cached_level``; readers ``saved_under`` / ``tensor_index``),
+how a level is made from other levels (``build_union_level``, ``compact_mask``)."""
 from __future__ import annotations
 
 import ctypes
@@ -104,6 +105,15 @@ class OccupancyIndex:
         elif n:
             L.call('u3d_index_coords', L.ptr(self.bitmap), L.ptr(self.rank), self.B, *self.shape, L.ptr(c), L.stream())
         return c
+
+    def rows_of(self, coords: torch.Tensor) -> torch.Tensor:
+        """int32 [n]: the canonical row of every coordinate (int32 [n, 4] = (b, x, y, z)) in this index, -1 for a cell that is absent or
+        outside the grid or the batch (u3d_index_rows); no coordinates, no launch"""
+        n = coords.shape[0]
+        rows = torch.empty(n, dtype=torch.int32, device=coords.device)
+        if n:
+            L.call('u3d_index_rows', L.ptr(coords), n, *self.table(), self.B, *self.shape, L.ptr(rows), L.stream())
+        return rows
 
     @staticmethod
     def from_coords(coords: torch.Tensor, B: int, shape, shift: int = 0) -> 'OccupancyIndex':
@@ -421,6 +431,73 @@ def build_convt_rulebook(coords: torch.Tensor, B: int, shape, geom, outpad):
     ix_out = _marked_level(coords, B, shape, oshape, geom, 'u3d_convt_mark', (ctypes.c_int * 3)(*outpad))
     oc, n2, pin, pout, cnt = _level_pairs(coords, None, B, shape, geom, new=ix_out, transposed=True)
     return oc, oshape, ix_out, Rulebook(pin, pout, cnt, pin.shape[0], n2, coords.shape[0])
+
+
+# ----------------------------------------------------------------------------------------
+# levels made from levels: the union of two voxel sets, the rows a mask keeps
+# ----------------------------------------------------------------------------------------
+class UnionLevel:
+    """The union of two levels A and B of one grid.  ``coords`` / ``index`` / ``n``: its rows (canonical order), occupancy index and row
+    count; ``rows_a`` / ``rows_b`` int32 [n]: the operand row of every union row, or -1; ``same``: 'a' / 'b' when the union IS that
+    operand's level (then ``coords`` and ``index`` are that operand's own objects), else None.  ``into(which)``: int32 [n_operand], the
+    union row of every operand row (the backward's map), built on first use."""
+
+    def __init__(self, coords, index, n, rows_a, rows_b, same, a_coords, b_coords):
+        self.coords, self.index, self.n, self.rows_a, self.rows_b, self.same = coords, index, n, rows_a, rows_b, same
+        self._operand = {'a': a_coords, 'b': b_coords}
+        self._into: Dict = {}
+
+    def into(self, which: str) -> torch.Tensor:
+        if which not in self._into:      # every operand cell is in the union: no -1, and the map is injective
+            self._into[which] = self.index.rows_of(self._operand[which])
+        return self._into[which]
+
+
+def build_union_level(a_coords, a_index: OccupancyIndex, b_coords, b_index: OccupancyIndex, B: int, shape) -> UnionLevel:
+    """The level on the union of the rows ``a_coords`` and ``b_coords`` (both canonical, one grid).  The index comes from
+    ``OccupancyIndex.from_marks`` like every other: two marks into the one zeroed bitmap (``atomicOr``: the union) and the rank pass, or
+    the two cell-id lists concatenated into the hashed build (which drops the duplicates).  One host read, ``count()``.  A union with as
+    many rows as an operand IS that operand's level -- canonical order makes "a superset with the same count" the same rows in the same
+    order -- and keeps that operand's coordinate tensor and index; otherwise ``coords(n)`` writes the new rows.  The destination-major
+    maps are the union's coordinates looked up in each operand's index (``rows_of``)."""
+    shape = [int(s) for s in shape]
+    na, nb, dev = a_coords.shape[0], b_coords.shape[0], a_coords.device
+
+    def mark(bitmap):
+        if bitmap is not None:
+            for c in (a_coords, b_coords):
+                if c.shape[0]:
+                    L.call('u3d_index_mark', L.ptr(c), c.shape[0], 0, *shape, L.ptr(bitmap), L.stream())
+            return None
+        cells = torch.empty(na + nb, dtype=torch.int64, device=dev)
+        for c, out in ((a_coords, cells[:na]), (b_coords, cells[na:])):
+            if c.shape[0]:
+                L.call('u3d_cells_of_coords', L.ptr(c), c.shape[0], 0, B, *shape, L.ptr(out), L.stream())
+        return cells
+    ix = OccupancyIndex.from_marks(B, shape, dev, mark)
+    n = ix.count()
+    same = 'a' if n == na else 'b' if n == nb else None
+    if same is not None:
+        coords, ix = (a_coords, a_index) if same == 'a' else (b_coords, b_index)
+    else:
+        coords = ix.coords(n)
+    return UnionLevel(coords, ix, n, a_index.rows_of(coords), b_index.rows_of(coords), same, a_coords, b_coords)
+
+
+def compact_mask(keep: torch.Tensor):
+    """(kept int32 [n_keep] ascending, pos int32 [n]: the position of a row in ``kept`` or -1, n_keep) of a torch.bool mask [n] on the
+    device (u3d_mask_compact: block counts, scan, ballot prefix; stable, no atomics).  One host read, the count; an empty mask launches
+    nothing."""
+    n, dev = keep.shape[0], keep.device
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    pos = torch.empty(n, dtype=torch.int32, device=dev)
+    if not n:
+        return kept, pos, 0
+    n_dev = torch.empty(1, dtype=torch.int32, device=dev)
+    w = L.ws(L.lib().u3d_mask_compact_ws_bytes(n), dev)
+    L.call('u3d_mask_compact', L.ptr(keep), n, L.ptr(kept), L.ptr(pos), L.ptr(n_dev), L.ptr(w), L.stream())
+    n_keep = int(n_dev.item())             # documented read-back (one host sync), as ``OccupancyIndex.count``
+    return kept[:n_keep], pos, n_keep
 
 
 # ----------------------------------------------------------------------------------------

@@ -7,8 +7,10 @@ replace_feature / per-forward ``indice_dict`` rulebook cache keyed by
 ``indice_key``), ``SparseSequential``, ``SubMConv3d``, ``SparseConv3d``,
 ``SparseInverseConv3d``; plus the BatchNorm the reference takes from torch
 (``nn.SyncBatchNorm`` / ``nn.BatchNorm1d``), spconv's ``SparseMaxPool3d`` /
-``SparseAvgPool3d`` on the strided convolution's geometry, and ``SparseConvTranspose3d``
-(with ``output_padding``).  Same constructor arguments, same parameter names (``weight``,
+``SparseAvgPool3d`` on the strided convolution's geometry, ``SparseConvTranspose3d``
+(with ``output_padding``), and the two operations a generative decoder puts behind it: ``sparse_add`` (spconv's
+``functional.sparse_add``: operands on different voxel sets, result on their union) and ``prune`` / ``SparsePrune``
+(MinkowskiEngine's ``MinkowskiPruning``: drop voxels by a mask).  Same constructor arguments, same parameter names (``weight``,
 ``bias`` with ``bias=True``) and weight layout ``[C_out, k, k, k, C_in]``.
 
 Every compute step is a call through the C ABI (include/u3d.h); there is no
@@ -43,7 +45,8 @@ from . import precision as P
 from . import account
 from . import wgrad_stream as WS
 from .geometry import (OccupancyIndex, Rulebook, UpLevel, build_subm_rulebook, build_conv_rulebook, build_convt_rulebook, conv_geometry,
-                       output_padding_of, strided_geometry, cached_level, layer_geometry, saved_under, tensor_index, _DOWN_K2S2)
+                       output_padding_of, strided_geometry, cached_level, layer_geometry, saved_under, tensor_index, _DOWN_K2S2,
+                       UnionLevel, build_union_level, compact_mask)
 from .geometry import build_down_rulebook, conv_out_shape, convt_out_shape, _geom_array, _TILE_HISTORY      # noqa: F401  (re-exported)
 from .wgrad_stream import set_wgrad_overlap, async_dw_ok, join_wgrad_stream, end_of_backward, _ASYNC_DW_SEEN      # noqa: F401  (re-exported)
 
@@ -976,6 +979,84 @@ class SparseBatchNorm(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------
+# rows of one tensor at the rows of another (csrc/sparse_sets.hip, include/u3d.h section S1)
+# ----------------------------------------------------------------------------------------
+def _rows_check(t: torch.Tensor, what: str):
+    refuse_rows_only(t, what)
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise L.U3DError(f'{what}: features must be fp32 [n, C], got {t.dtype} {tuple(t.shape)} (fp32 rows under every operand format)')
+    C = t.shape[1]
+    if C % 4 or not 4 <= C <= 512:
+        raise L.U3DError(f'{what}: {C} channels: the gfx950 kernels take a multiple of 4 in 4..512')
+    if not t.is_cuda:
+        raise L.U3DError(f'{what}: u3d kernels need CUDA (HIP) tensors: the product path has no CPU fallback')
+
+
+def rows_take(x: torch.Tensor, rows: torch.Tensor, what: str = 'rows_take') -> torch.Tensor:
+    """y[j] = x[rows[j]], bit for bit; a row value outside [0, len(x)) gives a row of +0.0 (u3d_rows_take: every element of y written
+    once by the kernel).  No destination rows launches nothing; no source rows gives zeros without a launch."""
+    _rows_check(x, what)
+    n_out, (n_src, C) = rows.shape[0], x.shape
+    if not (n_out and n_src):
+        return torch.zeros(n_out, C, dtype=torch.float32, device=x.device)
+    y = torch.empty(n_out, C, dtype=torch.float32, device=x.device)
+    L.call('u3d_rows_take', L.ptr(x.contiguous()), L.ptr(rows), n_out, n_src, C, L.ptr(y), L.stream())
+    return y
+
+
+def rows_take2(a: torch.Tensor, rows_a: torch.Tensor, b: torch.Tensor, rows_b: torch.Tensor, what: str = 'rows_take2') -> torch.Tensor:
+    """y[j] = a[rows_a[j]] + b[rows_b[j]] in one pass (u3d_rows_take2): the fp32 sum where both rows are present, the bits of the
+    present one where one is, +0.0 where neither is.  Both operands have rows (an empty operand is the caller's case)."""
+    _rows_check(a, what)
+    _rows_check(b, what)
+    n_out, C = rows_a.shape[0], a.shape[1]
+    y = torch.empty(n_out, C, dtype=torch.float32, device=a.device)
+    if n_out:
+        L.call('u3d_rows_take2', L.ptr(a.contiguous()), L.ptr(rows_a), a.shape[0], L.ptr(b.contiguous()), L.ptr(rows_b), b.shape[0], n_out, C,
+               L.ptr(y), L.stream())
+    return y
+
+
+class _JoinFn(torch.autograd.Function):
+    """a and b on the union level ``lvl`` (``geometry.UnionLevel``).  The backward is two copies, da[i] = dy[union row of a's row i],
+    each made only where its operand asks for it; an operand whose level IS the union takes dy itself."""
+
+    @staticmethod
+    def forward(ctx, a, b, lvl: UnionLevel):
+        ctx.lvl = lvl
+        return rows_take2(a, lvl.rows_a, b, lvl.rows_b, 'sparse_add')
+
+    @staticmethod
+    def backward(ctx, dy):
+        lvl, dy = ctx.lvl, dy.contiguous()
+        grads = [None, None]
+        for i, which in enumerate('ab'):
+            if ctx.needs_input_grad[i]:
+                grads[i] = dy if lvl.same == which else rows_take(dy, lvl.into(which), 'sparse_add (backward)')
+        return grads[0], grads[1], None
+
+
+class _PruneFn(torch.autograd.Function):
+    """the rows ``kept`` of x; backward dx[i] = dy[pos[i]], +0.0 for a dropped row (pos -1) -- every element written by the kernel"""
+
+    @staticmethod
+    def forward(ctx, x, kept, pos):
+        ctx.save_for_backward(pos)
+        return rows_take(x, kept, 'prune')
+
+    @staticmethod
+    def backward(ctx, dy):
+        (pos,) = ctx.saved_tensors
+        return rows_take(dy.contiguous(), pos, 'prune (backward)'), None, None
+
+
+def _plain(t: torch.Tensor) -> torch.Tensor:
+    """the same values as a new tensor object: what a layer left on ``t`` for its reader (bf16 shadow, epilogue statistics, the
+    ``_u3d_from_conv`` mark: attributes of the object) does not travel, as behind ``sparse_bias``"""
+    return t.view(t.shape)
+
+
+# ----------------------------------------------------------------------------------------
 # SparseConvTensor + layers
 # ----------------------------------------------------------------------------------------
 class SparseConvTensor:
@@ -1236,3 +1317,80 @@ class SparseConvTranspose3d(_ConvBase):
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
         oc, oshape, ix, rb = self.geometry(x)
         return SparseConvTensor(self._conv(x, rb, 'inv'), oc, oshape, x.batch_size, x.indice_dict, ix)
+
+
+# ----------------------------------------------------------------------------------------
+# tensors on different voxel sets: union add, pruning
+# ----------------------------------------------------------------------------------------
+def _join_check(a: 'SparseConvTensor', b: 'SparseConvTensor'):
+    if a.batch_size != b.batch_size:
+        raise L.U3DError(f'sparse_add: the operands differ in batch_size: {a.batch_size} and {b.batch_size}')
+    if list(a.spatial_shape) != list(b.spatial_shape):
+        raise L.U3DError(f'sparse_add: the operands differ in spatial_shape: {a.spatial_shape} and {b.spatial_shape}')
+    fa, fb = a.features, b.features
+    refuse_rows_only(fa, 'sparse_add')
+    refuse_rows_only(fb, 'sparse_add')
+    if fa.dim() != 2 or fb.dim() != 2 or fa.shape[1] != fb.shape[1]:
+        raise L.U3DError(f'sparse_add: the operands differ in channel count: {tuple(fa.shape)} and {tuple(fb.shape)} features')
+
+
+def sparse_add(a: 'SparseConvTensor', b: 'SparseConvTensor', *more: 'SparseConvTensor') -> 'SparseConvTensor':
+    """a + b for tensors on DIFFERENT voxel sets of one grid (spconv's ``functional.sparse_add``, MinkowskiEngine's ``a + b``): the result
+    lives on the union of the active sets, rows in canonical order.  Per row and channel: the fp32 sum (one rounding) where both operands
+    have the voxel, exactly the bits of the one operand that has it otherwise.  More operands fold from the LEFT, ((a + b) + c) + ...:
+    that order is part of the contract (fp32 addition is not associative).  The operands must agree in batch_size, spatial_shape and
+    channel count.  fp32 rows under every operand format; the result hands no bf16 shadow, no epilogue statistics and no
+    ``_u3d_from_conv`` mark to its reader.  Backward: pure copies, da[i] = dy[row of a's voxel i], made only for an operand that asks.
+    Levels: a result on a NEW voxel set starts from a fresh, empty ``indice_dict`` (no rulebook of another row count can reach it); when
+    the union has as many rows as an operand (the other set lies inside it) the result keeps that operand's ``indices``, index and
+    ``indice_dict``; operands that share one ``indices`` tensor object build no geometry at all; an empty operand gives the other's level.
+    One host read (the row count of the union)."""
+    for other in (b, *more):                        # every operand, before the first launch: what must agree, then what the kernels take
+        _join_check(a, other)
+    for t in (a, b, *more):
+        _rows_check(t.features, 'sparse_add')
+        if t.features.device != a.features.device:
+            raise L.U3DError(f'sparse_add: the operands live on different devices: {a.features.device} and {t.features.device}')
+    if more:
+        return sparse_add(sparse_add(a, b), *more)
+    na, nb = a.features.shape[0], b.features.shape[0]
+    if a.indices is b.indices:                      # one level: a plain feature add
+        return a.replace_feature(a.features + b.features)
+    if not nb:
+        return a.replace_feature(_plain(a.features))
+    if not na:
+        return b.replace_feature(_plain(b.features))
+    lvl = build_union_level(a.indices, a.index, b.indices, b.index, a.batch_size, a.spatial_shape)
+    y = _JoinFn.apply(a.features, b.features, lvl)
+    if lvl.same is not None:
+        return (a if lvl.same == 'a' else b).replace_feature(y)
+    return SparseConvTensor(y, lvl.coords, a.spatial_shape, a.batch_size, None, lvl.index)
+
+
+def prune(x: 'SparseConvTensor', keep: torch.Tensor) -> 'SparseConvTensor':
+    """The voxels of ``x`` whose ``keep`` bit is set (MinkowskiEngine's ``MinkowskiPruning``), rows in their old order -- a subset of a
+    canonical order is canonical.  ``keep``: torch.bool [n] on the tensor's device, typically ``score > t`` or a scatter of top-k indices;
+    it takes no gradient.  Backward: dx[i] = dy[position of i] for a kept row, +0.0 for a dropped one.  The result lives on a new voxel
+    set and starts from a fresh, empty ``indice_dict`` -- unless every bit is set, then it keeps the level of ``x``; no bit set gives an
+    empty tensor.  fp32 rows under every operand format, nothing handed to the reader (``sparse_add``).  One host read (the kept count)."""
+    f = x.features
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool:
+        raise L.U3DError(f'prune: the mask must be a torch.bool tensor, got {getattr(keep, "dtype", type(keep).__name__)}')
+    if keep.dim() != 1 or keep.shape[0] != f.shape[0]:
+        raise L.U3DError(f'prune: the mask must have one entry per row: {tuple(keep.shape)} for {f.shape[0]} rows')
+    _rows_check(f, 'prune')
+    if keep.device != f.device:
+        raise L.U3DError(f'prune: the mask lives on {keep.device}, the tensor on {f.device}')
+    kept, pos, n_keep = compact_mask(keep.contiguous())
+    if n_keep == f.shape[0]:                        # every row kept: the level of x (same count as a superset = the same rows)
+        return x.replace_feature(_plain(f))
+    y = _PruneFn.apply(f, kept, pos)
+    coords = rows_take(x.indices.view(torch.float32), kept, 'prune (coordinates)').view(torch.int32) if n_keep else x.indices[:0]
+    return SparseConvTensor(y, coords, x.spatial_shape, x.batch_size)
+
+
+class SparsePrune(SparseModule):
+    """``prune`` as a module (``MinkowskiPruning``): ``forward(x, keep)``.  No parameters."""
+
+    def forward(self, x: 'SparseConvTensor', keep: torch.Tensor) -> 'SparseConvTensor':
+        return prune(x, keep)
