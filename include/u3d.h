@@ -508,6 +508,17 @@ int u3d_bias_grad(const float* dy, int64_t n, int C, float* db, void* ws, u3d_st
 int64_t u3d_bias_grad_ws_bytes(int64_t n, int C);
 
 /* =====================================================================================
+ * A1  Stand-alone ReLU of a sparse layer stack: an nn.ReLU that no batch norm precedes (csrc/relu.hip).  Flat fp32 buffers of `count`
+ *     elements, any count >= 1: every row count and channel count a layer can produce.  Not on the hot path.
+ *   u3d_relu_fwd: y[i] = x[i] > 0 ? x[i] : +0.0 (so -0.0 and NaN give +0.0).
+ *   u3d_relu_bwd: dx[i] = x[i] > 0 ? dy[i] : +0.0: the bits of dy where the unit is on, no arithmetic.
+ *   Every element written once; y / dx may be x / dy themselves.  Errors, before any HIP call and with a u3d_last_error text: U3D_EINVAL
+ *   for NULL pointers and count <= 0 (an empty tensor is the caller's business: no launch).  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+int u3d_relu_fwd(const float* x, int64_t count, float* y, u3d_stream_t stream);
+int u3d_relu_bwd(const float* x, const float* dy, int64_t count, float* dx, u3d_stream_t stream);
+
+/* =====================================================================================
  * S1  Sparse tensors on different voxel sets: union add and pruning (csrc/sparse_sets.hip).  Rows fp32 [n, C]; row maps int32.
  *   u3d_index_rows: rows_out[i] = the canonical row of coords[i] = (b, x, y, z) in the occupancy index (either form, as every entry
  *     point takes it), or -1 for a cell that is absent, outside the grid or outside the batch [0, B).  Thread = row.

@@ -129,6 +129,8 @@ PROTOTYPES = {
     'u3d_index_rows': (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     'u3d_mask_compact': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     'u3d_mask_compact_ws_bytes': (_i64, [_i64]),
+    'u3d_relu_fwd': (_i32, [_vp, _i64, _vp, _vp]),
+    'u3d_relu_bwd': (_i32, [_vp, _vp, _i64, _vp, _vp]),
     'u3d_rows_take': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'u3d_rows_take2': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'u3d_segment_gather_sum': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),

@@ -503,11 +503,30 @@ class _SparseConvFn(torch.autograd.Function):
         return dsrc, dw, None, None, (dout if ctx.has_addend else None), None
 
 
+def _conv_check(src, weight, rb: Rulebook, mode: str, addend):
+    """What must agree before a convolution over ``rb`` is launched: the feature rows with the rulebook's source level for ``mode``, their
+    width with the weight's C_in, an addend with the result.  The kernels read through bounded buffers, so a rulebook of another level
+    (a SubM ``indice_key`` met again on other rows, an inverse layer fed from the wrong level) would not fault: rows past the tensor
+    would come back as zeros and the result would be silently wrong."""
+    if mode not in ('fwd', 'inv'):
+        raise L.U3DError(f"sparse_conv: mode must be 'fwd' or 'inv', got {mode!r}")
+    where = '' if rb.tag is None else f' (rulebook {rb.tag!r})'
+    n_src, n_dst = (rb.n_in, rb.n_out) if mode == 'fwd' else (rb.n_out, rb.n_in)
+    if src.dim() != 2 or src.shape[0] != n_src:
+        raise L.U3DError(f"sparse_conv: {tuple(src.shape)} features, the rulebook has {n_src} source rows in mode '{mode}'{where}: it was "
+                         f'built for another level')
+    if src.shape[1] != weight.shape[-1]:
+        raise L.U3DError(f'sparse_conv: the features have {src.shape[1]} channels, the weight takes {weight.shape[-1]}{where}')
+    if addend is not None and tuple(addend.shape) != (n_dst, weight.shape[0]):
+        raise L.U3DError(f'sparse_conv: the addend is {tuple(addend.shape)}, the result [{n_dst}, {weight.shape[0]}]{where}')
+
+
 def sparse_conv(src, weight, rb, mode='fwd', addend=None, want_stats=False):
     """``want_stats``: a batch norm in training mode reads the result: what the launch wrote for it (``_gmm``) rides on the returned
     tensor (``stats_of``)."""
     st = {} if want_stats else None
     refuse_rows_only(src, 'sparse_conv')
+    _conv_check(src, weight, rb, mode, addend)
     dst = _SparseConvFn.apply(src, weight, rb, mode, addend, st)
     if st:
         attach_stats(dst, st['partial'], st['n_tiles'])
@@ -1123,14 +1142,38 @@ class SparseSequential(SparseModule):
         return x
 
 
+class _ReLUFn(torch.autograd.Function):
+    """y = x where x > 0, else +0.0 (u3d_relu_fwd); dx = dy where x > 0, else +0.0 (u3d_relu_bwd).  Flat buffers: any row count, zero
+    included (no launch), any channel count."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        if x.numel():
+            L.call('u3d_relu_fwd', L.ptr(x), x.numel(), L.ptr(y), L.stream())
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        if x.numel():
+            L.call('u3d_relu_bwd', L.ptr(x), L.ptr(dy), x.numel(), L.ptr(dx), L.stream())
+        return dx
+
+
 def _relu(f):
-    # stand-alone ReLU (not preceded by BN) does not occur on the hot path; identity-BN kernel reuse
-    C = f.shape[1]
-    one = torch.ones(C, device=f.device)
-    zero = torch.zeros(C, device=f.device)
-    y = torch.empty_like(f)
-    L.call('u3d_bn_apply', L.ptr(f.contiguous()), L.ptr(one), L.ptr(zero), 1, f.shape[0], C, L.ptr(y), None, L.stream())
-    return y
+    """stand-alone ReLU (an nn.ReLU that no batch norm precedes): off the hot path, differentiable.  The result is a new tensor: what a
+    layer left on ``f`` for its reader (bf16 shadow, epilogue statistics, the ``_u3d_from_conv`` mark) stays behind."""
+    refuse_rows_only(f, 'ReLU')
+    if f.dim() != 2 or f.dtype != torch.float32:
+        raise L.U3DError(f'ReLU: features must be fp32 [n, C], got {f.dtype} {tuple(f.shape)}')
+    if not f.is_cuda:
+        raise L.U3DError('ReLU: u3d kernels need CUDA (HIP) tensors: the product path has no CPU fallback')
+    return _ReLUFn.apply(f)
 
 
 def _pad16(f):
