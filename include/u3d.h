@@ -546,7 +546,35 @@ int u3d_rows_take2(const float* a, const int32_t* rows_a, int64_t n_a, const flo
                    float* y, u3d_stream_t stream);
 
 /* =====================================================================================
- * K13  self-attention core of nn.MultiheadAttention(256, 8, batch_first) per scene
+ * S2  Dense interchange of sparse tensors (csrc/sparse_dense.hip): SparseConvTensor.dense / from_dense.  Rows fp32 [n, C]; coords int32
+ *     [n, 4] = (b, x, y, z); the dense grid is fp32 [B, X, Y, Z, C] (channels_first == 0) or [B, C, X, Y, Z] (channels_first != 0),
+ *     contiguous.  Dense cell number of (b, x, y, z) = ((b X + x) Y + y) Z + z, a 32-bit number: B X Y Z < 2^31.  Element offsets are
+ *     64-bit.  Every kernel is a copy: -0.0 stays -0.0, a NaN keeps its payload; every destination element is written exactly once, no
+ *     atomics, no memset; results are bit-reproducible.
+ *   u3d_dense_scatter: dense[cell] = feats[row of the cell in the occupancy index] (either form, as every entry point takes it), +0.0
+ *     for a cell without a row.  Cell-driven: the zeros cost no second pass.  A looked-up row outside [0, n) is an absent row.
+ *     Channels last: a group of lanes per cell, 16-byte slices.  Channels first: a workgroup owns 64 consecutive cell numbers of ONE
+ *     batch item x 64 channels, rows read as 16-byte slices into a padded LDS tile, written out as 256-byte runs per channel.
+ *   u3d_dense_gather: rows[i] = dense[cell of coords[i]]; a coordinate outside the grid or the batch [0, B) (unsigned compare) gives a
+ *     row of +0.0 and reads nothing.  Row-driven: no index, no empty region touched.  Channels first: 64 consecutive rows x 64 channels
+ *     through the same tile.
+ *   u3d_dense_active: mask uint8 [n_cells] (a torch.bool tensor's bytes): 1 where any of the C values of cell i of a channels-last
+ *     grid x [n_cells, C] is != 0 (a NaN is; -0.0 is not), else 0.  Every byte written.
+ *   u3d_cells_coords: coords[i] = (b, x, y, z) of the dense cell number cells[i], one 16-byte store per row (no B: b = cell / (X Y Z)).
+ *   Contract: C % 4 == 0, 4 <= C <= 512; 1 <= n, n_cells < 2^31; B, X, Y, Z >= 1.  Errors, before any HIP call and with a
+ *   u3d_last_error text: U3D_EINVAL for NULL pointers, n <= 0 / n_cells <= 0, an empty grid, negative hash_slots; U3D_EUNSUPPORTED for
+ *   other widths, counts or grids of 2^31 and more, and a launch of 2^24 workgroups and more.  Empty inputs are the caller's business
+ *   (no launch).  Outputs must not overlap the inputs.  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+int u3d_dense_scatter(const float* feats, int64_t n, int C, const uint64_t* bitmap, const int32_t* word_rank, int64_t hash_slots, int B, int X,
+                      int Y, int Z, int channels_first, float* dense, u3d_stream_t stream);
+int u3d_dense_gather(const float* dense, int B, int X, int Y, int Z, int C, int channels_first, const int32_t* coords, int64_t n, float* rows,
+                     u3d_stream_t stream);
+int u3d_dense_active(const float* x, int64_t n_cells, int C, uint8_t* mask, u3d_stream_t stream);
+int u3d_cells_coords(const int32_t* cells, int64_t n, int X, int Y, int Z, int32_t* coords, u3d_stream_t stream);
+
+/* =====================================================================================
+ * K13 self-attention core of nn.MultiheadAttention(256, 8, batch_first) per scene
  *     (unidet3d/encoder.py:19-20,36-37): softmax(Q K^T / sqrt(hd)) V over packed variable
  *     length scenes.  qkv [n_total, 3*H*hd] (the in_proj output), cu_seqlens int32 [B+1],
  *     out [n_total, H*hd], lse [H, n_total] (log-sum-exp, saved for backward).

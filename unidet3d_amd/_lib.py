@@ -133,6 +133,11 @@ PROTOTYPES = {
     'u3d_relu_bwd': (_i32, [_vp, _vp, _i64, _vp, _vp]),
     'u3d_rows_take': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'u3d_rows_take2': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    # dense interchange of sparse tensors (csrc/sparse_dense.hip; added entry points, same ABI version)
+    'u3d_dense_scatter': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'u3d_dense_gather': (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    'u3d_dense_active': (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    'u3d_cells_coords': (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     'u3d_segment_gather_sum': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     'u3d_segment_mean_xyz': (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'u3d_segment_minmax_xyz': (_i32, [_vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),

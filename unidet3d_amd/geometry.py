@@ -2,7 +2,7 @@
 no features, no autograd, nothing of the package but the C ABI (``_lib``); ``unidet3d_amd.sparse`` re-exports the public names.
 Decided here and nowhere else: how an index is made (``OccupancyIndex.from_marks``), how a general layer's new level gets its pair lists
 (``_level_pairs``), what lives where in a ``SparseConvTensor.indice_dict`` (``cached_level``; readers ``saved_under`` / ``tensor_index``),
-how a level is made from other levels (``build_union_level``, ``compact_mask``)."""
+how a level is made from other levels (``build_union_level``, ``compact_mask``) or from a dense grid (``active_cells``, ``cells_coords``)."""
 from __future__ import annotations
 
 import ctypes
@@ -498,6 +498,42 @@ def compact_mask(keep: torch.Tensor):
     L.call('u3d_mask_compact', L.ptr(keep), n, L.ptr(kept), L.ptr(pos), L.ptr(n_dev), L.ptr(w), L.stream())
     n_keep = int(n_dev.item())             # documented read-back (one host sync), as ``OccupancyIndex.count``
     return kept[:n_keep], pos, n_keep
+
+
+# ----------------------------------------------------------------------------------------
+# levels from dense grids (csrc/sparse_dense.hip): dense cell number of (b, x, y, z) = ((b X + x) Y + y) Z + z
+# ----------------------------------------------------------------------------------------
+def dense_cells(B: int, shape, what: str) -> int:
+    """B X Y Z, refused at 2^31 and above: cell and row numbers are 32-bit (element offsets are not)"""
+    n_cells = int(B)
+    for s in shape:
+        n_cells *= int(s)
+    if int(B) < 0 or any(int(s) < 0 for s in shape):
+        raise L.U3DError(f'{what}: the grid {int(B)} x {" x ".join(str(int(s)) for s in shape)} has a negative extent')
+    if n_cells >= 1 << 31:
+        raise L.U3DError(f'{what}: the grid {int(B)} x {" x ".join(str(int(s)) for s in shape)} has {n_cells} cells, 2^31 or more: cell numbers are 32-bit')
+    return n_cells
+
+
+def active_cells(x: torch.Tensor):
+    """(kept int32 [n_active] ascending, pos int32 [n_cells], n_active) of a contiguous fp32 channels-last grid [B, X, Y, Z, C] on the
+    device: a cell is active iff any of its C values != 0 (u3d_dense_active), the mask goes through ``compact_mask``.  Ascending cell
+    number = canonical row order.  One host read, the count; a grid without cells launches nothing."""
+    C = x.shape[-1]
+    n_cells = x.numel() // C
+    mask = torch.empty(n_cells, dtype=torch.bool, device=x.device)
+    if n_cells:
+        L.call('u3d_dense_active', L.ptr(x), n_cells, C, L.ptr(mask), L.stream())
+    return compact_mask(mask)
+
+
+def cells_coords(cells: torch.Tensor, shape) -> torch.Tensor:
+    """int32 [n, 4] = (b, x, y, z) of the dense cell numbers ``cells`` int32 [n] (u3d_cells_coords); no cells, no launch"""
+    n = cells.shape[0]
+    coords = torch.empty(n, 4, dtype=torch.int32, device=cells.device)
+    if n:
+        L.call('u3d_cells_coords', L.ptr(cells.contiguous()), n, *[int(s) for s in shape], L.ptr(coords), L.stream())
+    return coords
 
 
 # ----------------------------------------------------------------------------------------

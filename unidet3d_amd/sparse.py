@@ -10,7 +10,8 @@ replace_feature / per-forward ``indice_dict`` rulebook cache keyed by
 ``SparseAvgPool3d`` on the strided convolution's geometry, ``SparseConvTranspose3d``
 (with ``output_padding``), and the two operations a generative decoder puts behind it: ``sparse_add`` (spconv's
 ``functional.sparse_add``: operands on different voxel sets, result on their union) and ``prune`` / ``SparsePrune``
-(MinkowskiEngine's ``MinkowskiPruning``: drop voxels by a mask).  Same constructor arguments, same parameter names (``weight``,
+(MinkowskiEngine's ``MinkowskiPruning``: drop voxels by a mask), and the dense interchange almost every spconv network ends with:
+``SparseConvTensor.dense`` / ``SparseConvTensor.from_dense`` / ``ToDense``.  Same constructor arguments, same parameter names (``weight``,
 ``bias`` with ``bias=True``) and weight layout ``[C_out, k, k, k, C_in]``.
 
 Every compute step is a call through the C ABI (include/u3d.h); there is no
@@ -46,7 +47,7 @@ from . import account
 from . import wgrad_stream as WS
 from .geometry import (OccupancyIndex, Rulebook, UpLevel, build_subm_rulebook, build_conv_rulebook, build_convt_rulebook, conv_geometry,
                        output_padding_of, strided_geometry, cached_level, layer_geometry, saved_under, tensor_index, _DOWN_K2S2,
-                       UnionLevel, build_union_level, compact_mask)
+                       UnionLevel, build_union_level, compact_mask, dense_cells, active_cells, cells_coords)
 from .geometry import build_down_rulebook, conv_out_shape, convt_out_shape, _geom_array, _TILE_HISTORY      # noqa: F401  (re-exported)
 from .wgrad_stream import set_wgrad_overlap, async_dw_ok, join_wgrad_stream, end_of_backward, _ASYNC_DW_SEEN      # noqa: F401  (re-exported)
 
@@ -1069,6 +1070,41 @@ class _PruneFn(torch.autograd.Function):
         return rows_take(dy.contiguous(), pos, 'prune (backward)'), None, None
 
 
+class _DenseFn(torch.autograd.Function):
+    """the rows of ``x`` in a dense grid (u3d_dense_scatter: every element written once by the kernel, +0.0 in a cell without a row);
+    backward the pure copy df[i] = d_dense[cell of row i] (u3d_dense_gather) -- autograd runs it only when the features ask for it"""
+
+    @staticmethod
+    def forward(ctx, f, x: 'SparseConvTensor', channels_first: bool):
+        B, (X, Y, Z), (n, C) = x.batch_size, x.spatial_shape, f.shape
+        ctx.geo = (x.indices, B, X, Y, Z, C, int(channels_first))
+        y = torch.empty((B, C, X, Y, Z) if channels_first else (B, X, Y, Z, C), dtype=torch.float32, device=f.device)
+        L.call('u3d_dense_scatter', L.ptr(f.contiguous()), n, C, *x.index.table(), B, X, Y, Z, int(channels_first), L.ptr(y), L.stream())
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        coords, B, X, Y, Z, C, channels_first = ctx.geo
+        df = torch.empty(coords.shape[0], C, dtype=torch.float32, device=dy.device)
+        L.call('u3d_dense_gather', L.ptr(dy.contiguous()), B, X, Y, Z, C, channels_first, L.ptr(coords), coords.shape[0], L.ptr(df), L.stream())
+        return df, None, None
+
+
+class _FromDenseFn(torch.autograd.Function):
+    """the active cells ``kept`` of a channels-last grid viewed as rows [n_cells, C]; backward dx[cell] = dy[pos[cell]], +0.0 for an
+    inactive cell (pos -1) -- both directions are u3d_rows_take, every element written"""
+
+    @staticmethod
+    def forward(ctx, cells, kept, pos):
+        ctx.save_for_backward(pos)
+        return rows_take(cells, kept, 'from_dense')
+
+    @staticmethod
+    def backward(ctx, dy):
+        (pos,) = ctx.saved_tensors
+        return rows_take(dy.contiguous(), pos, 'from_dense (backward)'), None, None
+
+
 def _plain(t: torch.Tensor) -> torch.Tensor:
     """the same values as a new tensor object: what a layer left on ``t`` for its reader (bf16 shadow, epilogue statistics, the
     ``_u3d_from_conv`` mark: attributes of the object) does not travel, as behind ``sparse_bias``"""
@@ -1096,6 +1132,56 @@ class SparseConvTensor:
             self._index = tensor_index(self.indice_dict, self.indices, self.batch_size, self.spatial_shape)
         return self._index
 
+    def dense(self, channels_first: bool = True) -> torch.Tensor:
+        """spconv's ``SparseConvTensor.dense``: a contiguous fp32 [B, C, X, Y, Z] -- [B, X, Y, Z, C] with ``channels_first=False`` -- whose
+        axes follow ``spatial_shape``.  An active cell holds exactly the bits of its feature row (-0.0 stays -0.0, a NaN keeps its
+        payload), every other cell +0.0; one kernel writes every element of the result once (u3d_dense_scatter: no memset, no
+        ``torch.zeros`` of the result).  A tensor without rows gives zeros by one fill, a zero-size result launches nothing.  No host read.
+        fp32 rows under every operand format, a multiple of 4 in 4..512 channels, fewer than 2^31 cells (B X Y Z; element offsets are
+        64-bit); bf16 rows only are refused.  The result is a plain tensor: no shadow, no statistics, no marks.  Backward: the pure copy
+        dfeatures[i] = d_dense[cell of row i] (u3d_dense_gather), run only when the features ask for a gradient.
+        ``from_dense(t.dense(channels_first=False))`` holds exactly the rows of ``t`` that are not all-zero, in order."""
+        f = self.features
+        refuse_rows_only(f, 'dense')
+        n_cells = dense_cells(self.batch_size, self.spatial_shape, 'dense')
+        _rows_check(f, 'dense')
+        if len(self.spatial_shape) != 3 or self.indices.shape[0] != f.shape[0]:
+            raise L.U3DError(f'dense: {f.shape[0]} feature rows on {self.indices.shape[0]} coordinate rows of a grid {self.spatial_shape}: a '
+                             'three-dimensional grid and one coordinate row per feature row are needed')
+        B, (X, Y, Z), C = self.batch_size, self.spatial_shape, f.shape[1]
+        shape = (B, C, X, Y, Z) if channels_first else (B, X, Y, Z, C)
+        if not n_cells:
+            return torch.empty(shape, dtype=torch.float32, device=f.device)
+        if not f.shape[0]:
+            return torch.zeros(shape, dtype=torch.float32, device=f.device)
+        return _DenseFn.apply(f, self, bool(channels_first))
+
+    @classmethod
+    def from_dense(cls, x: torch.Tensor) -> 'SparseConvTensor':
+        """spconv's ``SparseConvTensor.from_dense``: ``x`` is a contiguous fp32 [B, X, Y, Z, C] (channels last) on the device.  A cell is
+        active iff any of its C values != 0: a NaN makes a cell active, a cell of only +0.0 / -0.0 is not.  Rows in canonical order
+        (= ascending cell number ((b X + x) Y + y) Z + z), features bit copies, ``indices`` built on the device (u3d_dense_active,
+        ``compact_mask``, u3d_cells_coords, u3d_rows_take); ``spatial_shape = [X, Y, Z]``, ``batch_size = B``, a fresh, empty
+        ``indice_dict``; the occupancy index is built when a layer first asks for it.  One host read, the active count; no active cell
+        gives an empty tensor.  A multiple of 4 in 4..512 channels, fewer than 2^31 cells.  Backward: dx[cell] = dfeatures[row] for an
+        active cell, +0.0 elsewhere, every element written.
+        ``from_dense(x).dense(channels_first=False)`` equals ``x`` bit for bit, except that a -0.0 in an inactive cell comes back +0.0."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 5 or x.dtype != torch.float32:
+            raise L.U3DError(f'from_dense: the grid must be an fp32 tensor [B, X, Y, Z, C], got {getattr(x, "dtype", type(x).__name__)} '
+                             f'{tuple(getattr(x, "shape", ()))}')
+        B, X, Y, Z, C = x.shape
+        if C % 4 or not 4 <= C <= 512:
+            raise L.U3DError(f'from_dense: {C} channels: the gfx950 kernels take a multiple of 4 in 4..512')
+        n_cells = dense_cells(B, (X, Y, Z), 'from_dense')
+        if not x.is_contiguous():
+            raise L.U3DError(f'from_dense: the grid must be contiguous [B, X, Y, Z, C] (channels last), got strides {tuple(x.stride())}')
+        if not x.is_cuda:
+            raise L.U3DError('from_dense: u3d kernels need CUDA (HIP) tensors: the product path has no CPU fallback')
+        if not n_cells:
+            return cls(x.view(0, C), torch.empty(0, 4, dtype=torch.int32, device=x.device), [X, Y, Z], B)
+        kept, pos, _ = active_cells(x.detach())
+        return cls(_FromDenseFn.apply(x.view(n_cells, C), kept, pos), cells_coords(kept, (X, Y, Z)), [X, Y, Z], B)
+
 
 class SparseModule(nn.Module):
     pass
@@ -1122,6 +1208,8 @@ class SparseSequential(SparseModule):
 
     def forward(self, x: SparseConvTensor) -> SparseConvTensor:
         mods = list(self._modules.values())
+        if any(isinstance(m, ToDense) for m in mods[:-1]):
+            raise L.U3DError('SparseSequential: ToDense must come last: what it returns is a dense tensor, no layer of this library reads one')
         i = 0
         while i < len(mods):
             m = mods[i]
@@ -1437,3 +1525,14 @@ class SparsePrune(SparseModule):
 
     def forward(self, x: 'SparseConvTensor', keep: torch.Tensor) -> 'SparseConvTensor':
         return prune(x, keep)
+
+
+# ----------------------------------------------------------------------------------------
+# dense interchange: the module form of ``SparseConvTensor.dense``
+# ----------------------------------------------------------------------------------------
+class ToDense(SparseModule):
+    """spconv's ``ToDense``: ``forward(x) -> x.dense()``, fp32 [B, C, X, Y, Z].  No parameters.  In a ``SparseSequential`` it is the last
+    module -- the sequence then returns the dense tensor; a module behind it is refused."""
+
+    def forward(self, x: 'SparseConvTensor') -> torch.Tensor:
+        return x.dense()
