@@ -574,6 +574,57 @@ int u3d_dense_active(const float* x, int64_t n_cells, int C, uint8_t* mask, u3d_
 int u3d_cells_coords(const int32_t* cells, int64_t n, int X, int Y, int Z, int32_t* coords, u3d_stream_t stream);
 
 /* =====================================================================================
+ * S3  Per-scene operations on sparse tensors (csrc/sparse_scene.hip): scene ranges, top-k per scene, global max / average pooling.
+ *     coords int32 [n, 4] = (b, x, y, z) in canonical order, so the batch index ascends; rows fp32 [n, C]; offsets int32 [B + 1].
+ *   u3d_scene_offsets: offsets[b] = the first row whose batch index is >= b, offsets[B] = n; empty scenes at the start, in the middle
+ *     and at the end come out right.  Thread = row: it compares its batch index with its predecessor's and writes every entry in
+ *     between, so each entry is written exactly once (no atomics on offsets, no memset of it).  flag int32 [1] (cleared by the call):
+ *     bit 0 = a batch index descends, bit 1 = a batch index lies outside [0, B).  A flagged tensor is not in canonical order; its
+ *     offsets are unspecified, and every reader below clamps the ranges it takes from them to [0, n]: wrong values, never an access
+ *     outside a tensor.
+ *   u3d_scene_topk: scene b keeps its first min(k[b], n_b) rows in this order: key descending, then row ascending.  key = the
+ *     order-preserving integer image of the score's bits: every NaN is one key above +inf, -0.0 equals +0.0, denormals keep their value
+ *     (no floating-point instruction reads a score).  largest == 0 reverses the order of the numbers only: NaNs still come first, ties
+ *     still go to the lower row.  k int32 [B] on the device; a negative entry counts as 0.  Outputs: mask uint8 [n] (a torch.bool
+ *     tensor's bytes, every byte written), kept int32 [n] (the kept rows ascending in the first n_kept entries, the rest not touched),
+ *     pos int32 [n] (the position of every row in that list or -1, every entry written), result int32 [2] = (n_kept, the flag word of
+ *     u3d_scene_offsets): one host read serves both.  A radix select: four 8-bit histogram passes over the keys of each scene
+ *     (blocks_per_scene workgroups per scene, LDS counters, one integer atomic per non-empty bin and workgroup) give the threshold key T
+ *     and the rows strictly above it; one stable pass keeps key > T plus the first k - above rows with key == T (block counts, a scan,
+ *     a wave-64 ballot prefix).  Integer only, no floating-point atomic: one result whatever the arrival order.
+ *     ws: u3d_scene_topk_ws_bytes(n, B) bytes (0 for n <= 0 or B <= 0); the call clears what it needs of it.
+ *   u3d_scene_topk_plan (host only): rows_per_block = the rows one workgroup takes per trip of a histogram pass (and of a block of the
+ *     stable pass), blocks_per_scene = the workgroups per scene: a scene of more than rows_per_block * blocks_per_scene rows takes a
+ *     second trip.  Either pointer may be NULL.
+ *   u3d_scene_pool_fwd: y fp32 [B, C].  U3D_POOL_MAX: the rule of u3d_sparse_pool_fwd -- a strictly larger value replaces the held one,
+ *     a NaN replaces a number, ties and later NaNs keep the lower row; arg int32 [B, C] = the winning row, -1 for an empty scene, whose
+ *     y is +0.0.  U3D_POOL_AVG: the column sums of a scene in fp64, y = (float)(sum / n_b), one rounding to fp32; +0.0 for an empty
+ *     scene; arg is not touched (may be NULL).  Two passes: partials per chunk of rows_per_chunk consecutive rows of one scene (16-byte
+ *     loads, a group of lanes per row, the groups of a workgroup meet in LDS in a fixed tree), then one workgroup per scene over its
+ *     chunks in ascending order: cut into consecutive runs, one per group of lanes, each added up chunk by chunk, the runs meeting in the
+ *     same tree.  The summation order depends on (n_b, C) and the plan alone: results are bit-reproducible.
+ *     ws: u3d_scene_pool_ws_bytes(n, B, C) = max_chunks * C * 8 bytes; nothing of it needs clearing.
+ *   u3d_scene_pool_plan (host only): rows_per_chunk, max_chunks = ceil(n / rows_per_chunk) + B.  Either pointer may be NULL.
+ *   u3d_scene_pool_bwd: gather form, dx[i, c] = dy[b(i), c] where arg[b(i), c] == i, else +0.0 (max); dx[i, c] = dy[b(i), c] * inv_b
+ *     with inv_b = 1.0f / (float)n_b, each product rounded on its own (avg; arg may be NULL).  b(i) = the batch index of row i; a row
+ *     whose batch index lies outside [0, B) gets +0.0.  Every element of dx is written exactly once: no atomics, no memset.
+ *   Contract: 1 <= n < 2^31, 1 <= B <= 65535, C % 4 == 0, 4 <= C <= 512.  Errors, before any HIP call and with a u3d_last_error text:
+ *   U3D_EINVAL for NULL pointers, n <= 0, B <= 0 and an unknown mode; U3D_EUNSUPPORTED for n >= 2^31, B > 65535 and other widths.  Empty
+ *   tensors are the caller's business (no launch).  Outputs must not overlap the inputs.  Added entry points: U3D_ABI_VERSION is unchanged.
+ * ===================================================================================== */
+int u3d_scene_offsets(const int32_t* coords, int64_t n, int B, int32_t* offsets, int32_t* flag, u3d_stream_t stream);
+int u3d_scene_topk_plan(int64_t n, int B, int* rows_per_block, int* blocks_per_scene);
+int64_t u3d_scene_topk_ws_bytes(int64_t n, int B);
+int u3d_scene_topk(const float* scores, const int32_t* coords, const int32_t* offsets, const int32_t* flag, const int32_t* k, int64_t n, int B,
+                   int largest, uint8_t* mask, int32_t* kept, int32_t* pos, int32_t* result, void* ws, u3d_stream_t stream);
+int u3d_scene_pool_plan(int64_t n, int B, int C, int* rows_per_chunk, int64_t* max_chunks);
+int64_t u3d_scene_pool_ws_bytes(int64_t n, int B, int C);
+int u3d_scene_pool_fwd(const float* x, const int32_t* offsets, int64_t n, int B, int C, int mode, float* y, int32_t* arg, void* ws,
+                       u3d_stream_t stream);
+int u3d_scene_pool_bwd(const float* dy, const int32_t* coords, const int32_t* offsets, const int32_t* arg, int64_t n, int B, int C, int mode,
+                       float* dx, u3d_stream_t stream);
+
+/* =====================================================================================
  * K13 self-attention core of nn.MultiheadAttention(256, 8, batch_first) per scene
  *     (unidet3d/encoder.py:19-20,36-37): softmax(Q K^T / sqrt(hd)) V over packed variable
  *     length scenes.  qkv [n_total, 3*H*hd] (the in_proj output), cu_seqlens int32 [B+1],

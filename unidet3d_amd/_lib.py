@@ -138,6 +138,15 @@ PROTOTYPES = {
     'u3d_dense_gather': (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     'u3d_dense_active': (_i32, [_vp, _i64, _i32, _vp, _vp]),
     'u3d_cells_coords': (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    # per-scene operations on sparse tensors (csrc/sparse_scene.hip; added entry points, same ABI version)
+    'u3d_scene_offsets': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    'u3d_scene_topk_plan': (_i32, [_i64, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    'u3d_scene_topk_ws_bytes': (_i64, [_i64, _i32]),
+    'u3d_scene_topk': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'u3d_scene_pool_plan': (_i32, [_i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
+    'u3d_scene_pool_ws_bytes': (_i64, [_i64, _i32, _i32]),
+    'u3d_scene_pool_fwd': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'u3d_scene_pool_bwd': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     'u3d_segment_gather_sum': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     'u3d_segment_mean_xyz': (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'u3d_segment_minmax_xyz': (_i32, [_vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),

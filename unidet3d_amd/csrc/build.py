@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ['misc.hip', 'voxelize.hip', 'rulebook.hip', 'spconv.hip', 'spconv_wg.hip', 'spconv_ts.hip', 'spconv_wgrad_rows.hip', 'spconv_wgrad_blk.hip', 'bn.hip', 'pool.hip', 'sparse_pool.hip', 'sparse_bias.hip', 'sparse_sets.hip', 'sparse_dense.hip', 'relu.hip', 'attn.hip', 'attn_x3.hip', 'gemm.hip', 'gemm_b16.hip', 'norm.hip', 'postproc.hip', 'criterion.hip', 'hashidx.hip', 'radix.hip', 'augment.hip', 'targets.hip', 'optim.hip', 'evalmap.hip']
+SOURCES = ['misc.hip', 'voxelize.hip', 'rulebook.hip', 'spconv.hip', 'spconv_wg.hip', 'spconv_ts.hip', 'spconv_wgrad_rows.hip', 'spconv_wgrad_blk.hip', 'bn.hip', 'pool.hip', 'sparse_pool.hip', 'sparse_bias.hip', 'sparse_sets.hip', 'sparse_dense.hip', 'sparse_scene.hip', 'relu.hip', 'attn.hip', 'attn_x3.hip', 'gemm.hip', 'gemm_b16.hip', 'norm.hip', 'postproc.hip', 'criterion.hip', 'hashidx.hip', 'radix.hip', 'augment.hip', 'targets.hip', 'optim.hip', 'evalmap.hip']
 LIB = os.path.join(HERE, 'libu3d_hip.so')
 # (no -munsafe-fp-atomics: since round 5 no kernel of the library issues a floating-point atomic -- every reduction has a fixed order)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value',
@@ -24,7 +24,7 @@ EXTRA = {'spconv.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
          'optim.hip': ['-ffp-contract=off'],                        # the dwordx4 and the dword path of a row round alike
          'evalmap.hip': ['-ffp-contract=off']}                      # bit-exact against evaluation.boxes_iou_3d's axis-aligned IoU
 # (sparse_pool.hip turns contraction off in the source, `#pragma clang fp contract(off)`: its sums round term by term, in offset order;
-#  sparse_bias.hip and sparse_sets.hip likewise)
+#  sparse_bias.hip, sparse_sets.hip and sparse_scene.hip likewise)
 
 
 def _hipcc():

@@ -104,7 +104,7 @@ class OccupancyIndex:
             L.call('u3d_hash_index_coords', L.ptr(self.ukeys), n, *self.shape, L.ptr(c), L.stream())
         elif n:
             L.call('u3d_index_coords', L.ptr(self.bitmap), L.ptr(self.rank), self.B, *self.shape, L.ptr(c), L.stream())
-        return c
+        return mark_canonical(c)
 
     def rows_of(self, coords: torch.Tensor) -> torch.Tensor:
         """int32 [n]: the canonical row of every coordinate (int32 [n, 4] = (b, x, y, z)) in this index, -1 for a cell that is absent or
@@ -533,7 +533,49 @@ def cells_coords(cells: torch.Tensor, shape) -> torch.Tensor:
     coords = torch.empty(n, 4, dtype=torch.int32, device=cells.device)
     if n:
         L.call('u3d_cells_coords', L.ptr(cells.contiguous()), n, *[int(s) for s in shape], L.ptr(coords), L.stream())
+    return mark_canonical(coords)
+
+
+# ----------------------------------------------------------------------------------------
+# scene ranges (csrc/sparse_scene.hip, include/u3d.h section S3)
+# ----------------------------------------------------------------------------------------
+# Coordinate rows that this library wrote itself (``OccupancyIndex.coords``, ``cells_coords``, a subset of such rows taken in order) are in
+# canonical order by construction: they carry a mark, an attribute of the tensor object as a bf16 shadow is one of its features.  Rows a
+# caller hands in carry none until a reader of the order flag has seen it clear (``check_scene_order``).
+def mark_canonical(coords: torch.Tensor) -> torch.Tensor:
+    coords._u3d_canonical = True
     return coords
+
+
+def is_canonical(coords: torch.Tensor) -> bool:
+    return getattr(coords, '_u3d_canonical', False)
+
+
+def scene_offsets(indices: torch.Tensor, B: int):
+    """(offsets int32 [B + 1], flag int32 [1]) of coordinate rows int32 [n, 4] in canonical order, on their device: offsets[b] = the first
+    row whose batch index is >= b, offsets[B] = n (u3d_scene_offsets: thread = row, every entry written once).  flag != 0: a batch index
+    descends (bit 0) or lies outside [0, B) (bit 1) -- ``check_scene_order`` turns a flag value into the error.  No host read; no rows
+    gives zeros without a launch."""
+    if not isinstance(B, int) or isinstance(B, bool) or B < 1:
+        raise L.U3DError(f'scene_offsets: batch_size must be an int >= 1, got {B!r}')
+    if indices.dim() != 2 or indices.shape[1] != 4 or indices.dtype != torch.int32:
+        raise L.U3DError(f'scene_offsets: coordinates must be int32 [n, 4], got {indices.dtype} {tuple(indices.shape)}')
+    n, dev = indices.shape[0], indices.device
+    if not n:
+        buf = torch.zeros(B + 2, dtype=torch.int32, device=dev)
+        return buf[:B + 1], buf[B + 1:]
+    buf = torch.empty(B + 2, dtype=torch.int32, device=dev)
+    offsets, flag = buf[:B + 1], buf[B + 1:]
+    L.call('u3d_scene_offsets', L.ptr(indices.contiguous()), n, B, L.ptr(offsets), L.ptr(flag), L.stream())
+    return offsets, flag
+
+
+def check_scene_order(flag: int, what: str, B: int):
+    """raise for a non-zero order flag of ``scene_offsets``, naming the first thing that can be said about the violation"""
+    if flag & 2:
+        raise L.U3DError(f'{what}: a batch index lies outside [0, {B}): the tensor is not in canonical order (ascending ((b X + x) Y + y) Z + z)')
+    if flag & 1:
+        raise L.U3DError(f'{what}: the batch indices descend: the tensor is not in canonical order (ascending ((b X + x) Y + y) Z + z)')
 
 
 # ----------------------------------------------------------------------------------------

@@ -11,7 +11,8 @@ replace_feature / per-forward ``indice_dict`` rulebook cache keyed by
 (with ``output_padding``), and the two operations a generative decoder puts behind it: ``sparse_add`` (spconv's
 ``functional.sparse_add``: operands on different voxel sets, result on their union) and ``prune`` / ``SparsePrune``
 (MinkowskiEngine's ``MinkowskiPruning``: drop voxels by a mask), and the dense interchange almost every spconv network ends with:
-``SparseConvTensor.dense`` / ``SparseConvTensor.from_dense`` / ``ToDense``.  Same constructor arguments, same parameter names (``weight``,
+``SparseConvTensor.dense`` / ``SparseConvTensor.from_dense`` / ``ToDense``, and the per-scene operations: ``topk_mask`` / ``prune_topk`` /
+``SparseTopKPrune`` (the k best-scored voxels of every scene) and ``global_pool`` / ``SparseGlobalMaxPool`` / ``SparseGlobalAvgPool``.  Same constructor arguments, same parameter names (``weight``,
 ``bias`` with ``bias=True``) and weight layout ``[C_out, k, k, k, C_in]``.
 
 Every compute step is a call through the C ABI (include/u3d.h); there is no
@@ -47,7 +48,8 @@ from . import account
 from . import wgrad_stream as WS
 from .geometry import (OccupancyIndex, Rulebook, UpLevel, build_subm_rulebook, build_conv_rulebook, build_convt_rulebook, conv_geometry,
                        output_padding_of, strided_geometry, cached_level, layer_geometry, saved_under, tensor_index, _DOWN_K2S2,
-                       UnionLevel, build_union_level, compact_mask, dense_cells, active_cells, cells_coords)
+                       UnionLevel, build_union_level, compact_mask, dense_cells, active_cells, cells_coords, scene_offsets,
+                       check_scene_order, mark_canonical, is_canonical)
 from .geometry import build_down_rulebook, conv_out_shape, convt_out_shape, _geom_array, _TILE_HISTORY      # noqa: F401  (re-exported)
 from .wgrad_stream import set_wgrad_overlap, async_dw_ok, join_wgrad_stream, end_of_backward, _ASYNC_DW_SEEN      # noqa: F401  (re-exported)
 
@@ -1122,9 +1124,25 @@ class SparseConvTensor:
         self.batch_size = int(batch_size)
         self.indice_dict = {} if indice_dict is None else indice_dict
         self._index = index
+        self._scene = None
 
     def replace_feature(self, new_features):
-        return SparseConvTensor(new_features, self.indices, self.spatial_shape, self.batch_size, self.indice_dict, self._index)
+        t = SparseConvTensor(new_features, self.indices, self.spatial_shape, self.batch_size, self.indice_dict, self._index)
+        t._scene = self._scene                     # the result shares ``indices``: the same scene ranges
+        return t
+
+    def _scene_ranges(self):
+        """offsets, order flag (device tensors) and whether the flag has been seen clear; built on first use, no host read"""
+        if self._scene is None:
+            offsets, flag = scene_offsets(self.indices, self.batch_size)
+            self._scene = SimpleNamespace(offsets=offsets, flag=flag, checked=is_canonical(self.indices) or not self.indices.shape[0])
+        return self._scene
+
+    @property
+    def scene_offsets(self) -> torch.Tensor:
+        """int32 [batch_size + 1] on the device: scene b owns the rows offsets[b] .. offsets[b + 1] of the canonical order (empty scenes
+        included).  Cached on the tensor; ``replace_feature`` carries it.  u3d_scene_offsets, no host read."""
+        return self._scene_ranges().offsets
 
     @property
     def index(self) -> OccupancyIndex:
@@ -1210,6 +1228,10 @@ class SparseSequential(SparseModule):
         mods = list(self._modules.values())
         if any(isinstance(m, ToDense) for m in mods[:-1]):
             raise L.U3DError('SparseSequential: ToDense must come last: what it returns is a dense tensor, no layer of this library reads one')
+        for m in mods[:-1]:
+            if getattr(m, 'returns_dense', False):
+                raise L.U3DError(f'SparseSequential: {type(m).__name__} must come last: what it returns is a dense tensor [B, C], no layer of '
+                                 'this library reads one')
         i = 0
         while i < len(mods):
             m = mods[i]
@@ -1525,6 +1547,191 @@ class SparsePrune(SparseModule):
 
     def forward(self, x: 'SparseConvTensor', keep: torch.Tensor) -> 'SparseConvTensor':
         return prune(x, keep)
+
+
+# ----------------------------------------------------------------------------------------
+# per-scene operations (csrc/sparse_scene.hip, include/u3d.h section S3): top-k pruning, global pooling
+# ----------------------------------------------------------------------------------------
+# The order flag of a tensor's scene ranges is read by the host at most once per voxel set, and never on its own where another value is
+# read anyway: ``topk_mask`` / ``prune_topk`` read it in the same host read as the kept count.  ``global_pool`` reads no count, so it reads
+# the flag only for a tensor whose coordinate rows this library did not write itself (``geometry.is_canonical``: rows from an index, from a
+# dense grid, or a subset of checked rows are canonical by construction) -- once, on first use; ``replace_feature`` carries the verdict.
+def _scene_order_seen(x: 'SparseConvTensor', flag: int, what: str):
+    check_scene_order(flag, what, x.batch_size)
+    x._scene_ranges().checked = True
+    mark_canonical(x.indices)
+
+
+def _topk_check(x: 'SparseConvTensor', scores, k, what: str):
+    """the refusals of the top-k family, before any launch; returns (scores fp32 [n] contiguous, the B counts)"""
+    f = x.features
+    refuse_rows_only(f, what)
+    n, B = f.shape[0], x.batch_size
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32:
+        raise L.U3DError(f'{what}: the scores must be a torch.float32 tensor, got {getattr(scores, "dtype", type(scores).__name__)}')
+    if tuple(scores.shape) not in ((n,), (n, 1)):
+        raise L.U3DError(f'{what}: the scores must have one entry per row, [n] or [n, 1]: {tuple(scores.shape)} for {n} rows')
+    if isinstance(k, int) and not isinstance(k, bool):
+        ks = [int(k)] * B
+    else:
+        try:
+            ks = list(k)
+        except TypeError:
+            ks = None
+        if ks is None or isinstance(k, (str, torch.Tensor)) or any(isinstance(v, bool) or not isinstance(v, int) for v in ks):
+            raise L.U3DError(f'{what}: k must be an int or a sequence of ints (host values), got {type(k).__name__}')
+        if len(ks) != B:
+            raise L.U3DError(f'{what}: k must have one entry per scene: {len(ks)} for batch_size {B}')
+    if any(v < 0 for v in ks):
+        raise L.U3DError(f'{what}: k must be >= 0, got {min(ks)}')
+    if scores.device != f.device:
+        raise L.U3DError(f'{what}: the scores live on {scores.device}, the tensor on {f.device}')
+    _rows_check(f, what)
+    return scores.detach().reshape(n).contiguous(), [min(v, 0x7fffffff) for v in ks]
+
+
+def _scene_topk(x: 'SparseConvTensor', scores, k, largest, what: str):
+    """(mask bool [n], kept int32 [n_keep], pos int32 [n], n_keep) of the top-k rows of every scene (u3d_scene_topk).  One host read:
+    the kept count together with the order flag.  No rows: nothing launched, nothing read."""
+    s, ks = _topk_check(x, scores, k, what)
+    n, B, dev = s.shape[0], x.batch_size, s.device
+    mask = torch.empty(n, dtype=torch.bool, device=dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    pos = torch.empty(n, dtype=torch.int32, device=dev)
+    if not n:
+        return mask, kept, pos, 0
+    sc = x._scene_ranges()
+    result = torch.empty(2, dtype=torch.int32, device=dev)
+    w = L.ws(L.lib().u3d_scene_topk_ws_bytes(n, B), dev)
+    L.call('u3d_scene_topk', L.ptr(s), L.ptr(x.indices.contiguous()), L.ptr(sc.offsets), L.ptr(sc.flag), L.ptr(L.h2d(ks, torch.int32, dev)), n, B,
+           1 if largest else 0, L.ptr(mask), L.ptr(kept), L.ptr(pos), L.ptr(result), L.ptr(w), L.stream())
+    n_keep, flag = result.tolist()             # documented read-back (one host sync): the kept count and the order flag
+    _scene_order_seen(x, flag, what)
+    return mask, kept[:n_keep], pos, n_keep
+
+
+def topk_mask(x: 'SparseConvTensor', scores: torch.Tensor, k, largest: bool = True) -> torch.Tensor:
+    """torch.bool [n]: the mask of the ``k`` best-scored voxels of EVERY scene of ``x`` (the ``_prune`` step of FCAF3D / TR3D necks), for
+    ``prune``.  ``scores``: fp32 [n] or [n, 1] on the tensor's device, no gradient.  ``k``: an int >= 0 or a sequence of batch_size such
+    ints (host values).  Scene b keeps its first min(k_b, n_b) rows of this order -- that of a stable descending sort, defined here because
+    ``torch.topk`` leaves ties unspecified: score descending, then row ascending; every NaN ranks above +inf and all NaNs are equal; -0.0
+    equals +0.0; denormals keep their value (the comparison is on integer keys, nothing is flushed).  ``largest=False`` reverses the score
+    order only: NaNs still rank first, ties still go to the lower row.  One chain of launches for the whole batch (u3d_scene_topk: radix
+    select, integer only, deterministic) and ONE host read, the kept count together with the order flag of the scene ranges: a tensor
+    whose batch indices descend or leave [0, batch_size) raises.  fp32 rows under every operand format; bf16 rows only are refused."""
+    return _scene_topk(x, scores, k, largest, 'topk_mask')[0]
+
+
+def prune_topk(x: 'SparseConvTensor', scores: torch.Tensor, k, largest: bool = True) -> 'SparseConvTensor':
+    """``prune(x, topk_mask(x, scores, k, largest))`` in every bit and in what it does to levels, without the mask's round trip: the select
+    writes the kept list and the positions itself.  A new voxel set starts from a fresh, empty ``indice_dict``; every row kept keeps the
+    level of ``x``; nothing kept gives an empty tensor.  Backward as ``prune`` (``_PruneFn``).  One host read (the kept count, with the
+    order flag)."""
+    _, kept, pos, n_keep = _scene_topk(x, scores, k, largest, 'prune_topk')
+    f = x.features
+    if n_keep == f.shape[0]:
+        return x.replace_feature(_plain(f))
+    y = _PruneFn.apply(f, kept, pos)
+    coords = rows_take(x.indices.view(torch.float32), kept, 'prune_topk (coordinates)').view(torch.int32) if n_keep else x.indices[:0]
+    return SparseConvTensor(y, mark_canonical(coords), x.spatial_shape, x.batch_size)      # (rows of a checked order, taken in order)
+
+
+class SparseTopKPrune(SparseModule):
+    """``prune_topk`` as a module: ``SparseTopKPrune(k, largest=True)``, ``forward(x, scores)``.  No parameters."""
+
+    def __init__(self, k, largest: bool = True):
+        super().__init__()
+        ok = isinstance(k, int) and not isinstance(k, bool) or (isinstance(k, (list, tuple)) and
+                                                                  all(isinstance(v, int) and not isinstance(v, bool) for v in k))
+        if not ok:
+            raise L.U3DError(f'SparseTopKPrune: k must be an int or a sequence of ints (host values), got {type(k).__name__}')
+        if (k if isinstance(k, int) else min(k, default=0)) < 0:
+            raise L.U3DError(f'SparseTopKPrune: k must be >= 0, got {k if isinstance(k, int) else min(k)}')
+        self.k, self.largest = (k if isinstance(k, int) else list(k)), bool(largest)
+
+    def forward(self, x: 'SparseConvTensor', scores: torch.Tensor) -> 'SparseConvTensor':
+        return prune_topk(x, scores, self.k, self.largest)
+
+
+def _global_pool_check(x: 'SparseConvTensor', mode: str):
+    if mode not in _POOL_MODES:
+        raise L.U3DError(f"global_pool: mode must be 'max' or 'avg', got {mode!r}")
+    _rows_check(x.features, 'global_pool')
+    if x.indices.shape[0] != x.features.shape[0]:
+        raise L.U3DError(f'global_pool: {x.features.shape[0]} feature rows on {x.indices.shape[0]} coordinate rows')
+
+
+def global_pool_forward(f: torch.Tensor, x: 'SparseConvTensor', mode: str):
+    """(y fp32 [B, C], arg) without autograd: arg is int32 [B, C], the winning row of every element (-1 for an empty scene), for 'max'
+    and None for 'avg'.  No host read on rows this library wrote; see the rule above for others."""
+    n, C = f.shape
+    B, dev = x.batch_size, f.device
+    sc = x._scene_ranges()
+    if not sc.checked:
+        _scene_order_seen(x, int(sc.flag.item()), 'global_pool')          # rows a caller handed in: the flag's own read, once per voxel set
+    y = torch.empty(B, C, dtype=torch.float32, device=dev)
+    arg = torch.empty(B, C, dtype=torch.int32, device=dev) if mode == 'max' else None
+    w = L.ws(L.lib().u3d_scene_pool_ws_bytes(n, B, C), dev)
+    L.call('u3d_scene_pool_fwd', L.ptr(f.contiguous()), L.ptr(sc.offsets), n, B, C, _POOL_MODES[mode], L.ptr(y), L.ptr(arg), L.ptr(w), L.stream())
+    return y, arg
+
+
+def global_pool_backward(dy: torch.Tensor, indices: torch.Tensor, offsets: torch.Tensor, mode: str, arg) -> torch.Tensor:
+    """dx [n, C] from dy [B, C]: every element written by the kernel (u3d_scene_pool_bwd, gather form)"""
+    n, (B, C) = indices.shape[0], dy.shape
+    dx = torch.empty(n, C, dtype=torch.float32, device=dy.device)
+    L.call('u3d_scene_pool_bwd', L.ptr(dy.contiguous()), L.ptr(indices.contiguous()), L.ptr(offsets), L.ptr(arg), n, B, C, _POOL_MODES[mode],
+           L.ptr(dx), L.stream())
+    return dx
+
+
+class _GlobalPoolFn(torch.autograd.Function):
+    """Saves the winning rows (max) or nothing (avg: the scene ranges suffice), and neither x nor y."""
+
+    @staticmethod
+    def forward(ctx, f, x: 'SparseConvTensor', mode: str):
+        y, arg = global_pool_forward(f, x, mode)
+        ctx.save_for_backward(*([arg] if arg is not None else []))
+        ctx.geo = (x.indices, x.scene_offsets, mode)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        indices, offsets, mode = ctx.geo
+        arg = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        return global_pool_backward(dy, indices, offsets, mode, arg), None, None
+
+
+def global_pool(x: 'SparseConvTensor', mode: str) -> torch.Tensor:
+    """Global pooling of every scene of ``x`` (spconv's ``SparseGlobalMaxPool`` / ``SparseGlobalAvgPool``, MinkowskiEngine's global
+    pooling): fp32 [batch_size, C], a plain dense tensor.  'max': the rule of the pooling layers -- a strictly larger value replaces the held
+    one, a NaN replaces a number, ties and later NaNs keep the lower row; the gradient goes to the winning row alone.  'avg': the column
+    sums of a scene in fp64 in a fixed order, y = (float)(sum / n_b), one rounding; the gradient is dy * (1.0f / n_b).  An empty scene
+    gives a row of +0.0 and takes no gradient.  Several workgroups per scene, no atomics: bit-reproducible.  No host read (for coordinate
+    rows handed in by the caller, the order flag is read once per voxel set).  A multiple of 4 in 4..512 channels, fp32 rows under every
+    operand format; bf16 rows only are refused.  No rows gives zeros [batch_size, C] without a launch."""
+    _global_pool_check(x, mode)
+    f = x.features
+    if not f.shape[0]:
+        return torch.zeros(x.batch_size, f.shape[1], dtype=torch.float32, device=f.device)
+    return _GlobalPoolFn.apply(f, x, mode)
+
+
+class SparseGlobalMaxPool(SparseModule):
+    """``global_pool(x, 'max')`` as a module (spconv's ``SparseGlobalMaxPool``).  No parameters.  In a ``SparseSequential`` it is the last
+    module -- the sequence then returns the dense [B, C] tensor; a module behind it is refused."""
+    returns_dense = True
+
+    def forward(self, x: 'SparseConvTensor') -> torch.Tensor:
+        return global_pool(x, 'max')
+
+
+class SparseGlobalAvgPool(SparseModule):
+    """``global_pool(x, 'avg')`` as a module (spconv's ``SparseGlobalAvgPool``); otherwise as ``SparseGlobalMaxPool``."""
+    returns_dense = True
+
+    def forward(self, x: 'SparseConvTensor') -> torch.Tensor:
+        return global_pool(x, 'avg')
 
 
 # ----------------------------------------------------------------------------------------
